@@ -88,6 +88,32 @@ def roofline_key(model, seen, dt_code, B, S):
 
 
 NBATCH = 4
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE = 1 << 20  # parameter / EMA values written by --dump-outputs (a fixed, seeded sample when the model has more)
+
+
+def flat_sample(tensors, n=DUMP_SAMPLE, seed=0):
+    """every floating-point value of `tensors` (in order, as float32) when there are at most n, else a fixed seeded sample of n of them"""
+    flat = torch.cat([t.detach().reshape(-1).float() for t in tensors if t.is_floating_point()])
+    if flat.numel() <= n:
+        return flat.cpu()
+    idx = torch.randperm(flat.numel(), generator=torch.Generator().manual_seed(seed))[:n].sort().values
+    return flat[idx.to(flat.device)].cpu()
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: one float32 / float64 .npy per array; at most DUMP_LIMIT_BYTES in all"""
+    import numpy as np
+    out = {}
+    for k, v in arrays.items():
+        a = v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)
+        out[k] = a if a.dtype in (np.float32, np.float64) else a.astype(np.float32)
+    total = sum(a.nbytes for a in out.values())
+    assert total <= DUMP_LIMIT_BYTES, f"--dump-outputs: {total} bytes > {DUMP_LIMIT_BYTES}"
+    os.makedirs(path, exist_ok=True)
+    for k, a in out.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+    log(f"dumped {len(out)} arrays ({total / 1e6:.1f} MB) to {path}")
 
 
 def spawn_ranks(n, argv):
@@ -175,6 +201,11 @@ def main(argv=None):
     ap.add_argument("--no-val-batch", action="store_true", help="skip the second inference leg at the reference's validation batch (2 x --batch, engine/trainer.py:297)")
     ap.add_argument("--infer-mode", default="graph", choices=["graph", "eager"],
                     help="inference leg: replay the eval forward + postprocess from one captured hipGraph per batch (default), or launch eagerly")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the run, write what the last timed step of every leg computed as DIR/<name>.npy (rank 0): loss, loss items and a "
+                         "seeded sample of the updated parameters and EMA weights of the eager train leg (train_eager_*) and of the hipGraph one "
+                         "(train_graph_*, when it runs), and the detections of the last inference call (infer_*).  Which legs are written "
+                         "depends on the arguments alone, never on which leg was faster")
     args = ap.parse_args(argv)
     if args.gpus > 1 and not args.no_phases:
         args.phases = True  # four event records per step; the exposed all-reduce time is what a scaling run is read for
@@ -229,6 +260,7 @@ def main(argv=None):
     batch = batches[0]
     counter = [0]
     phase_ev = []
+    last_loss = [None]
 
     def step():
         bt = batches[counter[0] % NBATCH]
@@ -237,6 +269,8 @@ def main(argv=None):
         if ev:
             ev[0].record()
         loss, items = net(bt)
+        if args.dump_outputs:
+            last_loss[0] = loss.detach()
         if reducer is not None:
             loss.backward()   # SUM all-reduce of the unscaled losses' gradients == reference's loss * world + averaged gradients
             if ev:
@@ -297,6 +331,15 @@ def main(argv=None):
     assert torch.isfinite(items).all(), f"non-finite loss items {items}"
     train_ips = world * B * args.steps / dt_s
 
+    dumped = {}
+
+    def keep_train_outputs(leg, loss, items):  # --dump-outputs: what the last step of a train leg handed back, and the weights it left behind
+        if args.dump_outputs and rank == 0:
+            dumped.update({f"train_{leg}_loss": loss.detach().float().reshape(1).cpu(), f"train_{leg}_loss_items": items.detach().float().cpu(),
+                           f"train_{leg}_params_sample": flat_sample(list(model.parameters())),
+                           f"train_{leg}_ema_sample": flat_sample(list(ema.ema.state_dict().values())) if ema is not None else None})
+    keep_train_outputs("eager", last_loss[0], items)
+
     train_graph_ips = None
     if not args.no_train_graph and net is model:
         # the same step - forward, loss, backward, (N > 1: the reducer's bucket all-reduces on their side stream,) clip, SGD - replayed
@@ -354,6 +397,7 @@ def main(argv=None):
                 dist.all_reduce(tgm, op=dist.ReduceOp.MAX)
             tg = float(tgm)
             assert torch.isfinite(gitems).all(), f"non-finite loss items from the graphed step {gitems}"
+            keep_train_outputs("graph", gl, gitems)
             train_graph_ips = world * B * args.steps / tg
             log(f"graph-replayed train step: {1e3 * tg / args.steps:.2f} ms/step ({train_graph_ips:.1f} images/s)")
             opt.zero_grad(set_to_none=True)
@@ -369,6 +413,7 @@ def main(argv=None):
     # hipGraph per batch (yolov10-3d_amd/graph.py; --infer-mode eager keeps the launch-by-launch loop); the eager rate is reported next to it
     model.eval()
     infer_ips = infer_eager_ips = infer_val_ips = None
+    infer_last = None
     infer_mode = args.infer_mode
     roof_infer = None
     nc = model.yaml["nc"]
@@ -416,14 +461,20 @@ def main(argv=None):
                                   "achieved": round(eflops / (ems * 1e-3) / 1e12, 2), "peak": peak, "unit": "TFLOP/s",
                                   "frac": round(eflops / (ems * 1e-3) / 1e12 / peak, 4), "launches_timed": len(etimes), "avg_launch_ms": round(ems, 4),
                                   "flops_per_launch": eflops, "traffic": None}
-            infer_eager_ips = timed_infer(lambda: infer_once(batch["img"]), args.infer_steps)
+            eager_last = [None]
+
+            def infer_eager():
+                eager_last[0] = infer_once(batch["img"])
+            infer_eager_ips = timed_infer(infer_eager, args.infer_steps)
             infer_ips = infer_eager_ips
+            infer_last = eager_last[0]
             if infer_mode == "graph":
                 try:
                     from yolov10_3d_amd.graph import GraphedForward
                     gf = GraphedForward(infer_once, batch["img"])
                     gf(gf.inputs[0])
                     infer_ips = timed_infer(lambda: gf(gf.inputs[0]), args.infer_steps)
+                    infer_last = tuple(t.clone() for t in gf.outputs)  # the replays' static outputs (the val-batch leg below reuses the pool)
                 except Exception as e:  # a capture failure must not cost the run its train number
                     log(f"hipGraph capture of the eval forward failed ({type(e).__name__}: {e}); reporting the eager rate")
                     infer_mode = "eager"
@@ -500,6 +551,10 @@ def main(argv=None):
             bt = reducer.times() if reducer is not None else None
             if bt:
                 out["phases_ms"]["buckets"] = [{"MB": round(nb / 1e6, 1), "ready_to_done_ms": round(a, 3), "allreduce_ms": round(b, 3)} for nb, a, b in bt]
+        if args.dump_outputs:
+            if infer_last is not None:
+                dumped.update(zip(("infer_boxes", "infer_scores", "infer_labels"), infer_last))
+            dump_outputs(args.dump_outputs, {k: v for k, v in dumped.items() if v is not None})
         print(json.dumps(out))
     if dist.is_initialized():
         dist.destroy_process_group()
