@@ -80,6 +80,28 @@ int y3d_conv_stat_blocks(int B, int Ho, int Wo);
 /* number of BatchNorm partial rows y3d_conv2d_fwd emits for this geometry (depends on the kernel it dispatches to:
  * 3x3 s1 p1 convs with 128-byte channel slabs run the resident-halo tile kernel, one row per TH x 16 pixel tile) */
 int y3d_conv2d_stat_rows(int dtype, int B, int H, int W, int Cin, int Cout, int groups, int kh, int kw, int stride, int pad);
+/* the kernel a convolution entry point launches for this geometry, with pixel-dense NHWC operands (a view that is not pixel-dense
+ * can only move a 1x1 conv or a stride-2 data gradient off its streaming / resident kernel).  op: Y3D_OP_*; epi (forward only, else
+ * 0): Y3D_EPI_*.  Returns a Y3D_ROUTE_* code, or Y3D_ERR_INVALID where the entry point refuses the geometry (y3d_last_error says
+ * why).  y3d_conv2d_fwd / _fwd_affine / _fwd_affine_res, y3d_conv2d_bwd_data and y3d_conv2d_bwd_weight dispatch on this decision. */
+enum { Y3D_OP_FWD = 0, Y3D_OP_BWD_DATA = 1, Y3D_OP_BWD_WEIGHT = 2 };
+enum { Y3D_EPI_RAW = 0, Y3D_EPI_PARTIALS = 1, Y3D_EPI_AFFINE = 2, Y3D_EPI_AFFINE_RES = 3, Y3D_EPI_BIAS = 4 };
+enum {
+  Y3D_ROUTE_GENERIC = 0,          /* conv_gemm.hip: implicit GEMM (forward, data gradient) / split-K weight gradient */
+  Y3D_ROUTE_STREAM1X1 = 1,        /* conv1x1_stream.hip */
+  Y3D_ROUTE_SMALL = 2,            /* conv3x3_small.hip, stride 1 */
+  Y3D_ROUTE_SMALL_S2 = 3,         /* conv3x3_small.hip, stride 2 (forward) */
+  Y3D_ROUTE_S2_DGRAD = 4,         /* conv3x3s2_dgrad.hip */
+  Y3D_ROUTE_TILE8 = 5,            /* conv3x3_tile.hip, 8-row tiles */
+  Y3D_ROUTE_TILE16 = 6,           /* conv3x3_tile.hip, 16-row tiles */
+  Y3D_ROUTE_WIDE3_8 = 7,          /* conv3x3_wide3.hip, 8-row tiles (also ragged heights) */
+  Y3D_ROUTE_WIDE3_16 = 8,         /* conv3x3_wide3.hip, 16-row tiles */
+  Y3D_ROUTE_FLAT = 9,             /* conv3x3_flat.hip */
+  Y3D_ROUTE_WGRAD_SMALL = 10,     /* wgrad3x3_small.hip */
+  Y3D_ROUTE_WGRAD_TILE = 11,      /* conv3x3_wgrad_tile.hip */
+  Y3D_ROUTE_WGRAD_STREAM1X1 = 12  /* wgrad1x1_stream.hip */
+};
+int y3d_conv2d_route(int dtype, int op, int epi, int B, int H, int W, int Cin, int Cout, int groups, int kh, int kw, int stride, int pad);
 /* y = conv(x, w) (+bias).  stat_partials (optional, no bias): [y3d_conv_stat_blocks][Cout][2] = per-block (sum, sum^2) of y. */
 int y3d_conv2d_fwd(int dtype, const void* x, int64_t xsb, int64_t xsh, int64_t xsw, int B, int H, int W, int Cin,
                    const void* w_packed, const float* bias, void* y, int64_t ysw, int Ho, int Wo, int Cout, int groups,

@@ -31,6 +31,59 @@ def test_host_side_helpers_without_gpu():
     assert 1 <= L.conv2d_wgrad_splits(_lib.BF16, 32, 80, 80, 128, 128, 1, 3, 3) <= 256
 
 
+def route_codes():
+    """{name: code} of the Y3D_ROUTE_* enum, read from the header (the codes have no second definition)"""
+    src = open(os.path.join(ROOT, "include", "y3d.h")).read()
+    return {k: int(v) for k, v in re.findall(r"\bY3D_ROUTE_(\w+)\s*=\s*(\d+)", src)}
+
+
+def test_conv2d_route_of_known_shapes():
+    L, R = y3d.lib(), route_codes()
+    bf, f32 = _lib.BF16, _lib.F32
+    FWD, DGRAD, WGRAD = 0, 1, 2
+    RAW, PART, AFF, RES, BIAS = 0, 1, 2, 3, 4
+    cases = [
+        # (dtype, op, epi, B, H, W, Cin, Cout, groups, k, stride, pad) -> route
+        ((bf, FWD, AFF, 32, 80, 80, 2048, 2048, 16, 3, 1, 1), "WIDE3_16"),   # the roofline launch: 16 x (128 -> 128) @80x80
+        ((bf, FWD, PART, 32, 80, 80, 2048, 2048, 16, 3, 1, 1), "WIDE3_16"),
+        ((bf, DGRAD, RAW, 32, 80, 80, 2048, 2048, 16, 3, 1, 1), "WIDE3_16"),
+        ((bf, FWD, AFF, 32, 40, 40, 2048, 2048, 16, 3, 1, 1), "FLAT"),
+        ((bf, FWD, AFF, 32, 40, 40, 128, 128, 1, 3, 1, 1), "TILE8"),         # 120 persistent tiles: the 256-pixel tiles fill the chip
+        ((f32, FWD, AFF, 32, 80, 80, 128, 128, 1, 3, 1, 1), "TILE16"),
+        ((bf, FWD, AFF, 4, 80, 80, 64, 64, 1, 3, 1, 1), "SMALL"),
+        ((bf, FWD, RES, 4, 80, 80, 64, 64, 1, 3, 1, 1), "SMALL"),
+        ((bf, FWD, BIAS, 4, 80, 80, 64, 64, 1, 3, 1, 1), "GENERIC"),          # no bias epilogue on the narrow kernel
+        ((bf, FWD, AFF, 32, 640, 640, 8, 16, 1, 3, 2, 1), "SMALL_S2"),
+        ((bf, FWD, AFF, 32, 80, 80, 128, 128, 1, 1, 1, 0), "STREAM1X1"),
+        ((bf, FWD, AFF, 1600, 5, 5, 512, 896, 1, 3, 1, 0), "GENERIC"),        # the sparse head's unpadded patch conv
+        ((bf, DGRAD, RAW, 32, 80, 80, 64, 128, 1, 3, 2, 1), "S2_DGRAD"),
+        ((bf, WGRAD, RAW, 4, 80, 80, 64, 64, 1, 3, 1, 1), "WGRAD_SMALL"),
+        ((bf, WGRAD, RAW, 32, 80, 80, 128, 128, 1, 3, 1, 1), "WGRAD_TILE"),
+        ((bf, WGRAD, RAW, 32, 80, 80, 128, 256, 1, 1, 1, 0), "WGRAD_STREAM1X1"),
+        ((f32, WGRAD, RAW, 32, 80, 80, 128, 128, 1, 3, 1, 1), "GENERIC"),
+    ]
+    for (dt, op, epi, B, H, W, Cin, Cout, g, k, s, p), want in cases:
+        got = L.conv2d_route(dt, op, epi, B, H, W, Cin, Cout, g, k, k, s, p)
+        name = {v: n for n, v in R.items()}.get(got, got)
+        assert got == R[want], f"route of {(dt, op, epi, B, H, W, Cin, Cout, g, k, s, p)}: {name}, expected {want}"
+    # refusals: a residual epilogue only on the narrow kernel; channels the 16-byte chunks cannot carry; a bad op
+    assert L.conv2d_route(bf, FWD, RES, 4, 80, 80, 128, 128, 1, 3, 3, 1, 1) < 0
+    assert L.conv2d_route(bf, FWD, AFF, 4, 80, 80, 12, 16, 1, 3, 3, 1, 1) < 0 and "multiple" in L.last_error()
+    assert L.conv2d_route(bf, 3, 0, 4, 80, 80, 64, 64, 1, 3, 3, 1, 1) < 0
+    # the A/B knobs take their kernels out of the choice
+    old = L.set_tile_kernels(0)
+    try:
+        assert L.conv2d_route(bf, FWD, AFF, 32, 80, 80, 2048, 2048, 16, 3, 3, 1, 1) == R["GENERIC"]
+    finally:
+        L.set_tile_kernels(old)
+    old = L.set_stream1x1(0)
+    try:
+        assert L.conv2d_route(bf, FWD, AFF, 4, 80, 80, 64, 64, 1, 3, 3, 1, 1) == R["TILE16"]  # (the narrow kernel shares the knob)
+        assert L.conv2d_route(bf, FWD, AFF, 32, 80, 80, 128, 128, 1, 1, 1, 1, 0) == R["GENERIC"]
+    finally:
+        L.set_stream1x1(old)
+
+
 def test_invalid_arguments_raise_python_exceptions():
     L = y3d.lib()
     with pytest.raises(y3d.Y3DError, match="dtype"):

@@ -332,8 +332,8 @@ int y3d_conv3x3_flat_launch(const void* x, long xsb, long xsh, long xsw, int B, 
 // with fewer 512-pixel tiles than this (half the CUs) the 256-pixel tiles of this file's kernel fill the chip better
 static int v2_max_tiles() { return 129; }
 
-// tile height the resident-halo kernels would use for this geometry, 0 if the generic implicit GEMM must be used
-int y3d_tile_height(int dtype, int B, int H, int W, int Cg, int Cn, int G, int kh, int kw, int stride, int pad) {
+// tile height the resident-halo kernels would use for this geometry (-1: the flat tiling), 0 if the generic implicit GEMM must be used
+static int tile_height(int dtype, int B, int H, int W, int Cg, int Cn, int G, int kh, int kw, int stride, int pad) {
   int cse = 32;  // channels per K slab: 32 bf16 (64-byte rows, wide kernel) or 32 fp32 (128-byte rows)
   if (kh != 3 || kw != 3 || stride != 1 || pad != 1) return 0;
   // bf16: the persistent kernel (conv3x3_wide3.hip) zero-fills a partial last 32-channel slab: any multiple of 8 from 40 channels
@@ -358,23 +358,39 @@ int y3d_tile_height(int dtype, int B, int H, int W, int Cg, int Cn, int G, int k
   return 0;
 }
 
-int y3d_conv3x3_tile_launch(int dtype, int th, const void* x, long xsb, long xsh, long xsw, int B, int H, int W, int Cg, int Cn, int G,
+// which of the resident-halo kernels (Y3D_ROUTE_FLAT / _TILE8 / _TILE16 / _WIDE3_8 / _WIDE3_16) takes this 3x3 s1 p1 geometry, or
+// Y3D_ROUTE_GENERIC.  Part of conv_gemm.hip's conv_route: the only caller
+int y3d_conv3x3_tile_route(int dtype, int B, int H, int W, int Cg, int Cn, int G, int kh, int kw, int stride, int pad) {
+  const int th = tile_height(dtype, B, H, W, Cg, Cn, G, kh, kw, stride, pad);
+  if (th == 0) return Y3D_ROUTE_GENERIC;
+  if (th < 0) return Y3D_ROUTE_FLAT;
+  if (dtype == Y3D_BF16) {
+    // the persistent kernel runs one 512-pixel tile per CU at a time: with fewer tiles than half the CUs (128 -> 128 @40x40, B = 32:
+    // 120) the 256-pixel tiles of this file's kernel fill the chip better (628 / 671 against 448 / 482 TFLOP/s forward / dgrad)
+    const long wide_tiles = (long)G * cdiv(B, 32 / th) * cdiv(H, th) * cdiv(W, 16) * cdiv(Cn, 128);
+    if (wide_tiles < v2_max_tiles() && Cg % 64 == 0 && H % th == 0)  // this kernel's K slab is a 128-byte row: 64 bf16 channels
+      return th == 16 ? Y3D_ROUTE_TILE16 : Y3D_ROUTE_TILE8;
+    return th == 16 ? Y3D_ROUTE_WIDE3_16 : Y3D_ROUTE_WIDE3_8;
+  }
+  return th == 16 ? Y3D_ROUTE_TILE16 : Y3D_ROUTE_TILE8;
+}
+
+// route: a code y3d_conv3x3_tile_route returned for this geometry
+int y3d_conv3x3_tile_launch(int dtype, int route, const void* x, long xsb, long xsh, long xsw, int B, int H, int W, int Cg, int Cn, int G,
                             const void* w, int Ktot, void* y, long ysw, float* part, int flip, const float* scale, const float* shift, int act,
                             void* stream) {
+  if (route == Y3D_ROUTE_FLAT) return y3d_conv3x3_flat_launch(x, xsb, xsh, xsw, B, H, W, Cg, Cn, G, w, Ktot, y, ysw, part, flip, scale, shift, act, stream);
+  if (route == Y3D_ROUTE_WIDE3_8 || route == Y3D_ROUTE_WIDE3_16)
+    return y3d_conv3x3_wide3_launch(route == Y3D_ROUTE_WIDE3_16 ? 16 : 8, x, xsb, xsh, xsw, B, H, W, Cg, Cn, G, w, Ktot, y, ysw, part, flip, scale,
+                                    shift, act, stream);
+  Y3D_CHECK(route == Y3D_ROUTE_TILE8 || route == Y3D_ROUTE_TILE16, "conv3x3_tile: route %d is not a resident-halo kernel", route);
+  const int th = route == Y3D_ROUTE_TILE16 ? 16 : 8;
   C3P p;
   p.x = x; p.w = w; p.y = y; p.part = part; p.scale = scale; p.shift = shift; p.act = act;
   p.xsb = xsb; p.xsh = xsh; p.xsw = xsw; p.ysw = ysw;
   p.B = B; p.H = H; p.W = W; p.Cg = Cg; p.Cn = Cn; p.G = G; p.Ktot = Ktot;
   p.ntx = cdiv(W, 16); p.nty = cdiv(H, th); p.ntc = cdiv(Cn, 128); p.flip = flip;
   hipStream_t st = (hipStream_t)stream;
-  if (th < 0) return y3d_conv3x3_flat_launch(x, xsb, xsh, xsw, B, H, W, Cg, Cn, G, w, Ktot, y, ysw, part, flip, scale, shift, act, stream);
-  if (dtype == Y3D_BF16) {
-    // the persistent kernel runs one 512-pixel tile per CU at a time: with fewer tiles than half the CUs (128 -> 128 @40x40, B = 32:
-    // 120) the 256-pixel tiles of this file's kernel fill the chip better (628 / 671 against 448 / 482 TFLOP/s forward / dgrad)
-    const long wide_tiles = (long)G * cdiv(B, 32 / th) * p.nty * p.ntx * p.ntc;
-    if (wide_tiles < v2_max_tiles() && Cg % 64 == 0 && H % th == 0)  // this kernel's K slab is a 128-byte row: 64 bf16 channels
-      return th == 16 ? launch_tile_epi<bf16_t, 16>(p, st) : launch_tile_epi<bf16_t, 8>(p, st);
-    return y3d_conv3x3_wide3_launch(th, x, xsb, xsh, xsw, B, H, W, Cg, Cn, G, w, Ktot, y, ysw, part, flip, scale, shift, act, stream);
-  }
+  if (dtype == Y3D_BF16) return th == 16 ? launch_tile_epi<bf16_t, 16>(p, st) : launch_tile_epi<bf16_t, 8>(p, st);
   return th == 16 ? launch_tile_epi<float, 16>(p, st) : launch_tile_epi<float, 8>(p, st);
 }

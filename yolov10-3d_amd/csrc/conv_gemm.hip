@@ -753,9 +753,9 @@ int launch_conv(ConvP p, hipStream_t st) {
 }  // namespace
 
 // conv3x3_tile.hip
-int y3d_tile_height(int dtype, int B, int H, int W, int Cg, int Cn, int G, int kh, int kw, int stride, int pad);
+int y3d_conv3x3_tile_route(int dtype, int B, int H, int W, int Cg, int Cn, int G, int kh, int kw, int stride, int pad);
 int y3d_conv3x3_flat_tiles(int B, int H, int W);
-int y3d_conv3x3_tile_launch(int dtype, int th, const void* x, long xsb, long xsh, long xsw, int B, int H, int W, int Cg, int Cn, int G,
+int y3d_conv3x3_tile_launch(int dtype, int route, const void* x, long xsb, long xsh, long xsw, int B, int H, int W, int Cg, int Cn, int G,
                             const void* w, int Ktot, void* y, long ysw, float* part, int flip, const float* scale, const float* shift, int act,
                             void* stream);
 
@@ -788,7 +788,6 @@ int y3d_conv3x3_small_s2_rows(int B, int H, int W, int Cin, int Cout);
 int y3d_conv3x3_small_s2_launch(const void* x, long xsb, long xsh, long xsw, int B, int H, int W, int Cin, int Cout, const void* w, int Ktot, void* y,
                                 long ysw, float* part, int rows, const float* scale, const float* shift, int act, void* stream);
 int y3d_conv1x1_stream_rows(long M, int K, int N, int G = 1);
-extern "C" int y3d_conv2d_stat_rows(int dtype, int B, int H, int W, int Cin, int Cout, int groups, int kh, int kw, int stride, int pad);
 // wgrad3x3_small.hip
 int y3d_wgrad3x3_small_ok(int dtype, int B, int H, int W, int Cin, int Cout);
 int y3d_wgrad3x3_small_splits(int B, int H, int W);
@@ -800,6 +799,63 @@ static inline bool dense_pixels(int B, int H, int W, long sb, long sh, long sw) 
 
 static int g_tile_kernels = 1;
 extern "C" int y3d_conv2d_wgrad_splits(int dtype, int B, int Ho, int Wo, int Cout, int Cin_g, int groups, int kh, int kw);
+
+// THE kernel choice of every convolution entry point (Y3D_ROUTE_*), or Y3D_ERR_INVALID (message set) for a geometry it refuses.  One
+// source: the entry points dispatch on its result, y3d_conv2d_stat_rows / y3d_conv2d_wgrad_plan size their buffers from it and
+// y3d_conv2d_route exposes it.  Ho / Wo: the entry point's output (forward, weight gradient) or dy (data gradient) dims.  dense: the
+// operand the streaming kernels read (x; dy for the data gradient) is pixel-dense; asw: its pixel stride; bsw: the other pixel
+// stride the stride-2 data-gradient / 1x1 weight-gradient kernels check (dx; dy).  cin_full: the weight gradient writes every input
+// channel (Cin_real == Cin).
+static int conv_route(int dtype, int op, int epi, int B, int H, int W, int Ho, int Wo, int Cin, int Cout, int groups, int kh, int kw, int stride,
+                      int pad, bool dense, long asw, long bsw, bool cin_full) {
+  const int ce = dtype == Y3D_BF16 ? 8 : 4;
+  const bool k1 = kh == 1 && kw == 1 && stride == 1 && pad == 0, k3s1 = kh == 3 && kw == 3 && stride == 1 && pad == 1,
+             k3s2 = kh == 3 && kw == 3 && stride == 2 && pad == 1;
+  if (op == Y3D_OP_FWD) {
+    Y3D_CHECK(dtype == Y3D_BF16 || dtype == Y3D_F32, "conv2d_fwd: bad dtype %d", dtype);
+    Y3D_CHECK(B > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && groups > 0, "conv2d_fwd: empty shape");
+    Y3D_CHECK(Cin % groups == 0 && Cout % groups == 0, "conv2d_fwd: channels not divisible by groups");
+    Y3D_CHECK((Cin / groups) % ce == 0, "conv2d_fwd: Cin/groups=%d must be a multiple of %d (pad the input)", Cin / groups, ce);
+    Y3D_CHECK(kh * kw <= 64, "conv2d_fwd: at most 64 filter taps");
+    Y3D_CHECK(epi >= Y3D_EPI_RAW && epi <= Y3D_EPI_BIAS, "conv2d_fwd: bad epilogue %d", epi);
+    const int Cg = Cin / groups, Cn = Cout / groups;
+    const long M = (long)B * Ho * Wo;
+    const bool bias = epi == Y3D_EPI_BIAS;
+    if (k1 && dense && y3d_conv1x1_stream_ok(dtype, M, Cg, Cn, asw, groups)) return Y3D_ROUTE_STREAM1X1;
+    // y3d_conv2d_stat_rows sized the caller's partial buffer for the streaming kernel: an operand it cannot take (a view that is not
+    // pixel-dense, or beyond 32-bit byte offsets) must not fall through to the generic kernel's one-row-per-tile layout
+    Y3D_CHECK(!(epi == Y3D_EPI_PARTIALS && k1 && y3d_conv1x1_stream_ok(dtype, M, Cg, Cn, Cin, groups)),
+              "conv2d_fwd: 1x1 input view must be pixel-dense and below 4 GB for the BatchNorm partial layout of this shape");
+    if (k3s1 && groups == 1 && !bias && y3d_conv3x3_small_ok(dtype, B, H, W, Cin, Cout, 1)) return Y3D_ROUTE_SMALL;
+    Y3D_CHECK(epi != Y3D_EPI_AFFINE_RES, "conv2d_fwd_affine_res: no kernel with a residual epilogue takes this geometry (ask y3d_conv2d_fwd_affine_res_ok first)");
+    if (k3s2 && groups == 1 && !bias && y3d_conv3x3_small_s2_ok(dtype, B, H, W, Cin, Cout)) return Y3D_ROUTE_SMALL_S2;
+    if (!bias && g_tile_kernels) return y3d_conv3x3_tile_route(dtype, B, H, W, Cg, Cn, groups, kh, kw, stride, pad);
+    return Y3D_ROUTE_GENERIC;
+  }
+  if (op == Y3D_OP_BWD_DATA) {
+    Y3D_CHECK(dtype == Y3D_BF16 || dtype == Y3D_F32, "conv2d_bwd_data: bad dtype %d", dtype);
+    Y3D_CHECK(groups > 0 && Cin % groups == 0 && Cout % groups == 0, "conv2d_bwd_data: channels not divisible by groups");
+    Y3D_CHECK((Cout / groups) % ce == 0, "conv2d_bwd_data: Cout/groups=%d must be a multiple of %d", Cout / groups, ce);
+    Y3D_CHECK(kh * kw <= 64, "conv2d_bwd_data: at most 64 filter taps");
+    Y3D_CHECK(epi == 0, "conv2d_bwd_data: no epilogue variants");
+    const int Cg = Cout / groups, Cn = Cin / groups;
+    if (k1 && dense && y3d_conv1x1_stream_ok(dtype, (long)B * H * W, Cg, Cn, asw, groups)) return Y3D_ROUTE_STREAM1X1;
+    if (k3s1 && groups == 1 && Ho == H && Wo == W && y3d_conv3x3_small_ok(dtype, B, H, W, Cout, Cin, 1)) return Y3D_ROUTE_SMALL;
+    if (k3s2 && groups == 1 && dense && y3d_conv3x3s2_dgrad_ok(dtype, B, Ho, Wo, H, W, Cout, Cin, asw, bsw)) return Y3D_ROUTE_S2_DGRAD;
+    // a 3x3 s1 p1 data gradient is the same conv on dy with flipped taps (Ho == H, Wo == W)
+    if (g_tile_kernels && Ho == H && Wo == W) return y3d_conv3x3_tile_route(dtype, B, H, W, Cg, Cn, groups, kh, kw, stride, pad);
+    return Y3D_ROUTE_GENERIC;
+  }
+  Y3D_CHECK(op == Y3D_OP_BWD_WEIGHT, "conv2d_route: bad op %d", op);
+  Y3D_CHECK(dtype == Y3D_BF16 || dtype == Y3D_F32, "conv2d_bwd_weight: bad dtype %d", dtype);
+  Y3D_CHECK(groups > 0 && Cin % groups == 0 && Cout % groups == 0, "conv2d_bwd_weight: channels not divisible by groups");
+  Y3D_CHECK((Cin / groups) % ce == 0 && (Cout / groups) % ce == 0, "conv2d_bwd_weight: per-group channels must be multiples of %d", ce);
+  Y3D_CHECK(epi == 0, "conv2d_bwd_weight: no epilogue variants");
+  if (k3s1 && groups == 1 && cin_full && y3d_wgrad3x3_small_ok(dtype, B, H, W, Cin, Cout)) return Y3D_ROUTE_WGRAD_SMALL;
+  if (g_tile_kernels && cin_full && y3d_wgrad_tile_height(dtype, H, W, Cin / groups, Cout / groups, kh, kw, stride, pad)) return Y3D_ROUTE_WGRAD_TILE;
+  if (k1 && groups == 1 && cin_full && dense && y3d_wgrad1x1_stream_ok(dtype, (long)B * Ho * Wo, Cin, Cout, asw, bsw)) return Y3D_ROUTE_WGRAD_STREAM1X1;
+  return Y3D_ROUTE_GENERIC;
+}
 
 extern "C" {
 
@@ -813,38 +869,48 @@ int y3d_set_tile_kernels(int enable) {
 
 int y3d_conv_stat_blocks(int B, int Ho, int Wo) { return cdiv((long)B * Ho * Wo, 128); }
 
+int y3d_conv2d_route(int dtype, int op, int epi, int B, int H, int W, int Cin, int Cout, int groups, int kh, int kw, int stride, int pad) {
+  Y3D_CHECK(kh > 0 && kw > 0 && stride > 0 && pad >= 0, "conv2d_route: bad filter geometry");
+  const int Ho = (H + 2 * pad - kh) / stride + 1, Wo = (W + 2 * pad - kw) / stride + 1;
+  Y3D_CHECK(Ho > 0 && Wo > 0, "conv2d_route: empty output");
+  // pixel-dense NHWC operands: x / dy / dx pixel strides are their channel counts
+  if (op == Y3D_OP_BWD_DATA) return conv_route(dtype, op, epi, B, H, W, Ho, Wo, Cin, Cout, groups, kh, kw, stride, pad, true, Cout, Cin, true);
+  return conv_route(dtype, op, epi, B, H, W, Ho, Wo, Cin, Cout, groups, kh, kw, stride, pad, true, Cin, Cout, true);
+}
+
 int y3d_conv2d_wgrad_plan(int dtype, int B, int H, int W, int Cin, int Cout, int groups, int kh, int kw, int stride, int pad) {
-  if (kh == 3 && kw == 3 && stride == 1 && pad == 1 && groups == 1 && y3d_wgrad3x3_small_ok(dtype, B, H, W, Cin, Cout))
-    return y3d_wgrad3x3_small_splits(B, H, W);
-  int th = (g_tile_kernels && groups > 0) ? y3d_wgrad_tile_height(dtype, H, W, Cin / groups, Cout / groups, kh, kw, stride, pad) : 0;
-  if (th) return y3d_wgrad_tile_splits(th, B, H, W, Cin / groups, Cout / groups, groups);
   int Ho = (H + 2 * pad - kh) / stride + 1, Wo = (W + 2 * pad - kw) / stride + 1;
-  if (kh == 1 && kw == 1 && stride == 1 && pad == 0 && groups == 1 && y3d_wgrad1x1_stream_ok(dtype, (long)B * H * W, Cin, Cout, Cin, Cout)) {
-    // the streaming kernel keeps one 512-thread workgroup per CU busy (148 KB of LDS ring): one round of workgroups, at least four
-    // 64-pixel steps each; every further split is one more fp32 slab to write and to fold
-    const int target = 256;
-    const long tiles = (long)cdiv(Cin, Cin <= 64 ? 64 : 128) * cdiv(Cout, Cout <= 64 ? 64 : 128);
-    // rounded down, as y3d_wgrad_tile_splits: 15 tiles (640 -> 320, X widths) x 18 splits = 270 workgroups = a second round for 14 of them
-    long want = target / tiles, maxs = cdiv((long)B * H * W, 4 * 64);
-    if (want > maxs) want = maxs;
-    return (int)(want < 1 ? 1 : want);
+  switch (conv_route(dtype, Y3D_OP_BWD_WEIGHT, 0, B, H, W, Ho, Wo, Cin, Cout, groups, kh, kw, stride, pad, true, Cin, Cout, true)) {
+    case Y3D_ROUTE_WGRAD_SMALL: return y3d_wgrad3x3_small_splits(B, H, W);
+    case Y3D_ROUTE_WGRAD_TILE:
+      return y3d_wgrad_tile_splits(y3d_wgrad_tile_height(dtype, H, W, Cin / groups, Cout / groups, kh, kw, stride, pad), B, H, W, Cin / groups,
+                                   Cout / groups, groups);
+    case Y3D_ROUTE_WGRAD_STREAM1X1: {
+      // the streaming kernel keeps one 512-thread workgroup per CU busy (148 KB of LDS ring): one round of workgroups, at least four
+      // 64-pixel steps each; every further split is one more fp32 slab to write and to fold
+      const int target = 256;
+      const long tiles = (long)cdiv(Cin, Cin <= 64 ? 64 : 128) * cdiv(Cout, Cout <= 64 ? 64 : 128);
+      // rounded down, as y3d_wgrad_tile_splits: 15 tiles (640 -> 320, X widths) x 18 splits = 270 workgroups = a second round for 14 of them
+      long want = target / tiles, maxs = cdiv((long)B * H * W, 4 * 64);
+      if (want > maxs) want = maxs;
+      return (int)(want < 1 ? 1 : want);
+    }
+    default: return y3d_conv2d_wgrad_splits(dtype, B, Ho, Wo, Cout, Cin / groups, groups, kh, kw);
   }
-  return y3d_conv2d_wgrad_splits(dtype, B, Ho, Wo, Cout, Cin / groups, groups, kh, kw);
 }
 
 int y3d_conv2d_stat_rows(int dtype, int B, int H, int W, int Cin, int Cout, int groups, int kh, int kw, int stride, int pad) {
-  // the persistent kernels write one row per workgroup (a few hundred rows whatever the map size)
-  if (kh == 1 && kw == 1 && stride == 1 && pad == 0 && groups >= 1 && y3d_conv1x1_stream_ok(dtype, (long)B * H * W, Cin / groups, Cout / groups, Cin, groups))
-    return y3d_conv1x1_stream_rows((long)B * H * W, Cin / groups, Cout / groups, groups);
-  if (kh == 3 && kw == 3 && stride == 1 && pad == 1 && groups == 1 && y3d_conv3x3_small_ok(dtype, B, H, W, Cin, Cout, 1))
-    return y3d_conv3x3_small_rows(B, H, W, Cin, Cout);
-  if (kh == 3 && kw == 3 && stride == 2 && pad == 1 && groups == 1 && y3d_conv3x3_small_s2_ok(dtype, B, H, W, Cin, Cout))
-    return y3d_conv3x3_small_s2_rows(B, H, W, Cin, Cout);
-  int th = (g_tile_kernels && groups > 0) ? y3d_tile_height(dtype, B, H, W, Cin / groups, Cout / groups, groups, kh, kw, stride, pad) : 0;
-  if (th < 0) return y3d_conv3x3_flat_tiles(B, H, W);  // conv3x3_flat.hip: one row per 512-position tile of the flat padded space
-  if (th) return B * cdiv(H, th) * cdiv(W, 16);
   int Ho = (H + 2 * pad - kh) / stride + 1, Wo = (W + 2 * pad - kw) / stride + 1;
-  return cdiv((long)B * Ho * Wo, 128);
+  // the persistent kernels write one row per workgroup (a few hundred rows whatever the map size); the tile kernels one per tile
+  switch (conv_route(dtype, Y3D_OP_FWD, Y3D_EPI_PARTIALS, B, H, W, Ho, Wo, Cin, Cout, groups, kh, kw, stride, pad, true, Cin, Cout, true)) {
+    case Y3D_ROUTE_STREAM1X1: return y3d_conv1x1_stream_rows((long)B * H * W, Cin / groups, Cout / groups, groups);
+    case Y3D_ROUTE_SMALL: return y3d_conv3x3_small_rows(B, H, W, Cin, Cout);
+    case Y3D_ROUTE_SMALL_S2: return y3d_conv3x3_small_s2_rows(B, H, W, Cin, Cout);
+    case Y3D_ROUTE_FLAT: return y3d_conv3x3_flat_tiles(B, H, W);  // conv3x3_flat.hip: one row per 512-position tile of the flat padded space
+    case Y3D_ROUTE_TILE8: case Y3D_ROUTE_WIDE3_8: return B * cdiv(H, 8) * cdiv(W, 16);
+    case Y3D_ROUTE_TILE16: case Y3D_ROUTE_WIDE3_16: return B * cdiv(H, 16) * cdiv(W, 16);
+    default: return cdiv((long)B * Ho * Wo, 128);
+  }
 }
 
 int y3d_conv_kpad(int dtype, int k_total) {
@@ -891,14 +957,13 @@ static int conv2d_fwd_impl(int dtype, const void* x, int64_t xsb, int64_t xsh, i
                            int Ho, int Wo, int Cout, int groups, int kh, int kw, int stride, int pad, float* stat_partials, void* stream,
                            const void* res = nullptr, int64_t rsw = 0) {
   int ce = dtype == Y3D_BF16 ? 8 : 4;
-  Y3D_CHECK(dtype == Y3D_BF16 || dtype == Y3D_F32, "conv2d_fwd: bad dtype %d", dtype);
-  Y3D_CHECK(B > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && groups > 0, "conv2d_fwd: empty shape");
-  Y3D_CHECK(Cin % groups == 0 && Cout % groups == 0, "conv2d_fwd: channels not divisible by groups");
-  Y3D_CHECK((Cin / groups) % ce == 0, "conv2d_fwd: Cin/groups=%d must be a multiple of %d (pad the input)", Cin / groups, ce);
+  Y3D_CHECK(!(bias && stat_partials), "conv2d_fwd: bias and BN partials are mutually exclusive");
+  const int epi = res ? Y3D_EPI_AFFINE_RES : scale ? Y3D_EPI_AFFINE : stat_partials ? Y3D_EPI_PARTIALS : bias ? Y3D_EPI_BIAS : Y3D_EPI_RAW;
+  const int route = conv_route(dtype, Y3D_OP_FWD, epi, B, H, W, Ho, Wo, Cin, Cout, groups, kh, kw, stride, pad, dense_pixels(B, H, W, xsb, xsh, xsw),
+                               xsw, 0, true);
+  if (route < 0) return route;
   Y3D_CHECK(Ho == (H + 2 * pad - kh) / stride + 1 && Wo == (W + 2 * pad - kw) / stride + 1, "conv2d_fwd: output dims (%d,%d) inconsistent", Ho, Wo);
   Y3D_CHECK(ysw >= Cout, "conv2d_fwd: ysw < Cout");
-  Y3D_CHECK(kh * kw <= 64, "conv2d_fwd: at most 64 filter taps");
-  Y3D_CHECK(!(bias && stat_partials), "conv2d_fwd: bias and BN partials are mutually exclusive");
   if (check_align("conv2d_fwd x", x, xsb, xsh, xsw, ce)) return Y3D_ERR_INVALID;
   Y3D_CHECK(((uintptr_t)w_packed & 15) == 0 && ((uintptr_t)y & 7) == 0, "conv2d_fwd: w/y alignment");
   Y3D_CHECK((long)B * Ho * Wo < (1L << 31), "conv2d_fwd: too many pixels");
@@ -909,29 +974,24 @@ static int conv2d_fwd_impl(int dtype, const void* x, int64_t xsb, int64_t xsh, i
   p.Cg = Cin / groups; p.Cn = Cout / groups; p.G = groups;
   p.kh = kh; p.kw = kw; p.stride = stride; p.pad = pad;
   p.Ktot = kh * kw * p.Cg; p.Kpad = p.Ktot; p.M = B * Ho * Wo;
-  if (kh == 1 && kw == 1 && stride == 1 && pad == 0 && dense_pixels(B, H, W, xsb, xsh, xsw) &&
-      y3d_conv1x1_stream_ok(dtype, p.M, p.Cg, p.Cn, xsw, groups))
-    return y3d_conv1x1_stream_launch(x, xsw, w_packed, p.Kpad, bias, scale, shift, act, y, ysw, stat_partials, p.M, p.Cg, p.Cn, groups, stream);
-  // y3d_conv2d_stat_rows sized the caller's partial buffer for the streaming kernel: an operand it cannot take (a view that is not
-  // pixel-dense, or beyond 32-bit byte offsets) must not fall through to the generic kernel's one-row-per-tile layout
-  Y3D_CHECK(!(stat_partials && kh == 1 && kw == 1 && stride == 1 && pad == 0 && y3d_conv1x1_stream_ok(dtype, p.M, p.Cg, p.Cn, Cin, groups)),
-            "conv2d_fwd: 1x1 input view must be pixel-dense and below 4 GB for the BatchNorm partial layout of this shape");
-  if (kh == 3 && kw == 3 && stride == 1 && pad == 1 && groups == 1 && !bias) {
-    const int rows = stat_partials ? y3d_conv2d_stat_rows(dtype, B, H, W, Cin, Cout, groups, kh, kw, stride, pad) : 1;
-    if (y3d_conv3x3_small_ok(dtype, B, H, W, Cin, Cout, rows))
+  switch (route) {
+    case Y3D_ROUTE_STREAM1X1:
+      return y3d_conv1x1_stream_launch(x, xsw, w_packed, p.Kpad, bias, scale, shift, act, y, ysw, stat_partials, p.M, p.Cg, p.Cn, groups, stream);
+    case Y3D_ROUTE_SMALL: {
+      const int rows = stat_partials ? y3d_conv3x3_small_rows(B, H, W, Cin, Cout) : 1;
       return y3d_conv3x3_small_launch(x, xsb, xsh, xsw, B, H, W, Cin, Cout, w_packed, p.Ktot, y, ysw, stat_partials, rows, 0, scale, shift, act, res, rsw, stream);
+    }
+    case Y3D_ROUTE_SMALL_S2: {
+      const int rows = stat_partials ? y3d_conv3x3_small_s2_rows(B, H, W, Cin, Cout) : 1;
+      return y3d_conv3x3_small_s2_launch(x, xsb, xsh, xsw, B, H, W, Cin, Cout, w_packed, p.Ktot, y, ysw, stat_partials, rows, scale, shift, act, stream);
+    }
+    case Y3D_ROUTE_GENERIC:
+      if (dtype == Y3D_BF16) return launch_conv<bf16_t, false>(p, (hipStream_t)stream);
+      return launch_conv<float, false>(p, (hipStream_t)stream);
+    default:
+      return y3d_conv3x3_tile_launch(dtype, route, x, xsb, xsh, xsw, B, H, W, p.Cg, p.Cn, groups, w_packed, p.Ktot, y, ysw, stat_partials, 0, scale,
+                                     shift, act, stream);
   }
-  Y3D_CHECK(!res, "conv2d_fwd_affine_res: no kernel with a residual epilogue takes this geometry (ask y3d_conv2d_fwd_affine_res_ok first)");
-  if (kh == 3 && kw == 3 && stride == 2 && pad == 1 && groups == 1 && !bias && y3d_conv3x3_small_s2_ok(dtype, B, H, W, Cin, Cout)) {
-    const int rows = stat_partials ? y3d_conv2d_stat_rows(dtype, B, H, W, Cin, Cout, groups, kh, kw, stride, pad) : 1;
-    return y3d_conv3x3_small_s2_launch(x, xsb, xsh, xsw, B, H, W, Cin, Cout, w_packed, p.Ktot, y, ysw, stat_partials, rows, scale, shift, act, stream);
-  }
-  if (!bias && g_tile_kernels) {
-    int th = y3d_tile_height(dtype, B, H, W, p.Cg, p.Cn, groups, kh, kw, stride, pad);
-    if (th) return y3d_conv3x3_tile_launch(dtype, th, x, xsb, xsh, xsw, B, H, W, p.Cg, p.Cn, groups, w_packed, p.Ktot, y, ysw, stat_partials, 0, scale, shift, act, stream);
-  }
-  if (dtype == Y3D_BF16) return launch_conv<bf16_t, false>(p, (hipStream_t)stream);
-  return launch_conv<float, false>(p, (hipStream_t)stream);
 }
 
 int y3d_conv2d_fwd(int dtype, const void* x, int64_t xsb, int64_t xsh, int64_t xsw, int B, int H, int W, int Cin,
@@ -966,12 +1026,11 @@ int y3d_conv2d_bwd_data(int dtype, const void* dy, int64_t dsb, int64_t dsh, int
                         const void* w_packed_dgrad, void* dx, int64_t xsw, int H, int W, int Cin, int groups, int kh, int kw,
                         int stride, int pad, void* stream) {
   int ce = dtype == Y3D_BF16 ? 8 : 4;
-  Y3D_CHECK(dtype == Y3D_BF16 || dtype == Y3D_F32, "conv2d_bwd_data: bad dtype %d", dtype);
-  Y3D_CHECK(Cin % groups == 0 && Cout % groups == 0, "conv2d_bwd_data: channels not divisible by groups");
-  Y3D_CHECK((Cout / groups) % ce == 0, "conv2d_bwd_data: Cout/groups=%d must be a multiple of %d", Cout / groups, ce);
+  const int route = conv_route(dtype, Y3D_OP_BWD_DATA, 0, B, H, W, Ho, Wo, Cin, Cout, groups, kh, kw, stride, pad,
+                               dense_pixels(B, Ho, Wo, dsb, dsh, dsw), dsw, xsw, true);
+  if (route < 0) return route;
   Y3D_CHECK(xsw >= Cin, "conv2d_bwd_data: xsw < Cin");
   Y3D_CHECK(stride >= 1 && dsh % stride == 0 && dsw % stride == 0, "conv2d_bwd_data: stride %d must divide the dy strides", stride);
-  Y3D_CHECK(kh * kw <= 64, "conv2d_bwd_data: at most 64 filter taps");
   if (check_align("conv2d_bwd_data dy", dy, dsb, dsh, dsw, ce)) return Y3D_ERR_INVALID;
   ConvP p;
   p.x = dy; p.w = w_packed_dgrad; p.bias = nullptr; p.scale = nullptr; p.shift = nullptr; p.act = 0; p.y = dx; p.part = nullptr;
@@ -980,22 +1039,20 @@ int y3d_conv2d_bwd_data(int dtype, const void* dy, int64_t dsb, int64_t dsh, int
   p.Cg = Cout / groups; p.Cn = Cin / groups; p.G = groups;
   p.kh = kh; p.kw = kw; p.stride = stride; p.pad = pad;
   p.Ktot = kh * kw * p.Cg; p.Kpad = y3d_conv_kpad(dtype, p.Ktot); p.M = B * H * W;
-  if (kh == 1 && kw == 1 && stride == 1 && pad == 0 && dense_pixels(B, Ho, Wo, dsb, dsh, dsw) &&
-      y3d_conv1x1_stream_ok(dtype, p.M, p.Cg, p.Cn, dsw, groups))
-    return y3d_conv1x1_stream_launch(dy, dsw, w_packed_dgrad, p.Kpad, nullptr, nullptr, nullptr, 0, dx, xsw, nullptr, p.M, p.Cg, p.Cn, groups, stream);
-  if (kh == 3 && kw == 3 && stride == 1 && pad == 1 && groups == 1 && Ho == H && Wo == W && y3d_conv3x3_small_ok(dtype, B, H, W, Cout, Cin, 1))
-    return y3d_conv3x3_small_launch(dy, dsb, dsh, dsw, B, H, W, Cout, Cin, w_packed_dgrad, p.Kpad, dx, xsw, nullptr, 1, 1, nullptr, nullptr, 0, nullptr, 0, stream);
-  if (kh == 3 && kw == 3 && stride == 2 && pad == 1 && groups == 1 && dense_pixels(B, Ho, Wo, dsb, dsh, dsw) &&
-      y3d_conv3x3s2_dgrad_ok(dtype, B, Ho, Wo, H, W, Cout, Cin, dsw, xsw))
-    return y3d_conv3x3s2_dgrad_launch(dy, dsw, B, Ho, Wo, Cout, w_packed_dgrad, p.Kpad, dx, xsw, H, W, Cin, stream);
-  if (g_tile_kernels) {
-    // a 3x3 s1 p1 data gradient is the same conv on dy with flipped taps (Ho == H, Wo == W)
-    int th = y3d_tile_height(dtype, B, Ho, Wo, p.Cg, p.Cn, groups, kh, kw, stride, pad);
-    if (th && Ho == H && Wo == W)
-      return y3d_conv3x3_tile_launch(dtype, th, dy, dsb, dsh, dsw, B, H, W, p.Cg, p.Cn, groups, w_packed_dgrad, p.Kpad, dx, xsw, nullptr, 1, nullptr, nullptr, 0, stream);
+  switch (route) {
+    case Y3D_ROUTE_STREAM1X1:
+      return y3d_conv1x1_stream_launch(dy, dsw, w_packed_dgrad, p.Kpad, nullptr, nullptr, nullptr, 0, dx, xsw, nullptr, p.M, p.Cg, p.Cn, groups, stream);
+    case Y3D_ROUTE_SMALL:
+      return y3d_conv3x3_small_launch(dy, dsb, dsh, dsw, B, H, W, Cout, Cin, w_packed_dgrad, p.Kpad, dx, xsw, nullptr, 1, 1, nullptr, nullptr, 0, nullptr, 0, stream);
+    case Y3D_ROUTE_S2_DGRAD:
+      return y3d_conv3x3s2_dgrad_launch(dy, dsw, B, Ho, Wo, Cout, w_packed_dgrad, p.Kpad, dx, xsw, H, W, Cin, stream);
+    case Y3D_ROUTE_GENERIC:
+      if (dtype == Y3D_BF16) return launch_conv<bf16_t, true>(p, (hipStream_t)stream);
+      return launch_conv<float, true>(p, (hipStream_t)stream);
+    default:
+      return y3d_conv3x3_tile_launch(dtype, route, dy, dsb, dsh, dsw, B, H, W, p.Cg, p.Cn, groups, w_packed_dgrad, p.Kpad, dx, xsw, nullptr, 1, nullptr,
+                                     nullptr, 0, stream);
   }
-  if (dtype == Y3D_BF16) return launch_conv<bf16_t, true>(p, (hipStream_t)stream);
-  return launch_conv<float, true>(p, (hipStream_t)stream);
 }
 
 static inline int wgrad_tile_w(int n) { return n <= 32 ? 32 : (n <= 64 ? 64 : 128); }  // operand tile width of the generic wgrad kernel
@@ -1024,9 +1081,9 @@ int y3d_conv2d_bwd_weight(int dtype, const void* x, int64_t xsb, int64_t xsh, in
                           int stride, int pad, float* slab, int nsplit, float* grad_oihw, int accumulate, void* stream) {
   int ce = dtype == Y3D_BF16 ? 8 : 4;
   int bpk = dtype == Y3D_BF16 ? 64 : 32;
-  Y3D_CHECK(dtype == Y3D_BF16 || dtype == Y3D_F32, "conv2d_bwd_weight: bad dtype %d", dtype);
-  Y3D_CHECK(Cin % groups == 0 && Cout % groups == 0, "conv2d_bwd_weight: channels not divisible by groups");
-  Y3D_CHECK((Cin / groups) % ce == 0 && (Cout / groups) % ce == 0, "conv2d_bwd_weight: per-group channels must be multiples of %d", ce);
+  const int route = conv_route(dtype, Y3D_OP_BWD_WEIGHT, 0, B, H, W, Ho, Wo, Cin, Cout, groups, kh, kw, stride, pad, dense_pixels(B, H, W, xsb, xsh, xsw),
+                               xsw, dsw, Cin_real == Cin);
+  if (route < 0) return route;
   Y3D_CHECK(nsplit >= 1, "conv2d_bwd_weight: nsplit");
   Y3D_CHECK(Cin_real <= Cin && (Cin_real == Cin || groups == 1), "conv2d_bwd_weight: Cin_real");
   if (check_align("conv2d_bwd_weight x", x, xsb, xsh, xsw, ce)) return Y3D_ERR_INVALID;
@@ -1040,28 +1097,23 @@ int y3d_conv2d_bwd_weight(int dtype, const void* x, int64_t xsb, int64_t xsh, in
   p.Ktot = kh * kw * p.Cg; p.M = B * Ho * Wo; p.nsplit = nsplit;
   p.chunk_px = cdiv(cdiv(p.M, nsplit), bpk) * bpk;
   hipStream_t st = (hipStream_t)stream;
-  if (kh == 3 && kw == 3 && stride == 1 && pad == 1 && groups == 1 && Cin_real == Cin && y3d_wgrad3x3_small_ok(dtype, B, H, W, Cin, Cout)) {
+  if (route == Y3D_ROUTE_WGRAD_SMALL) {
     int rc = y3d_wgrad3x3_small_launch(x, xsb, xsh, xsw, dy, dsw, B, H, W, Cin, Cout, slab, nsplit, stream);
     if (rc) return rc;
     launch_wgrad_reduce(slab, grad_oihw, nsplit, Cout, 9, Cin, Cin, accumulate, st);
     Y3D_LAUNCH_CHECK();
     return Y3D_OK;
   }
-  {
-    int th = g_tile_kernels ? y3d_wgrad_tile_height(dtype, H, W, p.Cg, p.Cn, kh, kw, stride, pad) : 0;
-    if (th && Cin_real == Cin) {
-      Y3D_CHECK(nsplit == y3d_wgrad_tile_splits(th, B, H, W, p.Cg, p.Cn, groups), "conv2d_bwd_weight: nsplit must come from y3d_conv2d_wgrad_plan");
-      int rc = y3d_conv3x3_wgrad_tile_launch(th, x, xsb, xsh, xsw, dy, dsw, B, H, W, p.Cg, p.Cn, groups, slab, nsplit, stream);
-      if (rc) return rc;
-      long n2 = (long)Cout * kh * kw * p.Cg;
-      (void)n2;
-      launch_wgrad_reduce(slab, grad_oihw, nsplit, Cout, kh * kw, p.Cg, p.Cg, accumulate, st);
-      Y3D_LAUNCH_CHECK();
-      return Y3D_OK;
-    }
+  if (route == Y3D_ROUTE_WGRAD_TILE) {
+    const int th = y3d_wgrad_tile_height(dtype, H, W, p.Cg, p.Cn, kh, kw, stride, pad);
+    Y3D_CHECK(nsplit == y3d_wgrad_tile_splits(th, B, H, W, p.Cg, p.Cn, groups), "conv2d_bwd_weight: nsplit must come from y3d_conv2d_wgrad_plan");
+    int rc = y3d_conv3x3_wgrad_tile_launch(th, x, xsb, xsh, xsw, dy, dsw, B, H, W, p.Cg, p.Cn, groups, slab, nsplit, stream);
+    if (rc) return rc;
+    launch_wgrad_reduce(slab, grad_oihw, nsplit, Cout, kh * kw, p.Cg, p.Cg, accumulate, st);
+    Y3D_LAUNCH_CHECK();
+    return Y3D_OK;
   }
-  if (kh == 1 && kw == 1 && stride == 1 && pad == 0 && groups == 1 && Cin_real == Cin && dense_pixels(B, H, W, xsb, xsh, xsw) &&
-      y3d_wgrad1x1_stream_ok(dtype, p.M, Cin, Cout, xsw, dsw)) {
+  if (route == Y3D_ROUTE_WGRAD_STREAM1X1) {
     int rc = y3d_wgrad1x1_stream_launch(x, xsw, dy, dsw, p.M, Cin, Cout, slab, nsplit, p.chunk_px, stream);
     if (rc) return rc;
     launch_wgrad_reduce(slab, grad_oihw, nsplit, Cout, 1, Cin, Cin, accumulate, st);
