@@ -397,6 +397,37 @@ int y3d_kitti_decode(const float* preds, int B, int K, const double* calib, cons
                      const double* mean_size, int nc, int use_camera_dis, double threshold, double* out, unsigned char* keep, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * KITTI AP evaluation (kitti_eval.hip) — the evaluator behind KITTIDataset.get_stats (data/datasets/kitti.py:444-450):
+ * eval_from_scrach / get_official_eval_result (data/datasets/kitti_eval.py:1268-1336, :1075-1165).
+ * Boxes are packed per image, images back to back: gt / dt (N, 16) fp32 records
+ *   [x1, y1, x2, y2, x, y, z, l, h, w, ry, alpha, score, occluded, truncated, 0]   (camera frame, y = bottom face)
+ * gt_off / dt_off (n_img + 1) int32 prefix offsets into them; ov_off (n_img + 1) int64 prefix offsets of the per-image (n_dt, n_gt)
+ * overlap blocks.  gt_code / dt_code (N) int32 name codes: 0 car, 1 pedestrian, 2 cyclist, 3 van, 4 person_sitting, 5 tractor,
+ * 6 trailer, 7 other (case-insensitive), + 8 for a name that is exactly "DontCare".  At most y3d_kitti_eval_max_boxes() gts and dets
+ * per image (the host layer checks; larger images are skipped by the kernels).  All arithmetic fp32, FMA contraction off.
+ * ---------------------------------------------------------------------------------------------- */
+int y3d_kitti_eval_max_boxes(void);
+/* calculate_iou_partly(dt_annos, gt_annos, metric) (kitti_eval.py:698-781), the per-image blocks only: out[ov_off[i] + j * n_gt + g] =
+ * overlap of det j with gt g of image i.  metric 0: image_box_overlap (:429-455); 1: bev_box_overlap / devRotateIoUEval over
+ * (x, z, l, w, ry) with gt as rbox1 (:248-260, :458-461); 2: box3d_overlap with z_axis = 1, z_center = 1.0 (:465-515) */
+int y3d_kitti_box_overlaps(int metric, const float* gt, const float* dt, const int* gt_off, const int* dt_off, const int64_t* ov_off,
+                           int n_img, float* out, void* stream);
+/* Threshold pass of eval_class_v3 (kitti_eval.py:868-883): compute_statistics_jit(compute_fp = False, thresh = 0) (:518-636) for every
+ * (class x difficulty, min-overlap, image), ignore flags from clean_data (:369-425).  cd (ncd, 2) int32 = (class code, difficulty 0-2);
+ * min_ov (ncd * nk) float64, setting s = cd_index * nk + k.  tp_score (ncd * nk, total_gt): the score of the det each gt is a true
+ * positive of (entries of other gts are left as they are); nvalid (ncd, n_img): the image's gts with ignored_gt == 0 */
+int y3d_kitti_eval_thresholds(const float* gt, const int* gt_code, const float* dt, const int* dt_code, const int* gt_off, const int* dt_off,
+                              const int64_t* ov_off, const float* ov, int n_img, int total_gt, int metric, const int* cd, int ncd,
+                              const double* min_ov, int nk, float* tp_score, int* nvalid, void* stream);
+/* Counting pass: fused_compute_statistics (kitti_eval.py:648-696) — compute_statistics_jit(compute_fp = True) at the thresholds
+ * thr (ncd * nk, 41) fp32, nthr (ncd * nk) of them per setting (get_thresholds :347-366), DontCare suppression for metric 0, AOS
+ * similarity when compute_aos.  Work space cnt (ncd * nk * 41 * n_img * 3) int32, sim (ncd * nk * 41 * n_img) float64;
+ * pr (ncd * nk, 41, 4) float64 = [tp, fp, fn, similarity] summed over images in a fixed order (bit-reproducible) */
+int y3d_kitti_eval_counts(const float* gt, const int* gt_code, const float* dt, const int* dt_code, const int* gt_off, const int* dt_off,
+                          const int64_t* ov_off, const float* ov, int n_img, int metric, const int* cd, int ncd, const double* min_ov, int nk,
+                          const float* thr, const int* nthr, int compute_aos, int* cnt, double* sim, double* pr, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Optimizer step as multi-tensor launches (optim.hip): clip_grad_norm_ + SGD(nesterov, weight decay) — engine/trainer.py:567-575,
  * 734-790.  All table arguments are DEVICE arrays: tensor t has sizes[t] fp32 elements at param_ptrs[t] / grad_ptrs[t] / buf_ptrs[t];
  * workgroup c handles elements [chunk_off[c]*chunk, +chunk) of tensor chunk_tensor[c].
