@@ -428,6 +428,35 @@ int y3d_kitti_eval_counts(const float* gt, const int* gt_code, const float* dt, 
                           const float* thr, const int* nthr, int compute_aos, int* cnt, double* sim, double* pr, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Validator box metrics (det_metrics.hip): P, R, mAP50, mAP50-95 — box_iou (utils/metrics.py:53), match_predictions with
+ * use_scipy = False (engine/validator.py:229-273), the validators' box preparation (models/yolo/detect/val.py:97-175,
+ * models/yolov10_3D/val.py:114-187) and ap_per_class / compute_ap (utils/metrics.py:532, :499).  fp32 boxes and IoU with FMA
+ * contraction off; fp64 recall / precision / AP.  A tp mask holds bit t = "correct at thr[t]".  At most y3d_det_metrics_max_gts() gts
+ * and y3d_det_metrics_max_dets() detections per image, at most 16 thresholds.
+ * ---------------------------------------------------------------------------------------------- */
+int y3d_det_metrics_max_gts(void);
+int y3d_det_metrics_max_dets(void);
+/* out (n1, n2) fp32 = IoU of box1[i] and box2[j], both (n, 4) xyxy fp32 */
+int y3d_box_iou(const float* box1, int n1, const float* box2, int n2, float eps, float* out, void* stream);
+/* one image: iou (n_gt, n_det) fp32, gt_cls (n_gt) / det_cls (n_det) int32, thr (n_thr) fp32 > 0 -> tp (n_det) int32 masks */
+int y3d_match_predictions(const float* iou, const int* gt_cls, int n_gt, const int* det_cls, int n_det, const float* thr, int n_thr,
+                          int* tp, void* stream);
+/* One validation batch, one workgroup per image.  mode 0 (2D): preds (B, K, 6) fp32 [x1, y1, x2, y2, conf, cls] in the letterboxed
+ * (img_h, img_w) frame, meta (B, 5) f64 [h0, w0, gain, padw, padh] (ori_shape, ratio_pad); mode 1 (3D): preds (B, K, 14) f64
+ * decode_preds_eval rows (cls col 0, box cols 2:6, score col 13), meta (B, 2) f64 [h0, w0].  keep (B, K) u8 or NULL (all rows).
+ * Targets as collated: gt_img / gt_cls (n_gt) fp32 batch_idx / cls, gt_box (n_gt, 4) fp32 normalised xywh.  Row (b, k) writes slot
+ * b * K + k of tp (int32 mask), conf (f64) and cls (int32; -1 for a row that is not kept).  An image with more gts than the limit is
+ * scored without gts and atomicMax's its gt count into status[0]. */
+int y3d_box_match_batch(int mode, const void* preds, const unsigned char* keep, int B, int K, const double* meta, int img_h, int img_w,
+                        int single_cls, const float* gt_img, const float* gt_cls, const float* gt_box, int n_gt, const float* thr,
+                        int n_thr, int* tp, double* conf, int* cls, int* status, void* stream);
+/* ap_per_class core: n detections sorted by (class, confidence descending); ucls (nc) int32 classes with targets, nl (nc) f64 = n_l + eps;
+ * x_ap (n_ap <= 129) / x_curve (n_curve <= 1024) f64 ascending grids -> ap (nc, n_thr), p_curve / r_curve (nc, n_curve) f64 */
+int y3d_ap_per_class(const int* tp, const double* conf, const int* cls, int64_t n, const int* ucls, const double* nl, int nc, int n_thr,
+                     const double* x_ap, int n_ap, const double* x_curve, int n_curve, double* ap, double* p_curve, double* r_curve,
+                     void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Optimizer step as multi-tensor launches (optim.hip): clip_grad_norm_ + SGD(nesterov, weight decay) — engine/trainer.py:567-575,
  * 734-790.  All table arguments are DEVICE arrays: tensor t has sizes[t] fp32 elements at param_ptrs[t] / grad_ptrs[t] / buf_ptrs[t];
  * workgroup c handles elements [chunk_off[c]*chunk, +chunk) of tensor chunk_tensor[c].
