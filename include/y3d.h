@@ -395,6 +395,21 @@ int y3d_kde_depth_fusion(const float* predsO, int B, int K, const float* predsM,
  * out (B, K, 14) f64 [cls, alpha, x1, y1, x2, y2, h, w, l, x, y, z, ry, score]; keep (B, K) u8 = !(score < threshold). */
 int y3d_kitti_decode(const float* preds, int B, int K, const double* calib, const double* ratio, const double* inv_trans,
                      const double* mean_size, int nc, int use_camera_dis, double threshold, double* out, unsigned char* keep, void* stream);
+/* Input pipeline, label side of KITTIDataset.__getitem__ (data/datasets/kitti.py:208-405) and its collate_fn (:579-599), one workgroup
+ * per image (kitti_labels.hip).  rec (N, 16) float64 label records, images back to back, each image's primary lines then its mixup
+ * partner's, in label-file order: [cls id (0 .. n_cls-1, -1 for any other type), truncation, occlusion, x1, y1, x2, y2 (float32
+ * values), h, w, l, pos x, y, z (float32 values), ry, 0].  img_i (B, 7) int32 = (primary start row, primary line count, partner start
+ * row, partner line count (0: no mixup), flip, original width, original height); img_f (B, 19) float64 = P2 (3x4, already flipped
+ * when flip, float32 values), trans (2x3, original -> output), crop scale.  Outputs in a static layout of max_objs (<= 64) rows per
+ * image, survivors first in the reference's order, the rest batch_idx = -1 and zeros: cls (B*max_objs) int64, bboxes (.., 4) f64
+ * xywh / resolution clipped to [0, 1], center_2d (.., 2) f32, size_2d (.., 2) f32, center_3d (.., 2) f64, size_3d (.., 3) f64,
+ * depth f64, heading_bin int64, heading_res f64, batch_idx f32; counts (B) int32; calib (B, 6) f64 = (cu, cv, fu, fv, tx, ty) x the
+ * resolution ratio; ratio_pad (B, 2, 2) f64. */
+int y3d_kitti_encode_labels(const double* rec, const int* img_i, const double* img_f, int B, int out_w, int out_h, double min_depth,
+                            double max_depth, int use_camera_dis, const double* mean_size, int n_cls, int max_objs, int64_t* cls,
+                            double* bboxes, float* center_2d, float* size_2d, double* center_3d, double* size_3d, double* depth,
+                            int64_t* heading_bin, double* heading_res, float* batch_idx, int* counts, double* calib, double* ratio_pad,
+                            void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * KITTI AP evaluation (kitti_eval.hip) — the evaluator behind KITTIDataset.get_stats (data/datasets/kitti.py:444-450):

@@ -147,3 +147,302 @@ def augment_images(imgs, partners, flips, trans_inv, out_wh, mode="float"):
     lib().kitti_image_aug(src.data_ptr(), src2.data_ptr() if src2 is not None else None, hw.data_ptr(), fl.data_ptr(), ti.data_ptr(), B, H, W,
                           0 if mode == "float" else 1, out.data_ptr(), ops.stream())
     return out
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# f3: label side of the input pipeline (data/datasets/kitti.py:208-405) and collate_fn (:579-599) on the device
+# ------------------------------------------------------------------------------------------------------------------------------
+CLASS_IDS = {"Car": 0, "Pedestrian": 1, "Cyclist": 2}  # kitti.py:24, the writelist
+RESOLUTION = (1280, 384)  # W, H (kitti.py:25)
+MAX_OBJS = 50  # kitti.py:22
+PER_BOX = ("cls", "bboxes", "center_2d", "size_2d", "center_3d", "size_3d", "depth", "heading_bin", "heading_res", "batch_idx")
+_REC_W = 16
+# the data-pipeline hyper-parameters of cfg/default.yaml the dataset reads (kitti.py:61-70)
+DATA_ARGS = dict(fliplr=0.5, random_crop=0.5, mixup=0.5, min_scale=0.8, max_scale=1.2, translate=0.1, min_depth_threshold=1,
+                 max_depth_threshold=120, cam_dis=False, load_depth_maps=False)
+
+
+def data_args(**over):
+    """DATA_ARGS with overrides, as the attribute namespace build_batch / sample_augment read"""
+    from types import SimpleNamespace
+    return SimpleNamespace(**dict(DATA_ARGS, **over))
+
+
+def _level(box, trunc, occ):
+    """kitti_utils.py Object3d.get_obj_level, from the label's own box"""
+    height = float(box[3]) - float(box[1]) + 1
+    if trunc == -1:
+        return "DontCare"
+    if height >= 40 and trunc <= 0.15 and occ <= 0:
+        return "Easy"
+    if height >= 25 and trunc <= 0.3 and occ <= 1:
+        return "Moderate"
+    if height >= 25 and trunc <= 0.5 and occ <= 2:
+        return "Hard"
+    return "UnKnown"
+
+
+def read_label(path):
+    """A KITTI label file -> dict of per-line arrays in the reference's parse dtypes (kitti_utils.py Object3d): `type`, `level` (lists of
+    str), `truncation`, `occlusion`, `alpha`, `h`, `w`, `l`, `ry` float64, `box2d` (n, 4) float32, `pos` (n, 3) float32"""
+    import numpy as np
+    cols = [ln.strip().split(" ") for ln in open(path).read().splitlines() if ln.strip()]
+    f = lambda c: np.array([float(r[c]) for r in cols], np.float64)
+    lab = {"type": [r[0] for r in cols], "truncation": f(1), "occlusion": f(2), "alpha": f(3), "h": f(8), "w": f(9), "l": f(10), "ry": f(14),
+           "box2d": np.array([[float(v) for v in r[4:8]] for r in cols], np.float32).reshape(-1, 4),
+           "pos": np.array([[float(v) for v in r[11:14]] for r in cols], np.float32).reshape(-1, 3)}
+    lab["level"] = [_level(b, t, o) for b, t, o in zip(lab["box2d"], lab["truncation"], lab["occlusion"])]
+    return lab
+
+
+def read_calib(path):
+    """A KITTI calibration file -> P2 (3, 4) float32 (its third line, kitti_utils.py get_calib_from_file)"""
+    import numpy as np
+    line = open(path).read().splitlines()[2]
+    return np.array(line.strip().split(" ")[1:], np.float32).reshape(3, 4)
+
+
+def calib_params(P2):
+    """(cu, cv, fu, fv, tx, ty) of a float32 P2 as the reference's Calibration holds them (tx, ty divided in float32)"""
+    import numpy as np
+    P = np.asarray(P2, np.float32)
+    return (float(P[0, 2]), float(P[1, 2]), float(P[0, 0]), float(P[1, 1]), float(P[0, 3] / -P[0, 0]), float(P[1, 3] / -P[1, 1]))
+
+
+def flip_calib(P2, img_size):
+    """The projection of the mirrored image (kitti_utils.py Calibration.flip): eight pixels of a 4 x 2 grid over the image, at depths
+    2 .. 78, are lifted to 3D with the float32 calibration, mirrored (x -> -x, u -> W - u), and a pinhole camera with fu = fv is fitted to
+    them by least squares in float64.  -> P2 (3, 4) float32; as in the reference, its third row is (0, 0, 0, P2[2, 3])."""
+    import numpy as np
+    W, H = float(img_size[0]), float(img_size[1])
+    cu, cv, fu, fv, tx, ty = calib_params(P2)
+    u = np.tile(np.linspace(0.0, W, 4), 2)
+    v = np.repeat(np.linspace(0.0, H, 2), 4)
+    z = np.linspace(2.0, 78.0, 8)
+    x, y = ((u - cu) * z) / fu + tx, ((v - cv) * z) / fv + ty
+    x, u = -x, W - u
+    # unknowns (f, c_u, c_v, t_u, t_v, d): u * (z + d) = f x + c_u z + t_u and v * (z + d) = f y + c_v z + t_v
+    one, nil = np.ones(8), np.zeros(8)
+    A = np.concatenate([np.stack([x, z, nil, one, nil, -u], 1), np.stack([y, nil, z, nil, one, -v], 1)])
+    rhs = np.concatenate([u * z, v * z])
+    f, c_u, c_v, t_u, t_v, _ = np.linalg.lstsq(A, rhs, rcond=None)[0]
+    out = np.zeros((3, 4), np.float32)
+    out[0] = (f, 0.0, c_u, t_u)
+    out[1] = (0.0, f, c_v, t_v)
+    out[2, 3] = np.asarray(P2, np.float32)[2, 3]
+    return out
+
+
+def sample_augment(n, items, frame_info, args, mode="train", max_objs=MAX_OBJS, resolution=RESOLUTION):
+    """The random decisions of `KITTIDataset.__getitem__` (kitti.py:132-189) for dataset positions `items`, drawn from np.random in the
+    reference's order, so a seeded run decides as the reference with workers=0: mixup random(), flip random(), crop random(), the crop's
+    three randn (scale, x shift, y shift) only when cropping, then up to 50 randint(n) partner tries.  A partner has the primary's
+    (cu, cv, fu, fv), its size (when frame_info gives one) and fewer than max_objs label lines together with it.
+    frame_info(position) -> (cam (cu, cv, fu, fv) of its unflipped float32 P2, label line count, (W, H) or None); n = dataset length.
+    -> one dict per item: mixed, flip, crop (bool), scale, center (2,), crop_size (2,), partner (position or -1), trans, trans_inv."""
+    import numpy as np
+    aug = mode in ("train", "trainval")
+    out = []
+    for item in items:
+        cam, nl, size = frame_info(item)
+        img_size = np.asarray(size, np.int64)
+        center, crop_size, scale = img_size / 2, img_size, 1.0
+        want_mix = flip = crop = False
+        if aug:
+            want_mix = np.random.random() < 0.5 and bool(args.mixup)
+            flip = np.random.random() < args.fliplr
+            if np.random.random() < args.random_crop:
+                crop = True
+                half, mid = (args.max_scale - args.min_scale) / 2, (args.max_scale + args.min_scale) / 2
+                scale = float(np.clip(np.random.randn() * half + mid, args.min_scale, args.max_scale))
+                crop_size = img_size * scale
+                t = args.translate
+                center = center + np.array([img_size[0] * np.clip(np.random.randn() * t, -2 * t, 2 * t),
+                                            img_size[1] * np.clip(np.random.randn() * t, -2 * t, 2 * t)])
+        partner = -1
+        if want_mix:
+            for _ in range(50):
+                pos = int(np.random.randint(n))
+                cam2, nl2, size2 = frame_info(pos)
+                if tuple(cam2) == tuple(cam) and (size2 is None or tuple(size2) == tuple(size)) and nl + nl2 < max_objs:
+                    partner = pos
+                    break
+        trans, trans_inv = get_affine_transform(center, crop_size, resolution, inv=True)
+        out.append(dict(mixed=partner >= 0, flip=bool(flip), crop=crop, scale=scale, center=np.asarray(center, np.float64),
+                        crop_size=np.asarray(crop_size, np.float64), partner=partner, trans=trans, trans_inv=trans_inv))
+    return out
+
+
+def label_records(lab):
+    """read_label's dict -> (n, 16) float64 records of y3d_kitti_encode_labels"""
+    import numpy as np
+    n = len(lab["type"])
+    r = np.zeros((n, _REC_W), np.float64)
+    r[:, 0] = [CLASS_IDS.get(t, -1) for t in lab["type"]]
+    r[:, 1], r[:, 2] = lab["truncation"], lab["occlusion"]
+    r[:, 3:7] = lab["box2d"]
+    r[:, 7], r[:, 8], r[:, 9] = lab["h"], lab["w"], lab["l"]
+    r[:, 10:13] = lab["pos"]
+    r[:, 13] = lab["ry"]
+    return r
+
+
+def pack_labels(labels, partners, P2s, trans, flips, scales, img_sizes, device, cls_mean_size=CLS_MEAN_SIZE):
+    """Host side of encode_labels: B images' read_label dicts (partners[b]: the mixup partner's, or None), their P2 (flipped when
+    flips[b]: flip_calib), crop matrices `trans` (2, 3), crop scales and original (W, H) -> dict of device tensors (one upload each)"""
+    import numpy as np
+    if torch.device(device).type != "cuda":
+        raise Y3DError("pack_labels: the label encoder runs on a HIP device (no host fallback)")
+    B = len(labels)
+    recs, img_i, img_f, row = [], np.zeros((B, 7), np.int32), np.zeros((B, 19), np.float64), 0
+    for b in range(B):
+        r0 = label_records(labels[b])
+        r1 = label_records(partners[b]) if partners[b] is not None else np.zeros((0, _REC_W))
+        img_i[b] = (row, len(r0), row + len(r0), len(r1), int(bool(flips[b])), int(img_sizes[b][0]), int(img_sizes[b][1]))
+        img_f[b, :12] = np.asarray(P2s[b], np.float32).reshape(12)
+        img_f[b, 12:18] = np.asarray(trans[b], np.float64).reshape(6)
+        img_f[b, 18] = float(scales[b])
+        recs += [r0, r1]
+        row += len(r0) + len(r1)
+    rec = np.concatenate(recs) if row else np.zeros((1, _REC_W))
+    up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a)).to(device=device, dtype=dt)
+    return {"rec": up(rec, torch.float64), "img_i": up(img_i, torch.int32), "img_f": up(img_f, torch.float64),
+            "mean_size": up(np.asarray(cls_mean_size, np.float64).reshape(-1, 3), torch.float64)}
+
+
+def encode_labels(packed, out_wh=RESOLUTION, min_depth=1.0, max_depth=120.0, use_camera_dis=False, max_objs=MAX_OBJS):
+    """The label encoding of `KITTIDataset.__getitem__` + `collate_fn` for a packed batch (pack_labels), one HIP launch, no host
+    synchronisation (capturable).  -> dict of the per-box keys in a static layout: image b owns rows [b * max_objs, b * max_objs + count);
+    unused rows have batch_idx = -1 (skipped by pad_targets) and zeros elsewhere; plus `counts` (B,) int32, `calib` (B, 6) float64,
+    `ratio_pad` (B, 2, 2) float64."""
+    img_i = packed["img_i"]
+    if not img_i.is_cuda or any(not packed[k].is_cuda for k in ("rec", "img_f", "mean_size")):
+        raise Y3DError("encode_labels: the packed labels must live on a HIP device (no host fallback)")
+    dev, B = img_i.device, img_i.shape[0]
+    n = B * max_objs
+    e = lambda *s, dt: torch.empty(*s, dtype=dt, device=dev)
+    o = {"cls": e(n, 1, dt=torch.int64), "bboxes": e(n, 4, dt=torch.float64), "center_2d": e(n, 2, dt=torch.float32),
+         "size_2d": e(n, 2, dt=torch.float32), "center_3d": e(n, 2, dt=torch.float64), "size_3d": e(n, 3, dt=torch.float64),
+         "depth": e(n, dt=torch.float64), "heading_bin": e(n, dt=torch.int64), "heading_res": e(n, dt=torch.float64),
+         "batch_idx": e(n, dt=torch.float32), "counts": e(B, dt=torch.int32), "calib": e(B, 6, dt=torch.float64),
+         "ratio_pad": e(B, 2, 2, dt=torch.float64)}
+    ms = packed["mean_size"]
+    lib().kitti_encode_labels(packed["rec"].data_ptr(), img_i.data_ptr(), packed["img_f"].data_ptr(), B, int(out_wh[0]), int(out_wh[1]),
+                              float(min_depth), float(max_depth), int(bool(use_camera_dis)), ms.data_ptr(), ms.shape[0], int(max_objs),
+                              *[o[k].data_ptr() for k in PER_BOX], o["counts"].data_ptr(), o["calib"].data_ptr(), o["ratio_pad"].data_ptr(),
+                              ops.stream())
+    return o
+
+
+def compact_labels(static, counts, crops, use_camera_dis=False, max_objs=MAX_OBJS):
+    """Static layout -> the ragged per-box tensors `collate_fn` returns, in its shapes and dtypes.  torch.cat promotes over every
+    image's tensor: an image without boxes contributes a float64 (0,) tensor (bboxes: float32), an image's depth is float32 when it was
+    neither cropped nor encoded as camera distance, heading_res and the 2D centre / size are float32.  counts: host ints (B,)."""
+    B = len(counts)
+    rows = torch.cat([torch.arange(b * max_objs, b * max_objs + int(c)) for b, c in enumerate(counts)]).to(static["cls"].device)
+    total = int(sum(int(c) for c in counts))
+    own = {"cls": torch.int64, "bboxes": torch.float64, "center_2d": torch.float32, "size_2d": torch.float32, "center_3d": torch.float64,
+           "size_3d": torch.float64, "heading_bin": torch.int64, "heading_res": torch.float32, "batch_idx": torch.float32}
+    out = {}
+    for k in PER_BOX:
+        dts = []
+        for b in range(B):
+            if k == "batch_idx":
+                dts.append(torch.float32)
+            elif int(counts[b]) == 0:
+                dts.append(torch.float32 if k == "bboxes" else torch.float64)
+            elif k == "depth":
+                dts.append(torch.float64 if (crops[b] or use_camera_dis) else torch.float32)
+            else:
+                dts.append(own[k])
+        dt = dts[0]
+        for d in dts[1:]:
+            dt = torch.promote_types(dt, d)
+        v = static[k].index_select(0, rows).to(dt)
+        out[k] = v if total else v.reshape(0)
+    return out
+
+
+_SPLITS = {}
+
+
+def _split(root_or_split_file, mode):
+    import os
+    if os.path.isdir(root_or_split_file):
+        split_file = os.path.join(root_or_split_file, "ImageSets", f"{mode}.txt")
+    else:
+        split_file = root_or_split_file
+    root = os.path.dirname(os.path.dirname(os.path.abspath(split_file)))
+    data = os.path.join(root, "testing" if mode == "test" else "training")
+    ids = [int(s.strip()) for s in open(split_file).read().splitlines() if s.strip()]
+    return data, ids
+
+
+def build_batch(root_or_split_file, indices, args, device, mode="train", compact=False, img_mode="uint8", resolution=RESOLUTION):
+    """`collate_fn([dataset[i] for i in indices])` of the reference's KITTIDataset (kitti.py:116-442, 579-599) with the image and label
+    work on the device: PNGs (PIL), labels and calibrations are read on the host, the random decisions drawn (sample_augment), the
+    images mixed / mirrored / cropped by augment_images and the labels encoded by encode_labels.  root_or_split_file: a split file
+    (ImageSets/<split>.txt) or the KITTI root (then ImageSets/<mode>.txt).  -> every key collate_fn returns except ori_img and depth_map;
+    the per-box keys in encode_labels' static layout, or with compact=True (one read-back of the counts) in collate_fn's ragged shapes.
+    img_mode "uint8": (B, H, W, 3) uint8 for the stem; "float": the reference's (B, 3, H, W) float32."""
+    import os
+    import numpy as np
+    from PIL import Image
+    if getattr(args, "load_depth_maps", False):
+        raise Y3DError("build_batch: depth maps (load_depth_maps) are not supported")
+    if torch.device(device).type != "cuda":
+        raise Y3DError("build_batch: the batch is built on a HIP device (no host fallback)")
+    if mode == "test":
+        raise Y3DError("build_batch: the test split has no labels")
+    data, ids = _split(root_or_split_file, mode)
+    path = lambda sub, i, ext: os.path.join(data, sub, f"{i:06d}.{ext}")
+    calib_cache, label_cache = {}, {}
+
+    def calib(i):
+        if i not in calib_cache:
+            calib_cache[i] = read_calib(path("calib", i, "txt"))
+        return calib_cache[i]
+
+    def label(i):
+        if i not in label_cache:
+            label_cache[i] = read_label(path("label_2", i, "txt"))
+        return label_cache[i]
+
+    sizes = {}
+
+    def frame_info(pos):
+        i = ids[pos]
+        P = calib(i)
+        return (P[0, 2], P[1, 2], P[0, 0], P[1, 1]), len(label(i)["type"]), sizes.get(pos)
+
+    frames = []
+    for pos in indices:
+        im = Image.open(path("image_2", ids[pos], "png"))
+        sizes[pos] = im.size
+        frames.append(im)
+    draws = sample_augment(len(ids), indices, frame_info, args, mode, MAX_OBJS, resolution)
+    to_dev = lambda im: torch.from_numpy(np.array(im.convert("RGB"))).to(device)
+    imgs = [to_dev(im) for im in frames]
+    parts = [to_dev(Image.open(path("image_2", ids[d["partner"]], "png"))) if d["mixed"] else None for d in draws]
+    img = augment_images(imgs, parts, [d["flip"] for d in draws], [d["trans_inv"] for d in draws], resolution,
+                         mode="float" if img_mode == "float" else "uint8")
+    P2s, labels, partners = [], [], []
+    for pos, d, im in zip(indices, draws, frames):
+        P = calib(ids[pos])
+        P2s.append(flip_calib(P, im.size) if d["flip"] else P)
+        labels.append(label(ids[pos]))
+        partners.append(label(ids[d["partner"]]) if d["mixed"] else None)
+    packed = pack_labels(labels, partners, P2s, [d["trans"] for d in draws], [d["flip"] for d in draws], [d["scale"] for d in draws],
+                         [im.size for im in frames], device)
+    lab = encode_labels(packed, resolution, args.min_depth_threshold, args.max_depth_threshold, bool(args.cam_dis), MAX_OBJS)
+    batch = {"img": img, "calib": lab["calib"],
+             "info": [{"img_id": ids[p], "img_size": np.array(im.size), "trans_inv": d["trans_inv"]} for p, im, d in zip(indices, frames, draws)],
+             "im_file": [f"{ids[p]:06d}.txt" for p in indices], "ori_shape": [np.array(im.size)[::-1] for im in frames],
+             "ratio_pad": lab["ratio_pad"], "mean_sizes": packed["mean_size"],
+             "mixed": torch.tensor([int(d["mixed"]) for d in draws], dtype=torch.uint8).to(device), "counts": lab["counts"]}
+    if compact:
+        batch.update(compact_labels(lab, lab["counts"].tolist(), [d["crop"] for d in draws], bool(args.cam_dis)))
+        del batch["counts"]
+    else:
+        batch.update({k: lab[k] for k in PER_BOX})
+    return batch
