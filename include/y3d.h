@@ -74,6 +74,21 @@ int y3d_conv3x3_fp8_stat_rows(int B, int H, int W);
 int y3d_fp8_scale_pitch(int C);
 int y3d_conv3x3_fp8_fwd(const uint8_t* xq, const uint8_t* xs, int B, int H, int W, int Cin, const uint8_t* wq, const uint8_t* ws, void* y, int64_t ysw,
                         int Cout, int groups, float* stat_partials, const float* scale, const float* shift, int act, void* stream);
+/* fp8 DATA GRADIENT of the same layers (opt-in: ops.set_fp8_dgrad).  dx of a 3x3 stride-1 pad-1 conv is that conv of dy with the taps
+ * flipped and the channel roles swapped: the forward kernel runs on (dy, codes) in its plain-store form.  The fp8w row scales belong to
+ * the REDUCTION index there; powers of two, they are folded exactly into dy before it is quantised:
+ *   y3d_fp8_quantize_grad: y3d_fp8_quantize_act of dy[c] * scale[c] (fp32 product, exact): dy bf16 NHWC rows (M pixels, pixel stride sw,
+ *     C % 32 == 0), scale (C) fp32 -> q (M, C) + s (M, y3d_fp8_scale_pitch(C));
+ *   y3d_fp8_pack_weight_dgrad: the fp8w quantiser's codes (Cout, Cin / groups * 9), OIHW -> wq [groups][Cin / groups][9, flipped: t -> 8 - t]
+ *     [(hi - lo) / groups] bytes for the output channels [lo, hi) (a window needs groups == 1) + ws (Cin) unit E8M0 bytes (127);
+ *   y3d_conv3x3_fp8_dgrad: dx (bf16 NHWC, Cin channels, pixel stride dxsw) from channels [lo, hi) of dyq (rows qsw bytes wide) / dys (rows
+ *     spitch bytes wide); lo % 128 == 0.  Served: y3d_conv3x3_fp8_dgrad_ok (Cout / groups a multiple of 64, >= 128; Cin / groups a
+ *     multiple of 16; H >= 4, W >= 8) with Cout = hi - lo. */
+int y3d_fp8_quantize_grad(const void* dy, int64_t sw, const float* scale, int64_t M, int C, uint8_t* q, uint8_t* s, void* stream);
+int y3d_fp8_pack_weight_dgrad(const uint8_t* codes, int Cout, int Cin, int groups, int lo, int hi, uint8_t* wq, uint8_t* ws, void* stream);
+int y3d_conv3x3_fp8_dgrad_ok(int B, int H, int W, int Cin, int Cout, int groups);
+int y3d_conv3x3_fp8_dgrad(const uint8_t* dyq, const uint8_t* dys, int64_t qsw, int spitch, int lo, int hi, int B, int H, int W, const uint8_t* wq, const uint8_t* ws,
+                          void* dx, int64_t dxsw, int Cin, int groups, void* stream);
 int y3d_conv_kpad(int dtype, int k_total);
 /* number of BatchNorm partial rows of the generic implicit-GEMM kernel: ceil(B*Ho*Wo / 128) */
 int y3d_conv_stat_blocks(int B, int Ho, int Wo);

@@ -5,7 +5,8 @@
 //                (y3d_fp8_quantize_act: scale = smallest power of two with amax(block) / scale <= 448 - nothing saturates);
 //   weights      e4m3 codes packed [G][Cn][9][Cg] + one E8M0 byte per output channel (the fp8w quantiser's power-of-two row scale).
 // The instruction multiplies fp8 x fp8 exactly, applies both scales to each 32-deep partial sum and accumulates in fp32; it retires
-// 4x the K of v_mfma_f32_16x16x32_bf16 in 2x its cycles.  dgrad / wgrad stay on the bf16 kernels (straight-through).
+// 4x the K of v_mfma_f32_16x16x32_bf16 in 2x its cycles.  The data gradient (y3d_conv3x3_fp8_dgrad, opt-in) is the SAME kernel on
+// (dy with the weight's row scales folded in, the same codes with the taps flipped and the channel roles swapped); wgrad stays bf16.
 //
 // Operand layout (tools/probe/mfma_fp8_layout.cpp, profiles/r04_mfma_fp8_layout.txt - found with exact integer data, it is NOT "32
 // consecutive k per lane"): lane l, byte j of the 32-byte operand holds K = 64 * (j >> 4) + 16 * (l >> 4) + (j & 15) of row / column
@@ -538,6 +539,52 @@ __global__ __launch_bounds__(256) void fp8_pack_w_kernel(const unsigned char* __
   }
 }
 
+// ---- gradient quantiser: fp8_act_quant_kernel with a per-channel power-of-two factor folded in first (the fp8w row scale of the layer's
+// weight: in the data gradient that channel is the REDUCTION index, where the MFMA has no scale slot - dx = sum_c (dy[c] * 2^e_c) * value(code[c])).
+// dy * scale is exact in fp32 (a bf16 value times a power of two), so the codes are those of the MX rule applied to the folded tensor.
+__global__ __launch_bounds__(256) void fp8_grad_quant_kernel(const bf16_t* __restrict__ x, long xsw, const float* __restrict__ scale, unsigned char* __restrict__ q,
+                                                             unsigned char* __restrict__ s, long M, int C) {
+  const int cpr = C >> 3, SP = fp8_scale_pitch(C);
+  const long total = M * cpr;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < ((total + 255) & ~255L); i += (long)gridDim.x * 256) {
+    const bool live = i < total;
+    const long pix = live ? i / cpr : 0;
+    const int ch = live ? (int)(i - pix * cpr) : 0;
+    float f[8];
+    uint4 u = make_uint4(0, 0, 0, 0);
+    if (live) u = *(const uint4*)(x + pix * xsw + ch * 8);
+    Chunk<bf16_t>::unpack(u, f);
+    const float4 s0 = *(const float4*)(scale + ch * 8), s1 = *(const float4*)(scale + ch * 8 + 4);
+    f[0] *= s0.x; f[1] *= s0.y; f[2] *= s0.z; f[3] *= s0.w;
+    f[4] *= s1.x; f[5] *= s1.y; f[6] *= s1.z; f[7] *= s1.w;
+    unsigned lo, hi;
+    const int sbyte = mx_quantize8(f, lo, hi);
+    if (live) {
+      *(uint2*)(q + pix * C + ch * 8) = make_uint2(lo, hi);
+      if ((ch & 3) == 0) s[pix * SP + (ch >> 2)] = (unsigned char)sbyte;
+    }
+  }
+}
+
+// ---- data-gradient weight packer: fp8w codes (Cout, Cg_in * 9) in OIHW order -> the kernel's weight layout of the SWAPPED problem,
+// [G][Cin / G][9 taps, flipped: t -> 8 - t][Cw / G] bytes with Cw = hi - lo output channels of the window [lo, hi) (G == 1) or all of them; the
+// row scales are unit (E8M0 127): the fp8w scales travel with dy (fp8_grad_quant_kernel).  A byte permutation.
+__global__ __launch_bounds__(256) void fp8_pack_w_dgrad_kernel(const unsigned char* __restrict__ codes, unsigned char* __restrict__ wq, unsigned char* __restrict__ ws,
+                                                               int Cin, int Cout, int G, int lo, int Cw) {
+  const int Cig = Cin / G, Cwg = Cw / G, Cog = Cout / G;
+  const long total = (long)Cin * 9 * Cwg;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+    const int col = (int)(i % Cwg);
+    const long r = i / Cwg;
+    const int tap = (int)(r % 9);
+    const int row = (int)(r / 9);          // g * Cig + ci
+    const int g = row / Cig, ci = row - g * Cig;
+    const long co = (long)g * Cog + lo + col;
+    wq[i] = codes[(co * Cig + ci) * 9 + (8 - tap)];
+    if (col == 0 && tap == 0) ws[row] = 127;
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -586,6 +633,52 @@ int y3d_conv3x3_fp8_fwd(const uint8_t* xq, const uint8_t* xs, int B, int H, int 
   p.xbytes = (unsigned)xb; p.wbytes = (unsigned)wb; p.sbytes = (unsigned)sb;
   hipStream_t st = (hipStream_t)stream;
   return scale ? launch_f8<1>(p, st) : launch_f8<0>(p, st);
+}
+
+int y3d_fp8_quantize_grad(const void* dy, int64_t sw, const float* scale, int64_t M, int C, uint8_t* q, uint8_t* s, void* stream) {
+  Y3D_CHECK(dy && scale && q && s && M >= 1 && C >= 32 && C % 32 == 0 && sw >= C && sw % 8 == 0, "fp8_quantize_grad: C = %d must be a multiple of 32, rows 16-byte aligned", C);
+  Y3D_CHECK(((uintptr_t)dy & 15) == 0 && ((uintptr_t)scale & 15) == 0 && ((uintptr_t)q & 7) == 0, "fp8_quantize_grad: dy / scale 16-byte, q 8-byte aligned");
+  const long total = M * (C >> 3);
+  long nb = (total + 255) / 256;
+  hipLaunchKernelGGL(fp8_grad_quant_kernel, dim3((unsigned)(nb < 8192 ? nb : 8192)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dy, (long)sw, scale, q, s, (long)M, C);
+  Y3D_LAUNCH_CHECK();
+  return Y3D_OK;
+}
+
+int y3d_fp8_pack_weight_dgrad(const uint8_t* codes, int Cout, int Cin, int groups, int lo, int hi, uint8_t* wq, uint8_t* ws, void* stream) {
+  Y3D_CHECK(codes && wq && ws && groups >= 1 && Cin >= 1 && Cout >= 1 && Cin % groups == 0 && Cout % groups == 0, "fp8_pack_weight_dgrad: bad arguments");
+  Y3D_CHECK(0 <= lo && lo < hi && hi <= Cout && (groups == 1 || (lo == 0 && hi == Cout)), "fp8_pack_weight_dgrad: window [%d, %d) of %d channels (a window needs groups == 1)", lo, hi, Cout);
+  const long total = (long)Cin * 9 * ((hi - lo) / groups);
+  long nb = (total + 255) / 256;
+  hipLaunchKernelGGL(fp8_pack_w_dgrad_kernel, dim3((unsigned)(nb < 4096 ? nb : 4096)), dim3(256), 0, (hipStream_t)stream, codes, wq, ws, Cin, Cout, groups, lo, hi - lo);
+  Y3D_LAUNCH_CHECK();
+  return Y3D_OK;
+}
+
+// the data gradient of a 3x3 stride-1 pad-1 convolution is that convolution of dy with the taps flipped and the channel roles swapped
+int y3d_conv3x3_fp8_dgrad_ok(int B, int H, int W, int Cin, int Cout, int groups) { return y3d_conv3x3_fp8_ok(B, H, W, Cout, Cin, groups); }
+
+int y3d_conv3x3_fp8_dgrad(const uint8_t* dyq, const uint8_t* dys, int64_t qsw, int spitch, int lo, int hi, int B, int H, int W, const uint8_t* wq, const uint8_t* ws,
+                          void* dx, int64_t dxsw, int Cin, int groups, void* stream) {
+  Y3D_CHECK(dyq && dys && wq && ws && dx, "conv3x3_fp8_dgrad: null argument");
+  Y3D_CHECK(0 <= lo && lo < hi && hi <= qsw && lo % 128 == 0 && (groups == 1 || lo == 0),
+            "conv3x3_fp8_dgrad: window [%d, %d) of rows %ld wide: lo must be a multiple of 128 (the slab's scale bytes are read as an aligned dword), a window needs groups == 1", lo, hi, (long)qsw);
+  const int Cw = hi - lo;
+  Y3D_CHECK(y3d_conv3x3_fp8_dgrad_ok(B, H, W, Cin, Cw, groups), "conv3x3_fp8_dgrad: geometry B=%d H=%d W=%d Cin=%d Cout=%d groups=%d is not served (Cout / groups a multiple of 64, >= 128; Cin / groups a multiple of 16; H >= 4, W >= 8)", B, H, W, Cin, Cw, groups);
+  Y3D_CHECK(qsw % 16 == 0 && spitch % 4 == 0 && (long)spitch * 32 >= hi && ((uintptr_t)dyq & 15) == 0 && ((uintptr_t)dys & 3) == 0,
+            "conv3x3_fp8_dgrad: dy rows (stride %ld) must be 16-byte aligned, the scale pitch %d whole dwords covering %d channels", (long)qsw, spitch, hi);
+  Y3D_CHECK(dxsw >= Cin && dxsw % 8 == 0 && ((uintptr_t)dx & 15) == 0, "conv3x3_fp8_dgrad: dx pixel stride %ld (>= %d, 16-byte aligned rows)", (long)dxsw, Cin);
+  F8P p;
+  p.x = dyq + lo; p.xs = dys + (lo >> 5); p.w = wq; p.ws = ws; p.y = (bf16_t*)dx; p.part = nullptr; p.scale = nullptr; p.shift = nullptr; p.act = 0;
+  p.xsw = qsw; p.xsh = (long)W * qsw; p.xsb = (long)H * W * qsw; p.ysw = dxsw; p.CS = spitch;
+  p.B = B; p.H = H; p.W = W; p.G = groups; p.Cg = Cw / groups; p.Cn = Cin / groups; p.Ktot = 9 * p.Cg;
+  p.ntx = cdiv(W, 16); p.nty = cdiv(H, 8); p.ntc = cdiv(p.Cn, 128); p.nbt = cdiv(B, 4);
+  // the buffer descriptors start at the window: what they may address ends with the tensors
+  const unsigned long xb = (unsigned long)B * H * W * qsw, wb = (unsigned long)Cin * p.Ktot, sb = (unsigned long)B * H * W * spitch;
+  Y3D_CHECK(xb < 0xfffffff0ul && wb < 0xfffffff0ul, "conv3x3_fp8_dgrad: operand larger than 4 GB");
+  Y3D_CHECK(qsw < (1 << 22), "conv3x3_fp8_dgrad: pixel stride beyond the 24-bit address multiply");
+  p.xbytes = (unsigned)(xb - lo); p.wbytes = (unsigned)wb; p.sbytes = (unsigned)(sb - (lo >> 5));
+  return launch_f8<0>(p, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -430,6 +430,8 @@ def set_weight_quant(mode):
     if mode not in (None, "fp8"):
         raise ValueError("weight quantisation mode must be None or 'fp8'")
     WEIGHT_QUANT = mode
+    if mode is None:
+        set_fp8_dgrad(False)
     bump_param_epoch()
 
 
@@ -442,8 +444,11 @@ def weight_quant():
 # (y3d_conv3x3_fp8_ok: the head's two 3x3 layers at the S / B / L / X widths) runs on v_mfma_scale_f32_16x16x128_f8f6f4: e4m3 weight
 # codes (the fp8w quantiser's) x e4m3 activations with one E8M0 scale per (pixel, 32 channels).  The activation's fp8 copy comes from its
 # producer when that is a BatchNorm + SiLU pass told to write one (`want_fp8_copy`: y3d_bn_act_fwd_q), else from y3d_fp8_quantize_act.
-# Data and weight gradients stay on the bf16 kernels (x and w_eff in bf16: straight-through).
+# Weight gradients stay on the bf16 kernels (x and w_eff in bf16: straight-through); so do the data gradients unless `set_fp8_dgrad(True)`:
+# then the data gradient of every layer whose forward took the fp8 kernel and whose swapped geometry it serves (y3d_conv3x3_fp8_dgrad_ok)
+# runs on the same kernel - dy with the weight's power-of-two row scales folded in, MX-quantised, x the SAME e4m3 codes with the taps flipped.
 FP8_CONV = False
+FP8_DGRAD = False
 _FP8_WANT = False
 _FP8_ACT = {}  # address of a bf16 activation -> (q, s, shape, z): the fp8 copy its producer wrote; dropped at the next forward
 
@@ -453,11 +458,26 @@ def set_fp8_conv(on: bool):
     if on and WEIGHT_QUANT != "fp8":
         raise ValueError('set_fp8_conv(True) needs set_weight_quant("fp8"): the kernel multiplies the fp8w quantiser\'s codes')
     FP8_CONV = bool(on)
+    if not on:
+        set_fp8_dgrad(False)
     bump_param_epoch()
 
 
 def fp8_conv():
     return FP8_CONV
+
+
+def set_fp8_dgrad(on: bool):
+    """opt-in: data gradients of the fp8 MFMA convolutions in fp8 (e4m3 / MX) as well.  Needs `set_fp8_conv(True)`; switching the fp8
+    convolutions or the fp8 weights off switches it off too."""
+    global FP8_DGRAD
+    if on and not FP8_CONV:
+        raise ValueError("set_fp8_dgrad(True) needs set_fp8_conv(True): the data gradient follows the layers whose forward runs in fp8")
+    FP8_DGRAD = bool(on)
+
+
+def fp8_dgrad():
+    return FP8_DGRAD
 
 
 class want_fp8_copy:
@@ -500,6 +520,31 @@ def fp8_weight(ent, Cg):
         lib().fp8_pack_weight_fwd(ent["codes"].data_ptr(), ent["scale"].data_ptr(), rows, Cg, wq.data_ptr(), ws.data_ptr(), stream())
         hit = ent["wq"] = (tok, wq, ws)
     return hit[1], hit[2]
+
+
+def fp8_weight_dgrad(ent, Cin, g, lo, hi):
+    """(wq [g][Cin / g][9 flipped][(hi - lo) / g] bytes, ws (Cin,) unit E8M0 bytes) of a quantised 3x3 weight for its data gradient over the
+    output channels [lo, hi); cached per window in the _QuantRegistry entry and repacked (into the same storage) when its codes changed"""
+    tok = (WEIGHT_EPOCH, ent["count"])
+    cache = ent.setdefault("wqd", {})
+    hit = cache.get((g, lo, hi))
+    if hit is None or hit[0] != tok:
+        Cout = ent["shape"][0]
+        dev = ent["codes"].device
+        wq = hit[1] if hit is not None else torch.empty(g, Cin // g, 9, (hi - lo) // g, dtype=torch.uint8, device=dev)
+        ws = hit[2] if hit is not None else torch.empty(Cin, dtype=torch.uint8, device=dev)
+        lib().fp8_pack_weight_dgrad(ent["codes"].data_ptr(), Cout, Cin, g, lo, hi, wq.data_ptr(), ws.data_ptr(), stream())
+        hit = cache[(g, lo, hi)] = (tok, wq, ws)
+    return hit[1], hit[2]
+
+
+def _fp8_dgrad_entry(cfg):
+    """the _QuantRegistry entry whose codes the fp8 data gradient of this layer multiplies, or None: the switch is on, the layer's forward
+    took the fp8 kernel (cfg[18]) and the entry still holds the weight version that forward packed (cfg[17])"""
+    if not (FP8_DGRAD and FP8_CONV and len(cfg) > 18 and isinstance(cfg[18], dict)):
+        return None
+    ent = cfg[18]
+    return ent if cfg[17] == ((WEIGHT_EPOCH, ent["count"]),) else None
 PROJ_BN_MFMA = True  # BatchNorm backward of the second head layer recomputing dz on MFMA (tests flip it: materialised path)
 STEM_FUSED = True  # the stem in one pass (tests flip it: im2col + dense conv)
 PACK_CACHE = True  # weight packs through the registry (one multi-tensor launch per step)
@@ -642,6 +687,7 @@ def _cba_forward(x, w32, g32, b32, rm, rv, k, s, p, g, act, res, res_mode, train
                                      pack_cache=False, quant=False)  # wcol is built from the already quantised stem weight
         return z, (cfg + ("stem",) if cfg is not None else None), saved
     dw = g > 1 and g == Cin and g == Cout
+    f8 = False
     # ---- input: NHWC compute dtype; the stem (Cin=3) is channel-padded while converting from NCHW fp32
     Cin_k = Cin
     if Cin % c != 0:
@@ -749,7 +795,8 @@ def _cba_forward(x, w32, g32, b32, rm, rv, k, s, p, g, act, res, res_mode, train
             stats = torch.zeros(6, Cout, dtype=torch.float32, device=dev)
             stats[2:4].copy_(ss_eval)
     if not bn_apply:  # the consumer applies BatchNorm + activation itself (FusedConvBNProjFn): hand back the pre-BN tensor
-        cfg = (B, Cin, Cin_k, H, W, Cout, Ho, Wo, k, s, p, g, dw, res_mode, training, dtype, int(act), ver[0] if ver is not None else None)
+        cfg = (B, Cin, Cin_k, H, W, Cout, Ho, Wo, k, s, p, g, dw, res_mode, training, dtype, int(act), ver[0] if ver is not None else None,
+               qent if f8 else None)
         return y, cfg, (xin, w32, y, stats, None)
     z = out_tensor(B, Cout, Ho, Wo, dtype, dev)
     rr = None
@@ -767,7 +814,9 @@ def _cba_forward(x, w32, g32, b32, rm, rv, k, s, p, g, act, res, res_mode, train
         L.bn_act_fwd(dt, y.data_ptr(), Cout, sc_t.data_ptr(), sh_t.data_ptr(), int(act), res_mode,
                      rr.data_ptr() if rr is not None else None, rr.stride(3) if rr is not None else 0, z.data_ptr(), z.stride(3), M, Cout, st)
     # [17]: version token of the weights as packed (stacked views / fp8 shadows carry their identity outside the tensor's own counter)
-    cfg = (B, Cin, Cin_k, H, W, Cout, Ho, Wo, k, s, p, g, dw, res_mode, training, dtype, int(act), ver[0] if ver is not None else None)
+    # [18]: the quantiser entry whose codes the fp8 MFMA forward multiplied (None on every other path): the fp8 data gradient follows it
+    cfg = (B, Cin, Cin_k, H, W, Cout, Ho, Wo, k, s, p, g, dw, res_mode, training, dtype, int(act), ver[0] if ver is not None else None,
+           qent if f8 else None)
     return z, cfg, (xin, w32, y, stats, rr if res_mode == 2 else None)
 
 
@@ -808,6 +857,23 @@ def _cba_backward(cfg, saved, dz, need_dx, need_dres, dx_range=None, pre=None, d
     return _conv_backward(cfg, saved, dy, dgb, dres, need_dx, dx_range, dx_out)
 
 
+def _fp8_dgrad_plan(cfg, need_dx, dx_range):
+    """(entry, lo, hi) when the data gradient of this layer runs on the fp8 kernel, else None (the bf16 call runs)"""
+    ent = _fp8_dgrad_entry(cfg)
+    if ent is None or not need_dx:
+        return None
+    B, Cin, Cin_k, H, W, Cout, Ho, Wo, k, s, p, g = cfg[:12]
+    lo, hi = dx_range if dx_range is not None else (0, Cout)
+    if Cin_k != Cin or cfg[15] != torch.bfloat16 or (k, s, p) != (3, 1, 1) or (g != 1 and (lo, hi) != (0, Cout)):
+        return None
+    # a window reads the slab's scale bytes as an aligned dword: lo and hi - lo in whole 128-channel units
+    if (lo, hi) != (0, Cout) and (lo % 128 or (hi - lo) % 128):
+        return None
+    if not lib().conv3x3_fp8_dgrad_ok(B, H, W, Cin, hi - lo, g):
+        return None
+    return ent, lo, hi
+
+
 def _conv_backward(cfg, saved, dy, dgb, dres, need_dx, dx_range, dx_out=None):
     """data and weight gradients of the conv given dy (gradient wrt its pre-BatchNorm output); cfg[17] = version token of the weights
     as the forward packed them"""
@@ -835,7 +901,26 @@ def _conv_backward(cfg, saved, dy, dgb, dres, need_dx, dx_range, dx_out=None):
         L.dwconv2d_bwd_weight(dt, xin.data_ptr(), sb, sh, sw, B, H, W, Cin, dy.data_ptr(), Cout, Ho, Wo, k, k, s, p, slab.data_ptr(),
                               dW.data_ptr(), 0, st)
     else:
-        if need_dx and Cin_k == Cin:
+        plan = _fp8_dgrad_plan(cfg, need_dx, dx_range) if not stem else None
+        if plan is not None and not (px_dense(dy) and dy.data_ptr() % 16 == 0 and dy.stride(3) % 8 == 0):
+            plan = None
+        if plan is not None:
+            # fp8 data gradient (set_fp8_dgrad): the forward kernel on (dy * row scales -> MX, the forward's codes flipped and swapped)
+            qent, lo, hi = plan
+            wqd, wsd = fp8_weight_dgrad(qent, Cin, g, lo, hi)
+            # dy's fp8 copy: the stand-alone quantiser over the window's channels (a copy written by the BatchNorm-backward apply pass itself
+            # measured slower than apply + this pass on the head shapes and is not part of the path: DESIGN.md 3.9)
+            co = hi - lo
+            dq = torch.empty(B, Ho, Wo, co, dtype=torch.uint8, device=dev)
+            ds = torch.empty(B, Ho, Wo, L.fp8_scale_pitch(co), dtype=torch.uint8, device=dev)
+            L.fp8_quantize_grad(dy.data_ptr() + lo * esz, dy.stride(3), qent["scale"].data_ptr() + lo * 4, M, co, dq.data_ptr(), ds.data_ptr(), st)
+            dx = dx_out if dx_out is not None else nhwc_empty(B, Cin, H, W, dtype, dev)
+            if not (px_dense(dx) and dx.data_ptr() % 16 == 0 and dx.stride(3) % 8 == 0):
+                raise Y3DError("fp8 data gradient: dx must be a pixel-dense NHWC tensor with 16-byte aligned rows")
+            _timed(("conv_dgrad_fp8", dt, B, H, W, Cin, hi - lo, k, s, g),
+                   lambda: L.conv3x3_fp8_dgrad(dq.data_ptr(), ds.data_ptr(), co, ds.shape[3], 0, co, B, H, W, wqd.data_ptr(), wsd.data_ptr(),
+                                               dx.data_ptr(), dx.stride(3), Cin, g, st))
+        elif need_dx and Cin_k == Cin:
             lo, hi = dx_range if dx_range is not None else (0, Cout)
             assert g == 1 or (lo, hi) == (0, Cout)
             co = hi - lo
