@@ -218,9 +218,9 @@ class DDDetectionLoss:
 
     def targets(self, batch, B, H, W, dev):
         """padded ground truth of one step (loss.py:848-856): (gt (B, cap, 17), n_used) or None when the batch has no box at all"""
-        rows = torch.cat([batch[k].to(dev).float().view(batch[k].shape[0], -1) for k in self.GT_KEYS], 1)
-        if rows.shape[0] == 0:
+        if batch["batch_idx"].shape[0] == 0:  # (checked first: a `view(0, -1)` of an empty tensor is ambiguous and raises)
             return None
+        rows = torch.cat([batch[k].to(dev).float().view(batch[k].shape[0], -1) for k in self.GT_KEYS], 1)
         return pad_targets(rows, B, 17, (W * self.stride[0], H * self.stride[0]))
 
     def __call__(self, preds, batch, embeddings=None, targets=None):
