@@ -350,6 +350,30 @@ int y3d_loss3d(int dtype, int nl, const void* const* maps, const int64_t* psw, v
                const int* target_gt_idx, const float* target_scores, const float* scal, float w_loss2d, float w_cls, float w_depth,
                float w_offset3d, float w_size3d, float w_heading, float grad_scale, float* partials, float* items, void* stream);
 
+/* Feature distillation, utils/loss.py:1156-1188 SupervisionLoss.forward_head as called at :893-898, for one head set (distill.hip).
+ * embs[l]: (B, H[l], W[l], >= C) NHWC slice of the depth branch's first-layer output at level l (pointer at its channel 0, pixel
+ * stride psw[l] elements, dtype `dtype`); C % 8 == 0.  teacher: (B, C, th, tw) of `teacher_dtype` with element strides (tsb, tsc, tsh,
+ * tsw): NCHW and NHWC are both accepted.  gt: the (B, n, 17) padded targets; fg_mask / target_gt_idx / scal: outputs of
+ * y3d_tal3d_assign (scal[0] = max(sum(target_scores), 1)); mixed: (B) uint8 or NULL when no_mixup == 0.  criterion: 0 soft, 1 mse,
+ * 2 cos.  An image takes part when it has a valid box and is not (no_mixup and mixed).  The teacher row of an anchor is read at
+ * round-half-even(center_3d / (img_w, img_h) * (tw, th)) of padded row target_gt_idx, clamped to the map: the valid rows of an image
+ * must be a prefix of its n rows (y3d_pad_targets lays them out so).  An image with boxes but no foreground anchor contributes 0 (the
+ * reference: NaN).
+ * Outputs: loss[0] = the item as the reference stores it in loss[6] (weighted, divided by scal[0]); the COMPACT gradient of loss[0]
+ * wrt the embeddings: row r (C values of `dtype`) belongs to image idx[2r], anchor idx[2r+1] (level-major, row-major), rows ordered by
+ * (image, anchor); counts[0..B) = foreground anchors per participating image (else 0), counts[B] = rows written = min(total, cap),
+ * counts[B+1] = total.  cap = row capacity: B*n*topk bounds the assigner's foreground set.  counts: B+2 ints, idx: 2*cap ints,
+ * rows: cap*C elements, partials: ceil(cap/4) floats.  No float atomics: the results are the same bits on every run. */
+int y3d_distill_loss(int dtype, int nl, const void* const* embs, const int64_t* psw, const int* H, const int* W, int B, int C,
+                     const void* teacher, int teacher_dtype, int th, int tw, int64_t tsb, int64_t tsc, int64_t tsh, int64_t tsw,
+                     const float* gt, int n, const uint8_t* fg_mask, const int* target_gt_idx, const float* scal, const uint8_t* mixed,
+                     int img_w, int img_h, float T, float weight, int criterion, int no_mixup, int cap, int* counts, int* idx,
+                     void* rows, float* partials, float* loss, void* stream);
+/* grad[b, y, x, 0..C) += scale[0] * row r for every row of y3d_distill_loss whose anchor lies in the level that starts at anchor a0
+ * (H x W pixels); grad: pointer at the slice's channel 0 with element strides (sb, sh, sw) of image / row / pixel; scale: device fp32. */
+int y3d_distill_scatter(int dtype, const void* rows, const int* idx, const int* nrows, const float* scale, int cap, int C, void* grad,
+                        int64_t sb, int64_t sh, int64_t sw, int a0, int H, int W, void* stream);
+
 /* 2D counterparts (tal_loss2d.hip): TaskAlignedAssigner utils/tal.py:45-94 and v8DetectionLoss utils/loss.py:206-257 (+BboxLoss :82-113,
  * DFL block.py:59-62).  maps[l]: (B, H, W, 64 + nc) with channel order [4 x 16 DFL bins | nc class logits]; gt: (B, n, 5) = cls | box xyxy px.
  * scratch as y3d_tal3d_scratch_floats.  items[3] = (box, cls, dfl) incl. gains; partials: 3 * ceil(B*A/256) floats */

@@ -24,7 +24,7 @@ import torch.distributed as dist
 PER_BOX_KEYS = ("cls", "bboxes", "center_2d", "size_2d", "center_3d", "size_3d", "depth", "heading_bin", "heading_res")
 # per-image entries: stacked tensors (`depth_map` is a (B, 1) placeholder unless depth maps are loaded, kitti.py:409-420) and the
 # tuples of B python objects collate_fn leaves un-stacked (`ori_img`, `info`, `im_file`, `ori_shape`)
-PER_IMAGE_KEYS = ("img", "calib", "mixed", "im_file", "ori_shape", "resized_shape", "ratio_pad", "info", "depth_map", "coord_range", "ori_img")
+PER_IMAGE_KEYS = ("img", "calib", "mixed", "teacher_emb", "im_file", "ori_shape", "resized_shape", "ratio_pad", "info", "depth_map", "coord_range", "ori_img")
 REPLICATED_KEYS = ("mean_sizes",)
 
 

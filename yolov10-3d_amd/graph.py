@@ -83,6 +83,10 @@ class GraphedTrainStep:
     Constructing one does NOT train: the warm-up steps it needs run on the first batch and are undone (parameters, BatchNorm buffers,
     optimizer state and step counts are restored in place before the capture).
 
+    Feature distillation (`distillation: True`): a "teacher_emb" batch entry is a static per-image tensor like the image; with a
+    teacher callable registered instead (loss.set_teacher) the call happens outside the graph, before every replay; the step keeps the
+    callable that was registered when it was constructed.
+
     Static shapes: the per-box label tensors (`ddp.PER_BOX_KEYS` + `batch_idx`) are padded to `label_capacity` rows (default: 64 per
     image, the assigner's own limit); padding rows carry batch_idx = -1, which no image matches.  `step(batch)` copies the batch into
     the static buffers and replays.  Left to the caller, eagerly, after the replay: `ema.update` (its decay ramp is a host-side
@@ -110,6 +114,14 @@ class GraphedTrainStep:
                 self.static[k] = t
             else:
                 self.static[k] = v.detach().clone()
+        # feature distillation with a registered teacher callable (loss.set_teacher) and no "teacher_emb" entry: the teacher is not part of
+        # the captured step - it runs eagerly on the static image before every replay and its map is copied into a static entry
+        self.teacher_fn = None
+        args = getattr(model, "args", None)
+        if getattr(args, "distillation", False) and "teacher_emb" not in batch:
+            self.teacher_fn = _loss.get_teacher()
+            if self.teacher_fn is not None:
+                self.static["teacher_emb"] = _loss.teacher_map({"img": self.static["img"]}, fn=self.teacher_fn).clone()
         self.convs = [m for m in model.modules() if isinstance(m, Conv)]
         self._load(batch)
         # The warm-up below runs REAL steps (the weight packs build their pointer / chunk tables on the second one, with a host-to-device
@@ -204,6 +216,8 @@ class GraphedTrainStep:
         if n > self.cap:
             raise Y3DError(f"GraphedTrainStep: {n} boxes in the batch, label capacity {self.cap}")
         for k, s in self.static.items():
+            if k == "teacher_emb" and self.teacher_fn is not None and k not in batch:
+                continue  # made from the static image below
             v = batch[k]
             if not torch.is_tensor(v) or v is s:
                 continue
@@ -215,6 +229,9 @@ class GraphedTrainStep:
                 if v.shape != s.shape:
                     raise Y3DError(f"GraphedTrainStep: batch entry {k!r} changed shape {tuple(s.shape)} -> {tuple(v.shape)}")
                 s.copy_(v, non_blocking=True)
+        if self.teacher_fn is not None and "teacher_emb" not in batch:
+            from . import loss as _loss
+            self.static["teacher_emb"].copy_(_loss.teacher_map({"img": self.static["img"]}, fn=self.teacher_fn), non_blocking=True)
 
     def __call__(self, batch=None):
         from . import loss as _loss

@@ -9,12 +9,17 @@ Both training losses (3D: DetectLoss3d / DDDetectionLoss, 2D: v10DetectLoss / v8
 terms and the gradient wrt the head maps) run on the fused HIP kernels of csrc/tal_loss3d.hip / tal_loss2d.hip (`Loss3dFn`,
 `Loss2dFn`).  Tie rule of the top-k is pinned to lowest-index-first.  Torch formulations of the assigners used
 as test comparators live in tests/torch_assigners.py, not here.
+
+Feature distillation (`distillation: True`; SupervisionLoss.forward_head :1156-1188): the seventh item of each 3D head set runs on
+csrc/distill.hip (`DistillFn`) over a teacher feature map the caller supplies (batch["teacher_emb"] or `set_teacher`); the DINOv2
+teacher network itself is not part of the package.
 """
 from __future__ import annotations
 
 import torch
 import torch.nn.functional as F
 
+import contextlib
 import ctypes
 
 from . import ops
@@ -90,6 +95,159 @@ def _flatten_maps(feats):
     return torch.cat([f.permute(0, 2, 3, 1).reshape(B, -1, no) for f in feats], 1).float()
 
 
+_SCAL_TAP = None  # a list while a distillation step runs: _loss3d_set appends each set's device words [max(sum(target_scores), 1), n_fg]
+
+
+class _tap_scal:
+    """with _tap_scal() as tap: the `scal` words of the head sets assigned inside, in call order (the distillation item divides by
+    the first word, loss.py:898; the word never visits the host)"""
+
+    def __enter__(self):
+        global _SCAL_TAP
+        self.prev, _SCAL_TAP = _SCAL_TAP, []
+        return _SCAL_TAP
+
+    def __exit__(self, *exc):
+        global _SCAL_TAP
+        _SCAL_TAP = self.prev
+
+
+_TEACHER = None
+
+
+def set_teacher(fn):
+    """Register the distillation teacher: a callable with `DinoDepther.forward`'s contract, `(depth_maps, embeddings) = fn(img)` with
+    embeddings (B, C, h, w) on the HIP device, C = width of the depth branch.  It is called once per step under torch.no_grad() when
+    the batch carries no "teacher_emb" entry, and both head sets share its result.  None unregisters.  -> the previous callable"""
+    global _TEACHER
+    prev, _TEACHER = _TEACHER, fn
+    return prev
+
+
+def get_teacher():
+    return _TEACHER
+
+
+def teacher_map(batch, C=None, fn=None, like=None):
+    """the teacher feature map of a step: batch["teacher_emb"], else `fn` / the registered callable on batch["img"]
+    (utils/loss.py:1159-1160).  C: expected channel count; like: a tensor whose batch size and device the map must share"""
+    t = batch.get("teacher_emb")
+    fn = fn if fn is not None else _TEACHER
+    if t is None:
+        if fn is None:
+            raise Y3DError('distillation needs a teacher feature map: pass it as batch["teacher_emb"] (B, C, h, w) or register a callable '
+                           "with loss.set_teacher(fn), (depth_maps, embeddings) = fn(img); the DINOv2 teacher itself is not part of this package")
+        with torch.no_grad():
+            t = fn(batch["img"])[1]
+    if not (torch.is_tensor(t) and t.dim() == 4):
+        raise ValueError("distillation: the teacher map must be a (B, C, h, w) tensor")
+    if not t.is_cuda:
+        raise Y3DError("distillation runs on the HIP kernels of distill.hip: the teacher map must live on a HIP device (no CPU fallback)")
+    if C is not None and t.shape[1] != C:
+        raise ValueError(f"distillation: the teacher map has {t.shape[1]} channels, the depth branch of the head is {C} wide")
+    if like is not None:
+        check_teacher(t, like)
+    t = t.detach()
+    return t if t.dtype in (torch.float32, ops.compute_dtype()) else t.float()
+
+
+def check_teacher(t, emb):
+    """the kernel reads teacher image b for every image b of the embeddings, on the embeddings' device"""
+    if t.shape[0] != emb.shape[0]:
+        raise ValueError(f"distillation: the teacher map holds {t.shape[0]} images, the batch {emb.shape[0]}")
+    if t.device != emb.device:
+        raise ValueError(f"distillation: the teacher map lives on {t.device}, the head's embeddings on {emb.device}")
+    if t.shape[1] != emb.shape[1]:
+        raise ValueError(f"distillation: the teacher map has {t.shape[1]} channels, the depth branch of the head is {emb.shape[1]} wide")
+
+
+CRITERIA = {"soft": 0, "mse": 1, "cos": 2}
+
+
+class DistillFn(torch.autograd.Function):
+    """utils/loss.py:893-898 + 1156-1188 for one head set on the HIP kernels of csrc/distill.hip: the distillation item (weighted,
+    divided by the target-score sum) and its gradient wrt the depth branch's first-layer embeddings, as compact rows.
+    apply(spec, *tensors) -> item (0-dim fp32).  spec: dict(embs, teacher, gt, fg, gi, scal, mixed, img_wh, T, weight, crit, no_mixup,
+    cap, slots, which).  Two ways back into the head:
+      * slots is None: `tensors` are the embeddings (one (B, C, H, W) NHWC map per level) and the backward returns their dense
+        gradients (zeros + scattered rows) - the per-branch head.
+      * slots (one per level, made by v10Detect3d.forward_train_fused): the embeddings are channel slices of z1 and take NO gradient
+        through autograd; `tensors` are the head maps, given only so that this backward runs before the head's.  The rows are left in
+        the slots, this backward adds the scale, and ops.InjectRowsFn adds scale * rows into z1's gradient.
+    The valid rows of every image of `gt` must be a prefix of its rows (pad_targets lays them out so): target_gt_idx indexes padded
+    rows here, valid rows in the reference.  An image with boxes but no foreground anchor contributes 0 (the reference: NaN)."""
+
+    @staticmethod
+    def forward(ctx, spec, *tensors):
+        L = lib()
+        embs, teacher, gt, fg = spec["embs"], spec["teacher"], spec["gt"], spec["fg"]
+        dtype, dev = embs[0].dtype, embs[0].device
+        if dtype != ops.compute_dtype() or not all(e.is_cuda and ops.is_nhwc(e) and ops.px_dense(e) for e in embs):
+            raise Y3DError("DistillFn: embeddings must be pixel-dense NHWC tensors of the compute dtype on a HIP device")
+        nl = len(embs)
+        B, C = embs[0].shape[:2]
+        Hs, Ws = [e.shape[2] for e in embs], [e.shape[3] for e in embs]
+        A, n, cap = sum(h * w for h, w in zip(Hs, Ws)), gt.shape[1], int(spec["cap"])
+        if fg.shape != (B, A):
+            raise ValueError(f"DistillFn: fg_mask {tuple(fg.shape)} does not match the {B} x {A} anchors of the embeddings")
+        check_teacher(teacher, embs[0])
+        if spec["mixed"] is not None and spec["mixed"].numel() != B:
+            raise ValueError(f"DistillFn: {spec['mixed'].numel()} `mixed` flags for {B} images")
+        if gt.shape[0] != B or spec["gi"].shape != (B, A):
+            raise ValueError(f"DistillFn: targets {tuple(gt.shape)} / target_gt_idx {tuple(spec['gi'].shape)} do not match {B} images x {A} anchors")
+        counts = torch.empty(B + 2, dtype=torch.int32, device=dev)
+        idx = torch.empty(cap, 2, dtype=torch.int32, device=dev)
+        rows = torch.empty(cap, C, dtype=dtype, device=dev)
+        part = torch.empty((cap + 3) // 4, dtype=torch.float32, device=dev)
+        item = torch.empty(1, dtype=torch.float32, device=dev)
+        mixed = spec["mixed"]
+        L.distill_loss(ops.code(dtype), nl, (ctypes.c_void_p * nl)(*[e.data_ptr() for e in embs]), (ctypes.c_int64 * nl)(*[e.stride(3) for e in embs]),
+                       (ctypes.c_int * nl)(*Hs), (ctypes.c_int * nl)(*Ws), B, C, teacher.data_ptr(), ops.code(teacher.dtype), teacher.shape[2],
+                       teacher.shape[3], *teacher.stride(), gt.data_ptr(), n, fg.data_ptr(), spec["gi"].data_ptr(), spec["scal"].data_ptr(),
+                       mixed.data_ptr() if mixed is not None else None, int(spec["img_wh"][0]), int(spec["img_wh"][1]), float(spec["T"]),
+                       float(spec["weight"]), int(spec["crit"]), int(bool(spec["no_mixup"])), cap, counts.data_ptr(), idx.data_ptr(), rows.data_ptr(),
+                       part.data_ptr(), item.data_ptr(), ops.stream())
+        ctx.entries, a0 = [], 0
+        for l in range(nl):
+            ctx.entries.append({"rows": rows, "idx": idx, "nrows": counts[B:], "cap": cap, "C": C, "a0": a0, "scale": None, "shape": (B, C, Hs[l], Ws[l])})
+            a0 += Hs[l] * Ws[l]
+        ctx.sparse = spec["slots"] is not None
+        if ctx.sparse:
+            for e, slot in zip(ctx.entries, spec["slots"]):
+                e["off"] = slot["offs"][spec["which"]]
+                slot.setdefault("entries", []).append(e)
+        ctx.nt, ctx.dtype, ctx.dev = len(tensors), dtype, dev
+        spec["compact"] = (rows, idx, counts)  # (rows, (image, anchor) index, [n_fg per image..., rows written, total]) for tests / tools
+        return item.reshape(())
+
+    @staticmethod
+    def backward(ctx, d):
+        if d is None:
+            return (None,) * (1 + ctx.nt)
+        scale = d.detach().float().reshape(1).contiguous()
+        if ctx.sparse:
+            for e in ctx.entries:
+                e["scale"] = scale
+            return (None,) * (1 + ctx.nt)
+        grads = []
+        for e in ctx.entries:
+            B, C, H, W = e["shape"]
+            g = ops.nhwc_empty(B, C, H, W, ctx.dtype, ctx.dev).zero_()
+            lib().distill_scatter(ops.code(ctx.dtype), e["rows"].data_ptr(), e["idx"].data_ptr(), e["nrows"].data_ptr(), scale.data_ptr(), e["cap"], C,
+                                  g.data_ptr(), *ops.s3(g), e["a0"], H, W, ops.stream())
+            grads.append(g)
+        return (None, *grads)
+
+
+def loss_names(args):
+    """models/yolov10_3D/train.py:33-39: names of the loss items DetectLoss3d returns, one-to-many set first"""
+    om = ["box_om", "cls_om", "dep_om", "o3d_om", "s3d_om", "hd_om"]
+    oo = ["box_oo", "cls_oo", "dep_oo", "o3d_oo", "s3d_oo", "hd_oo"]
+    if getattr(args, "distillation", False):
+        om, oo = om + ["dis_om"], oo + ["dis_oo"]
+    return om + oo
+
+
 def _loss3d_set(cfg, gt, n_used, calib, mean_sizes, map_ptrs, psw, grad_ptrs, gsw, Hs, Ws, B, dtype, dev):
     """one head set on the HIP kernels: assignment + six loss items + gradient rows written at grad_ptrs (pixel stride gsw).
     -> (items[6], fg (B, A) uint8, gt_idx (B, A) int32, target_scores (B, A, nc))"""
@@ -112,6 +270,8 @@ def _loss3d_set(cfg, gt, n_used, calib, mean_sizes, map_ptrs, psw, grad_ptrs, gs
     gi = torch.empty(B, A, dtype=torch.int32, device=dev)
     ts = torch.empty(B, A, nc, dtype=torch.float32, device=dev)
     scal = torch.empty(2, dtype=torch.float32, device=dev)
+    if _SCAL_TAP is not None:
+        _SCAL_TAP.append(scal)
     L.tal3d_assign(dt, nl, c_maps, c_psw, c_H, c_W, c_st, B, nc, gt.data_ptr(), n, calib.data_ptr(), mean_sizes.data_ptr(), topk,
                    alpha, beta, gamma, int(mode), scratch.data_ptr(), fg.data_ptr(), gi.data_ptr(), ts.data_ptr(), scal.data_ptr(),
                    n_used.data_ptr() if n_used is not None else None, st)
@@ -211,8 +371,13 @@ class DDDetectionLoss:
             raise ValueError(f"kps_dist_metric {h.kps_dist_metric!r}: 'l1' or 'l2' (utils/tal.py:465-470)")
         self.mode = (1 if h.tal_2d else 0) | (2 if h.tal_3d else 0) | (4 if h.kps_dist_metric == "l2" else 0) | (8 if h.constrain_anchors else 0)
         self.topk = tal_topk
-        if getattr(h, "distillation", False):
-            raise NotImplementedError("distillation needs the DINOv2 teacher (network); pinned off (SURVEY §0.5)")
+        # feature distillation (loss.py:792-793, 1146-1150): the loss runs here, the teacher map is supplied (batch["teacher_emb"] / set_teacher)
+        self.distillation = bool(getattr(h, "distillation", False))
+        m.distill = self.distillation  # on: the fused head opens its sparse gradient path (modules.v10Detect3d.forward_train_fused)
+        if self.distillation:
+            if h.distillation_loss not in CRITERIA:
+                raise RuntimeError(f"Unknown criterion function: {h.distillation_loss}")  # the reference's message, loss.py:1185
+            self.dis = (float(h.distillation_temp), float(h.distillation_weight), CRITERIA[h.distillation_loss], bool(h.distillation_no_mixup))
 
     GT_KEYS = ("batch_idx", "cls", "bboxes", "center_2d", "size_2d", "center_3d", "size_3d", "depth", "heading_bin", "heading_res")
 
@@ -223,7 +388,7 @@ class DDDetectionLoss:
         rows = torch.cat([batch[k].to(dev).float().view(batch[k].shape[0], -1) for k in self.GT_KEYS], 1)
         return pad_targets(rows, B, 17, (W * self.stride[0], H * self.stride[0]))
 
-    def __call__(self, preds, batch, embeddings=None, targets=None):
+    def __call__(self, preds, batch, embeddings=None, targets=None, teacher=None):
         """`targets`: the result of `self.targets(...)` when the caller shares it between the two head sets of a step"""
         feats = preds[1] if isinstance(preds, tuple) else preds
         dev = feats[0].device
@@ -234,13 +399,47 @@ class DDDetectionLoss:
         if targets is None:
             targets = self.targets(batch, B, H, W, dev)
         if targets is None:
-            loss = torch.zeros(6, device=dev)
+            loss = torch.zeros(7 if self.distillation else 6, device=dev)
             return loss.sum() * B, loss  # reference: graph-less zeros (loss.py:873-877); callers skip the step
         g, n_used = targets
         maps = [f if f.dtype == ops.compute_dtype() else f.to(ops.compute_dtype()) for f in feats]
-        total, items, fg, gt_idx, t_sc = Loss3dFn.apply(self.cfg(len(feats)), g, n_used, batch["calib"].to(dev), batch["mean_sizes"].to(dev), *maps)
+        with (_tap_scal() if self.distillation else contextlib.nullcontext()) as tap:
+            total, items, fg, gt_idx, t_sc = Loss3dFn.apply(self.cfg(len(feats)), g, n_used, batch["calib"].to(dev), batch["mean_sizes"].to(dev), *maps)
         self._assignment = (fg, gt_idx, t_sc)
-        return total * B, items
+        if not self.distillation:
+            return total * B, items
+        if embeddings is None:
+            raise Y3DError("distillation: the head's embeddings (preds['o2o_embs'] / preds['o2m_embs']) must be passed as `embeddings`")
+        dis = self.distill(batch, g, embeddings, fg, gt_idx, tap[0], (W * self.stride[0], H * self.stride[0]), teacher=teacher)
+        return (total + dis) * B, torch.cat((items, dis.detach().reshape(1)))
+
+    def distill(self, batch, gt, embeddings, fg, gt_idx, scal, img_wh, teacher=None, slots=None, which=0, ties=()):
+        """the distillation item of this head set (loss.py:893-898) -> 0-dim tensor tied into the autograd graph (DistillFn)"""
+        embs = list(embeddings)
+        dev = embs[0].device
+        if teacher is None:
+            teacher = teacher_map(batch, like=embs[0])
+        else:
+            check_teacher(teacher, embs[0])
+        T, weight, crit, no_mixup = self.dis
+        mixed = None
+        if no_mixup:
+            if "mixed" not in batch:
+                raise Y3DError('distillation_no_mixup: the batch needs its per-image "mixed" flags')
+            mixed = batch["mixed"].to(dev).to(torch.uint8).contiguous()
+        if "img" in batch and torch.is_tensor(batch["img"]):
+            img_wh = (batch["img"].shape[3], batch["img"].shape[2])  # loss.py:1165
+        B, n = gt.shape[:2]
+        A = sum(e.shape[2] * e.shape[3] for e in embs)
+        spec = dict(teacher=teacher, gt=gt.float().contiguous(), fg=fg, gi=gt_idx, scal=scal, mixed=mixed, img_wh=img_wh, T=T, weight=weight, crit=crit,
+                    no_mixup=no_mixup, cap=B * min(A, n * self.topk), slots=slots, which=which)
+        if slots is not None:
+            spec["embs"] = [e.detach() for e in embs]
+            return DistillFn.apply(spec, *ties)
+        dt = ops.compute_dtype()
+        embs = [e if (e.dtype == dt and ops.is_nhwc(e) and ops.px_dense(e)) else ops.to_nhwc(e, dt, dense=True) for e in embs]
+        spec["embs"] = [e.detach() for e in embs]
+        return DistillFn.apply(spec, *embs)
 
     def cfg(self, nl):
         h = self.hyp
@@ -274,6 +473,19 @@ class DetectLoss3d:
                 return None
         return list(maps)
 
+    @staticmethod
+    def _z1_slots(slots, e1, em):
+        """`slots`: preds["_y3d_distill"] of the fused head, accepted only when the embeddings really are the channel slices of z1 the
+        slots describe (then their gradient goes in as compact rows, ops.InjectRowsFn); else None: plain autograd"""
+        if not slots or len(slots) != len(e1) or len(e1) != len(em):
+            return None
+        for s, a, b in zip(slots, e1, em):
+            esz = a.element_size()
+            if (a.dtype != ops.compute_dtype() or a.data_ptr() != s["ptr"] + s["offs"][0] * esz or b.data_ptr() != s["ptr"] + s["offs"][1] * esz
+                    or a.shape[1] != s["C"][0] or b.shape[1] != s["C"][1] or not (ops.is_nhwc(a) and ops.px_dense(a) and ops.px_dense(b))):
+                return None
+        return slots
+
     def __call__(self, preds, batch):
         o2o = preds["one2one"][1] if isinstance(preds["one2one"], tuple) else preds["one2one"]
         dev = o2o[0].device
@@ -281,16 +493,28 @@ class DetectLoss3d:
         tg = self.one2one.targets(batch, B, H, W, dev) if o2o[0].is_cuda else None  # padded once per step
         kw = {"targets": tg} if tg is not None else {}
         o2m = preds.get("one2many", None)
+        dist = self.one2one.distillation and tg is not None
+        if dist:  # one teacher map per step, shared by both head sets (the reference runs its teacher once per set, loss.py:1159-1160)
+            kw["teacher"] = teacher_map(batch, like=preds["o2o_embs"][0])
         if o2m and tg is not None:
             o2m = o2m[1] if isinstance(o2m, tuple) else o2m
             bases = self._shared_maps(preds.get("_y3d_maps"), o2o, o2m, self.one2one.no)
             if bases is not None:
                 g, n_used = tg
                 nl = len(bases)
-                t1, i1, tm, im, fg1, gi1, ts1, fgm, gim, tsm = DualLoss3dFn.apply(self.one2one.cfg(nl), self.one2many.cfg(nl), g, n_used, batch["calib"].to(dev),
-                                                                                  batch["mean_sizes"].to(dev), *bases)
+                with (_tap_scal() if dist else contextlib.nullcontext()) as tap:
+                    t1, i1, tm, im, fg1, gi1, ts1, fgm, gim, tsm = DualLoss3dFn.apply(self.one2one.cfg(nl), self.one2many.cfg(nl), g, n_used, batch["calib"].to(dev),
+                                                                                      batch["mean_sizes"].to(dev), *bases)
                 self.one2one._assignment, self.one2many._assignment = (fg1, gi1, ts1), (fgm, gim, tsm)
-                return tm * B + t1 * B, torch.cat((im, i1))
+                if not dist:
+                    return tm * B + t1 * B, torch.cat((im, i1))
+                e1, em = preds["o2o_embs"], preds["o2m_embs"]
+                slots = self._z1_slots(preds.get("_y3d_distill"), e1, em)
+                ties = tuple(bases) if slots is not None else ()
+                wh = (W * self.one2one.stride[0], H * self.one2one.stride[0])
+                d1 = self.one2one.distill(batch, g, e1, fg1, gi1, tap[0], wh, teacher=kw["teacher"], slots=slots, which=0, ties=ties)
+                dm = self.one2many.distill(batch, g, em, fgm, gim, tap[1], wh, teacher=kw["teacher"], slots=slots, which=1, ties=ties)
+                return (tm + dm) * B + (t1 + d1) * B, torch.cat((im, dm.detach().reshape(1), i1, d1.detach().reshape(1)))
         l1, i1 = self.one2one(preds["one2one"], batch, embeddings=preds.get("o2o_embs"), **kw)
         if o2m:
             lm, im = self.one2many(preds["one2many"], batch, embeddings=preds.get("o2m_embs"), **kw)

@@ -414,6 +414,7 @@ class v10Detect3d(nn.Module):
     export = False
     shape = None
     fused = True  # sibling-branch fusion of the training forward (set False for the per-branch reference form)
+    distill = False  # set by loss.DDDetectionLoss under `distillation: True`: the fused forward opens the sparse gradient path into z1
     PREDECESSORS = {"cls": (), "o2d": (), "s2d": (), "o3d": ("cls",), "s3d": ("cls",), "hd": ("cls",), "dep": ("cls", "s3d"),
                     "dep_un": ("cls", "s3d", "dep")}  # head.py:585-594
 
@@ -543,12 +544,18 @@ class v10Detect3d(nn.Module):
         (B, 2*no, H, W) map.  Numerically identical to the per-branch form (BatchNorm is per channel)."""
         o2o, o2m, e_o2o, e_o2m = [], [], [], []
         self._maps = []  # the (B, 2*no, H, W) maps the two head sets are channel halves of: the fused loss takes them whole
+        self._slots = []
         for i in range(self.nl):
             branches, mids, s1, s2, parts, pos = self._stacks(i)
             half = sum(mids[:8])
             with ops.want_fp8_copy():  # fp8 convolutions on: layer 1's BatchNorm + SiLU pass also writes the fp8 copy layer 2 reads
                 z1 = ops.FusedConvBNActFn.apply(x[i], s1, 1, (half, sum(mids)), *s1.params())
             offs = [sum(mids[:j]) for j in range(16)]
+            if self.distill:
+                # feature distillation (loss.DistillFn): its gradient reaches z1 as compact rows added to layer 2's data gradient
+                slot = {"ptr": z1.data_ptr(), "offs": (offs[pos[6]], offs[pos[14]]), "C": (mids[pos[6]], mids[pos[14]])}
+                z1 = ops.InjectRowsFn.apply(z1, slot)
+                self._slots.append(slot)
             if s2 is not None and mids[0] % 64 == 0 and getattr(self, "fuse_bn_proj", True):
                 # grouped conv + BatchNorm statistics + projections with BatchNorm/SiLU applied on the fly (no activation tensor)
                 out = ops.FusedConvBNProjFn.apply(z1, s2, len(branches), offs, mids, 16, *s2.params(), *[b[2].weight for b in branches],
@@ -724,6 +731,9 @@ class v10Detect3d(nn.Module):
         out = {"one2many": one2many, "one2one": one2one, "o2m_embs": o2m_embs, "o2o_embs": o2o_embs, "depth_maps": torch.empty(1)}
         if fused:
             out["_y3d_maps"] = self.__dict__.pop("_maps")  # private extra next to the reference's keys (head.py:833)
+            slots = self.__dict__.pop("_slots")
+            if slots:
+                out["_y3d_distill"] = slots
         return out
 
     # head.py:847-871 as data: per number of levels, the depth bias of each level and the uniform range of its depth projection

@@ -1111,6 +1111,38 @@ class SplitChannelsFn(torch.autograd.Function):
         return dx, None, None
 
 
+class InjectRowsFn(torch.autograd.Function):
+    """Identity on the first head layer's output `z` ahead of the second layer, for feature distillation (loss.DistillFn): the
+    distillation gradient is non-zero at the foreground anchors of two channel slices of `z` only.  Through autograd's slice backward
+    it would be a zero-filled tensor of z's size plus a full-size add (S-3D, level 0, batch 32: 839 MB each way).  Instead the loss
+    leaves its compact rows in `slot["entries"]`, its backward - which runs earlier in the same pass: the head maps it is tied to are
+    made from this function's output - leaves the scale, and the backward here adds scale * rows into the gradient the second layer
+    has just produced (csrc/distill.hip, y3d_distill_scatter: one wave per row) and hands that same tensor on.
+    The add is IN PLACE on the gradient this backward is handed.  That assumes nobody else holds that tensor: z1's only consumer is
+    layer 2 (or the channel split in front of it), whose backward makes a fresh tensor, and no `retain_grad` / tensor hook sits on
+    this function's output.  A second consumer of the output would make autograd sum into a new tensor first, which is also fine."""
+
+    @staticmethod
+    def forward(ctx, z, slot):
+        ctx.slot = slot
+        return z.view_as(z)
+
+    @staticmethod
+    def backward(ctx, g):
+        entries = ctx.slot.pop("entries", ())
+        live = [e for e in entries if e["scale"] is not None]
+        if g is None or not live:
+            return g, None
+        dt = live[0]["rows"].dtype
+        g = to_nhwc(g, dt)
+        sb, sh, sw = s3(g)
+        B, _, H, W = g.shape
+        for e in live:
+            lib().distill_scatter(code(dt), e["rows"].data_ptr(), e["idx"].data_ptr(), e["nrows"].data_ptr(), e["scale"].data_ptr(), e["cap"],
+                                  e["C"], g.data_ptr() + e["off"] * g.element_size(), sb, sh, sw, e["a0"], H, W, stream())
+        return g, None
+
+
 class C2fSplitFn(torch.autograd.Function):
     """`y = list(cv1(x).chunk(2, 1))` of C2f (reference block.py:233) with the second half handed out TWICE (it feeds the first block and
     the concat): -> (y0, y1 for the concat, y1 for the block), all views.  Plain chunk + reuse makes autograd (a) add the two
