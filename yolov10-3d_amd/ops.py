@@ -8,6 +8,7 @@ dtype (bf16 by default, fp32 for the parity mode).
 from __future__ import annotations
 
 import os
+from collections import namedtuple
 
 import torch
 
@@ -259,40 +260,75 @@ def bump_weight_epoch():
     bump_param_epoch()
 
 
-class _PackRegistry:
+class _WeightRegistry:
+    """what the registries of per-weight device copies below share: the hipGraph lifetime rules, and when an entry is refreshed or dropped
+    (nobody looked it up for KEEP epochs: re-pointed / freed parameters)"""
+
+    KEEP = 4
+
+    def __init__(self):
+        self.entries, self.epoch, self.tables = {}, None, None
+        # A hipGraph capture (graph.GraphedTrainStep) bakes in the ADDRESSES of the descriptor tables and of the buffers it looked up:
+        # both must outlive the graph.  Tables used while capturing are kept here for good (a later multi-tensor launch with more entries
+        # - a second model in the process - builds new tables and would otherwise free the ones the graph's launch still reads: it then
+        # follows whatever "pointers" the reused memory holds), entries looked up while capturing are never evicted.
+        self.captured_tables = []
+
+    def _hold_tables(self):
+        """before a launch that reads self.tables"""
+        if torch.cuda.is_current_stream_capturing() and not any(t is self.tables for t in self.captured_tables):
+            self.captured_tables.append(self.tables)
+
+    def _revisit(self, e, now, ver, refresh_all):
+        """the bookkeeping of a lookup that found entry `e`.  `now`: the epoch its copy has to be of; `refresh_all()`: the registry's
+        multi-tensor launch, returning the entries it covered.  -> True when `e` was changed through torch since its copy was made
+        (load_state_dict, init, broadcast, torch.optim): the caller refreshes it on its own."""
+        e["seen"] = WEIGHT_EPOCH
+        capturing = torch.cuda.is_current_stream_capturing()
+        if capturing:
+            e["pinned"] = True
+        if self.epoch != now:
+            self.epoch = now
+            # (not while a hipGraph is being captured: dropping entries changes the table key, and rebuilding the descriptor tables is a
+            # host-to-device copy, which a capture does not allow - entries of a model that is gone wait for the next eager step)
+            stale = [] if capturing else [k for k, v in self.entries.items() if WEIGHT_EPOCH - v["seen"] > self.KEEP and not v.get("pinned")]
+            for k in stale:
+                del self.entries[k]
+            for v in refresh_all():
+                v["ver"] = None  # refreshed from memory: whatever version the tensor has now is the copied one
+        changed = e["ver"] is not None and e["ver"] != ver
+        e["ver"] = ver
+        return changed
+
+
+class _PackRegistry(_WeightRegistry):
     """Packed compute-dtype copies of the conv weights for the training step, refreshed by ONE multi-tensor launch per step
     (`y3d_mt_pack_weights`) instead of one tiny launch per conv and direction (S-3D: 113 launches of ~5 us + their gaps).
 
     A weight is identified by (address, geometry); its packed buffer is persistent.  The first lookup after the weights changed
-    (WEIGHT_EPOCH moved: the fused optimizer wrote them) repacks every registered weight from whatever its address holds now;
-    a weight changed through torch (in-place op: its `_version` moved) is repacked on its own; an unknown weight is packed on its
-    own and registered.  Entries that nobody looked up for a few epochs are dropped (re-pointed / freed parameters)."""
+    (WEIGHT_EPOCH moved: the fused optimizer wrote them) repacks every registered weight of that dtype from whatever its address holds
+    now; a weight changed through torch (in-place op: its `_version` moved) is repacked on its own; an unknown weight is packed on its
+    own and registered."""
 
     CHUNK = 16384
-    KEEP = 4
 
     def __init__(self, mode):
-        self.mode, self.entries, self.epoch, self.tables = mode, {}, None, None
-        # A hipGraph capture (graph.GraphedTrainStep) bakes in the ADDRESSES of the descriptor tables and of the packed buffers it looked
-        # up: both must outlive the graph.  Tables used while capturing are kept here for good (a later `_pack_all` with more entries -
-        # a second model in the process - builds new tables and would otherwise free the ones the graph's launch still reads: it then
-        # follows whatever "pointers" the reused memory holds), entries looked up while capturing are never evicted.
-        self.captured_tables = []
+        super().__init__()
+        self.mode = mode
 
     def _pack_one(self, e):
         L, st = lib(), stream()
         a, b, c, taps, kpad, dt = e["geo"]
+        k = int(round(taps ** 0.5))
         if self.mode == 0:
-            k = int(round(taps ** 0.5))
             L.pack_weight_fwd(dt, e["src"], e["dst"].data_ptr(), a, b, c, k, k, st)
         else:
-            k = int(round(taps ** 0.5))
             L.pack_weight_dgrad(dt, e["src"], e["dst"].data_ptr(), a * b, c, a, k, k, st)
 
     def _pack_all(self, dt):
         ents = [e for e in self.entries.values() if e["geo"][5] == dt]
         if not ents:
-            return
+            return ents
         dev = ents[0]["dst"].device
         key = tuple(id(e) for e in ents)
         if self.tables is None or self.tables[0] != (key, dt):
@@ -307,9 +343,9 @@ class _PackRegistry:
             self.tables = ((key, dt), torch.tensor(desc, dtype=torch.int64, device=dev), torch.tensor(ct, dtype=torch.int32, device=dev),
                            torch.tensor(co, dtype=torch.int32, device=dev), len(ct))
         _, desc, ct, co, n = self.tables
-        if torch.cuda.is_current_stream_capturing() and not any(t is self.tables for t in self.captured_tables):
-            self.captured_tables.append(self.tables)
+        self._hold_tables()
         lib().mt_pack_weights(dt, desc.data_ptr(), ct.data_ptr(), co.data_ptr(), n, self.CHUNK, stream())
+        return ents
 
     def lookup(self, w32, src_ptr, geo, dtype, ver=None):
         """geo = (a, b, c, taps, Kpad, dt) as y3d_mt_pack_weights; src_ptr: address of the (sub)tensor to pack -> packed tensor.
@@ -319,7 +355,6 @@ class _PackRegistry:
         key = (src_ptr, geo)
         ver = w32._version if ver is None else ver
         e = self.entries.get(key)
-        now = (WEIGHT_EPOCH, geo[5])
         if e is None:
             a, b, c, taps, kpad, dt = geo
             n = a * kpad if self.mode == 0 else a * c * kpad
@@ -328,31 +363,12 @@ class _PackRegistry:
                  "keep": w32}
             self.entries[key] = e
             self._pack_one(e)
-            return e["dst"]
-        e["seen"] = WEIGHT_EPOCH
-        capturing = torch.cuda.is_current_stream_capturing()
-        if capturing:
-            e["pinned"] = True
-        if self.epoch != now:
-            self.epoch = now
-            # (not while a hipGraph is being captured: dropping entries changes the table key, and rebuilding the descriptor tables is a
-            # host-to-device copy, which a capture does not allow - entries of a model that is gone wait for the next eager step)
-            stale = [] if capturing else [k for k, v in self.entries.items() if WEIGHT_EPOCH - v["seen"] > self.KEEP and not v.get("pinned")]
-            for k in stale:
-                del self.entries[k]
-            self._pack_all(geo[5])
-            for v in self.entries.values():
-                if v["geo"][5] == geo[5]:
-                    v["ver"] = None  # refreshed from memory: whatever version the tensor has now is the packed one
-        if e["ver"] is None:
-            e["ver"] = ver
-        elif e["ver"] != ver:  # changed through torch since it was packed (load_state_dict, init, broadcast, torch.optim)
-            e["ver"] = ver
+        elif self._revisit(e, (WEIGHT_EPOCH, geo[5]), ver, lambda: self._pack_all(geo[5])):
             self._pack_one(e)
         return e["dst"]
 
 
-class _QuantRegistry:
+class _QuantRegistry(_WeightRegistry):
     """fp8 (e4m3fn, per-output-channel power-of-two scale) shadows of the conv weights — the `fp8w` weight mode (csrc/fp8w.hip).
 
     For every registered fp32 master weight (identified by address + shape) it keeps `w_eff` (fp32, what the kernels pack and
@@ -360,10 +376,6 @@ class _QuantRegistry:
     launch the first time a weight is looked up after the fused optimizer moved the weight epoch; a weight changed through torch
     (its version token moved) is refreshed on its own.  `lookup` returns (w_eff, token): the token stands in for the master's
     version in the pack registries' and the eval caches' keys (the shadow's own counter never moves)."""
-
-    def __init__(self):
-        self.entries, self.epoch, self.tables = {}, None, None
-        self.captured_tables = []  # as _PackRegistry: tables a hipGraph capture has baked in stay alive
 
     def _run(self, ents):
         dev = ents[0]["weff"].device
@@ -377,45 +389,31 @@ class _QuantRegistry:
                 r += rows
             self.tables = (key, torch.tensor(desc, dtype=torch.int64, device=dev), torch.tensor(rb, dtype=torch.int32, device=dev), len(ents), r)
         _, desc, rb, nt, nrows = self.tables
-        if torch.cuda.is_current_stream_capturing() and not any(t is self.tables for t in self.captured_tables):
-            self.captured_tables.append(self.tables)
+        self._hold_tables()
         lib().mt_fp8w_quantize(desc.data_ptr(), rb.data_ptr(), nt, nrows, stream())
+        return ents
+
+    def _run_one(self, e):
+        tb, self.tables = self.tables, None  # a table of its own: the one over all entries stays for the next epoch
+        self._run([e])
+        self.tables = tb
 
     def lookup(self, w32, ver=None):
         ver = w32._version if ver is None else ver
         rows, K = w32.shape[0], w32[0].numel()
         key = (w32.data_ptr(), rows, K)
         e = self.entries.get(key)
-        self.last = e  # (the entry of the weight just looked up: the fp8 MFMA path packs its codes, fp8_weight)
         if e is None:
             dev = w32.device
             e = {"src": w32.data_ptr(), "shape": (rows, K), "keep": w32, "weff": torch.empty(w32.shape, dtype=torch.float32, device=dev),
                  "codes": torch.empty((rows, K), dtype=torch.uint8, device=dev), "scale": torch.empty(rows, dtype=torch.float32, device=dev),
                  "ver": ver, "count": 0, "seen": WEIGHT_EPOCH}
             self.entries[key] = e
-            self.last = e
-            tb, self.tables = self.tables, None
-            self._run([e])
-            self.tables = tb
-            return e["weff"], (WEIGHT_EPOCH, e["count"])
-        e["seen"] = WEIGHT_EPOCH
-        if torch.cuda.is_current_stream_capturing():
-            e["pinned"] = True
-        if self.epoch != WEIGHT_EPOCH:
-            self.epoch = WEIGHT_EPOCH
-            if not torch.cuda.is_current_stream_capturing():  # as _PackRegistry.lookup
-                for k in [k for k, v in self.entries.items() if WEIGHT_EPOCH - v["seen"] > _PackRegistry.KEEP and not v.get("pinned")]:
-                    del self.entries[k]
-            self._run(list(self.entries.values()))
-            for v in self.entries.values():
-                v["ver"] = None
-        if e["ver"] is None:
-            e["ver"] = ver
-        elif e["ver"] != ver:  # the master was written through torch since the shadow was made
-            e["ver"], e["count"] = ver, e["count"] + 1
-            tb, self.tables = self.tables, None
-            self._run([e])
-            self.tables = tb
+            self._run_one(e)
+        elif self._revisit(e, WEIGHT_EPOCH, ver, lambda: self._run(list(self.entries.values()))):
+            e["count"] += 1  # the master was written through torch since the shadow was made
+            self._run_one(e)
+        self.last = e  # (the entry of the weight just looked up: the fp8 MFMA path packs its codes, fp8_weight)
         return e["weff"], (WEIGHT_EPOCH, e["count"])
 
 
@@ -538,13 +536,6 @@ def fp8_weight_dgrad(ent, Cin, g, lo, hi):
     return hit[1], hit[2]
 
 
-def _fp8_dgrad_entry(cfg):
-    """the _QuantRegistry entry whose codes the fp8 data gradient of this layer multiplies, or None: the switch is on, the layer's forward
-    took the fp8 kernel (cfg[18]) and the entry still holds the weight version that forward packed (cfg[17])"""
-    if not (FP8_DGRAD and FP8_CONV and len(cfg) > 18 and isinstance(cfg[18], dict)):
-        return None
-    ent = cfg[18]
-    return ent if cfg[17] == ((WEIGHT_EPOCH, ent["count"]),) else None
 PROJ_BN_MFMA = True  # BatchNorm backward of the second head layer recomputing dz on MFMA (tests flip it: materialised path)
 STEM_FUSED = True  # the stem in one pass (tests flip it: im2col + dense conv)
 PACK_CACHE = True  # weight packs through the registry (one multi-tensor launch per step)
@@ -562,7 +553,14 @@ def conv_bn_act_eval(x, w, gamma, beta, rm, rv, k, s, p, g, act, eps, cache=None
     return z
 
 
-_IDENT = {}
+_IDENT = {}  # (channels, device) -> (ones, zeros): gamma / running variance and beta / running mean of an identity BatchNorm
+
+
+def _identity_bn(C, device):
+    ident = _IDENT.get((C, device))
+    if ident is None:
+        ident = _IDENT[(C, device)] = (torch.ones(C, dtype=torch.float32, device=device), torch.zeros(C, dtype=torch.float32, device=device))
+    return ident
 
 
 def conv_bias_act_eval(x, w, bias, k, s, p, g, act, res, res_mode, cache):
@@ -570,14 +568,17 @@ def conv_bias_act_eval(x, w, bias, k, s, p, g, act, res, res_mode, cache):
     sequence with an IDENTITY BatchNorm - gamma 1, running mean 0, running variance 1, eps 0: scale exactly 1, shift exactly the bias -
     so the folded model goes through the same kernels (affine conv epilogue, residual forms) as the unfolded eval path."""
     _require_gpu(x)
-    C = w.shape[0]
-    ident = _IDENT.get((str(w.device), C))
-    if ident is None:
-        ident = _IDENT[(str(w.device), C)] = (torch.ones(C, dtype=torch.float32, device=w.device), torch.zeros(C, dtype=torch.float32, device=w.device))
-    ones, zeros = ident
+    ones, zeros = _identity_bn(w.shape[0], w.device)
     with torch.no_grad():
         z, _, _ = _cba_forward(x, _w32(w), ones, bias.detach().float(), zeros, ones, k, s, p, g, act, res, res_mode, False, 0.0, 0.0, cache)
     return z
+
+
+def _cache_put(cache, key, value):
+    """insert into an eval cache (keys carry PARAM_EPOCH at [1]), dropping what older epochs left behind"""
+    for old in [q for q in cache if q[1] != PARAM_EPOCH]:
+        del cache[old]
+    cache[key] = value
 
 
 def _eval_consts(cache, kind, w32, g32, b32, rm, rv, ver, dtype, k, g, Cin_g, Cg_pad, Cout, eps):
@@ -599,9 +600,7 @@ def _eval_consts(cache, kind, w32, g32, b32, rm, rv, ver, dtype, k, g, Cin_g, Cg
         L.bn_eval_scale(Cout, g32.data_ptr(), b32.data_ptr(), rm.data_ptr(), rv.data_ptr(), eps, ss[0].data_ptr(), ss[1].data_ptr(), st)
         hit = (wp, ss, w32)  # w32 kept alive: its address is part of the key
         if cache is not None:  # owned by the module / stack, so it dies with the tensors it describes
-            for old in [q for q in cache if q[1] != PARAM_EPOCH]:
-                del cache[old]
-            cache[key] = hit
+            _cache_put(cache, key, hit)
     return hit[0], hit[1]
 
 
@@ -612,199 +611,231 @@ def _timed(key, launch):
         launch()
 
 
-def _cba_forward(x, w32, g32, b32, rm, rv, k, s, p, g, act, res, res_mode, training, eps, momentum, cache=None, bn_apply=True, pack_cache=True,
-                 ver=None, quant=True, pre_conv=None):
-    """conv -> BN statistics -> BN apply + SiLU (+res).  Returns (z, saved) with everything the backward needs.
+# What the forward of one conv + BatchNorm + activation decided and its backward needs.  Cin_k: input channels as the kernels see them (Cin
+# padded to whole 16-byte chunks); wver: version token of the weights as packed (stacked views / fp8 shadows carry their identity outside
+# the tensor's own counter); fp8_entry: the quantiser entry whose codes the fp8 MFMA forward multiplied (None on every other path: the
+# fp8 data gradient follows it); stem: the conv ran as a K = 32 GEMM over im2col rows of the image (dW is mapped back, no dx).
+ConvPlan = namedtuple("ConvPlan", "B Cin Cin_k H W Cout Ho Wo k s p g dw res_mode training dtype act wver fp8_entry stem", defaults=(False,))
+
+
+def _cba_forward(x, w32, g32, b32, rm, rv, k, s, p, g, act, res, res_mode, training, eps, momentum, cache=None, bn_apply=True, ver=None):
+    """conv -> BN statistics -> BN apply + SiLU (+res).  Returns (z, plan, saved) with everything the backward needs.
     ver = (weights token, all-tensors token) of a stacked view (StackedConvs), None for tensors that carry their own counters."""
-    L = lib()
     _require_gpu(x)
     dtype = _COMPUTE_DTYPE
-    dt, c = code(dtype), ce(dtype)
-    st = stream()
-    dev = x.device
     B, Cin, H, W = x.shape
+    dw = g > 1 and g == Cin and g == w32.shape[0]
     qent = None
-    if WEIGHT_QUANT and quant and not (g > 1 and g == Cin and g == w32.shape[0]):
+    if WEIGHT_QUANT and not dw:
         # fp8w mode: the kernels pack and multiply the fp8-valued shadow of the weight; the master keeps receiving the gradient
         w32, qtok = QUANT.lookup(w32, ver[0] if ver is not None else None)
         qent = QUANT.last
         ver = ((qtok,), (qtok,) + (ver[1] if ver is not None else (g32._version, b32._version, rm._version, rv._version)))
     Cout, Cg_w, kh, kw = w32.shape
     assert kh == k and kw == k and Cin // g == Cg_w, "Conv: weight shape does not match input"
-    Ho = (H + 2 * p - k) // s + 1
-    Wo = (W + 2 * p - k) // s + 1
-    M = B * Ho * Wo
     if Cin == 3 and k == 3 and s == 2 and p == 1 and g == 1 and not x.requires_grad:
-        # the stem: im2col the image once (27 window values + 5 zeros per output pixel) and run a dense 1x1 conv with K = 32;
-        # as a 9-tap conv over an 8-channel-padded image the MFMA tiles were 86 % padding.  dW is mapped back in _cba_backward.
-        wkey = ("stemcol", PARAM_EPOCH, w32.data_ptr(), ver[0] if ver is not None else w32._version)
-        wcol = cache.get(wkey) if (cache is not None and not training) else None
-        if wcol is None:
-            wcol = torch.zeros(Cout, 32, dtype=torch.float32, device=dev)
-            wcol[:, :27] = w32.detach().permute(0, 2, 3, 1).reshape(Cout, 27)  # column (r*3+q)*3+ci
-            if cache is not None and not training:  # eval: the im2col form of the stem weight is a constant of the forward
-                for old in [q for q in cache if q[1] != PARAM_EPOCH]:
-                    del cache[old]
-                cache[wkey] = wcol
-        if (not training and not res_mode and dtype == torch.bfloat16 and Cout % 16 == 0 and 16 <= Cout <= 80 and STEM_FUSED
-                and x.dtype in (torch.uint8, torch.float32)):
-            # eval: gather + MFMA + folded BatchNorm + SiLU in one pass over the image (csrc/stem_fused.hip); no column tensor
-            _, ss = _eval_consts(cache, "dense", wcol.view(Cout, 32, 1, 1), g32, b32, rm, rv, ver, dtype, 1, 1, 32, 32, Cout, eps)
-            if x.dtype == torch.uint8:
-                hwc = int(not x.is_contiguous() and x.permute(0, 2, 3, 1).is_contiguous())
-                xs, mode = (x if (hwc or x.is_contiguous()) else x.contiguous()), 1 + hwc
-            else:
-                xs, mode = x.contiguous(), 0
-            ye = out_tensor(B, Cout, Ho, Wo, dtype, dev)
-            _timed(("conv_eval", dt, B, H, W, 3, Cout, 3, 2, 1, 1),
-                   lambda: L.stem_conv_eval(xs.data_ptr(), mode, wcol.data_ptr(), ss[0].data_ptr(), ss[1].data_ptr(), int(act), ye.data_ptr(), ye.stride(3),
-                                            B, H, W, Cout, st))
-            return ye, None, None
-        xcol = nhwc_empty(B, 32, Ho, Wo, dtype, dev)
-        if training and dtype == torch.bfloat16 and Cout % 16 == 0 and 16 <= Cout <= 80 and STEM_FUSED and x.dtype in (torch.uint8, torch.float32):
-            # training: the same one-pass kernel writes the raw conv output, the BatchNorm partials and - its own B operand - the column
-            # tensor the weight gradient reads; the two-step form wrote the column tensor and read it back (im2col 167 us + conv 146 us)
-            if x.dtype == torch.uint8:
-                hwc = int(not x.is_contiguous() and x.permute(0, 2, 3, 1).is_contiguous())
-                xs, mode = (x if (hwc or x.is_contiguous()) else x.contiguous()), 1 + hwc
-            else:
-                xs, mode = x.contiguous(), 0
-            rows = L.stem_conv_train_rows(B, H, W)
-            ypre = nhwc_empty(B, Cout, Ho, Wo, dtype, dev)
-            part = _f32(rows * Cout * 2, dev)
-            _timed(("conv_fwd", dt, B, H, W, 3, Cout, 3, 2, 1),
-                   lambda: L.stem_conv_train(xs.data_ptr(), mode, wcol.data_ptr(), ypre.data_ptr(), ypre.stride(3), xcol.data_ptr(), part.data_ptr(), B, H, W, Cout, st))
-            z, cfg, saved = _cba_forward(xcol, wcol.view(Cout, 32, 1, 1), g32, b32, rm, rv, 1, 1, 0, 1, act, res, res_mode, training, eps, momentum, cache,
-                                         pack_cache=False, quant=False, pre_conv=(ypre, part, rows))
-            return z, (cfg + ("stem",) if cfg is not None else None), saved
-        if x.dtype == torch.uint8:  # the dataset's bytes: /255 happens in the kernel (NCHW, or NHWC when the tensor is channels-last)
-            hwc = int(not x.is_contiguous() and x.permute(0, 2, 3, 1).is_contiguous())
-            xs = x if (hwc or x.is_contiguous()) else x.contiguous()
-            L.stem_im2col_u8(dt, xs.data_ptr(), hwc, xcol.data_ptr(), B, H, W, Ho, Wo, st)
-        else:
-            L.stem_im2col(dt, x.float().contiguous().data_ptr(), xcol.data_ptr(), B, H, W, Ho, Wo, st)
-        z, cfg, saved = _cba_forward(xcol, wcol.view(Cout, 32, 1, 1), g32, b32, rm, rv, 1, 1, 0, 1, act, res, res_mode, training, eps, momentum, cache,
-                                     pack_cache=False, quant=False)  # wcol is built from the already quantised stem weight
-        return z, (cfg + ("stem",) if cfg is not None else None), saved
-    dw = g > 1 and g == Cin and g == Cout
-    f8 = False
-    # ---- input: NHWC compute dtype; the stem (Cin=3) is channel-padded while converting from NCHW fp32
-    Cin_k = Cin
+        return _stem_forward(x, w32, g32, b32, rm, rv, act, res, res_mode, training, eps, momentum, cache, ver)
+    # ---- input: NHWC compute dtype; a channel count that is no whole number of 16-byte chunks is padded while converting from NCHW fp32
+    c = ce(dtype)
     if Cin % c != 0:
         if g != 1:
             raise Y3DError(f"grouped conv with {Cin} channels is not 16-byte chunkable")
         Cin_k = (Cin + c - 1) // c * c
-        xin = nhwc_empty(B, Cin_k, H, W, dtype, dev)
-        L.nchw_to_nhwc(dt, x.float().contiguous().data_ptr(), xin.data_ptr(), B, Cin, H, W, Cin_k, st)
+        xin = nhwc_empty(B, Cin_k, H, W, dtype, x.device)
+        lib().nchw_to_nhwc(code(dtype), x.float().contiguous().data_ptr(), xin.data_ptr(), B, Cin, H, W, Cin_k, stream())
     else:
         xin = to_nhwc(x, dtype)
-    sb, sh, sw = s3(xin)
-    dw_fused = dw and not training and bn_apply and DW_EVAL_FUSED
-    y = nhwc_empty(B, Cout, Ho, Wo, dtype, dev) if ((dw or training or res_mode) and not dw_fused) else None  # pre-BatchNorm tensor (the eval fast paths have none)
-    part = None
     if dw:
-        if Cout % c != 0:
-            raise Y3DError(f"depth-wise conv with {Cout} channels is not 16-byte chunkable")
-        nblk = L.dw_blocks(M)
-        if training:
-            part = _f32(nblk * Cout * 2, dev)
-        ss_eval = None
-        if training:
-            wp = _f32(k * k * Cout, dev)
-            L.dw_pack_weight(w32.data_ptr(), wp.data_ptr(), Cout, k, k, st)
-        else:
-            wp, ss_eval = _eval_consts(cache, "dw", w32, g32, b32, rm, rv, ver, dtype, k, g, 1, 1, Cout, eps)
-            if dw_fused:
-                # eval: folded BatchNorm + SiLU (+ the RepVGGDW / shortcut residual) in the depth-wise kernel's epilogue - one launch, no
-                # pre-BN tensor (12 depth-wise layers of S-3D: 12 bn_act_fwd launches and their read + write less per forward)
-                ze = out_tensor(B, Cout, Ho, Wo, dtype, dev)
-                rr = to_nhwc(res, dtype, dense=True) if res_mode else None
-                if rr is not None:
-                    assert rr.shape == ze.shape, "residual shape mismatch"
-                L.dwconv2d_fwd_affine(dt, xin.data_ptr(), sb, sh, sw, B, H, W, Cin, wp.data_ptr(), ss_eval[0].data_ptr(), ss_eval[1].data_ptr(), int(act),
-                                      res_mode, rr.data_ptr() if rr is not None else None, rr.stride(3) if rr is not None else 0,
-                                      ze.data_ptr(), ze.stride(3), Ho, Wo, k, k, s, p, st)
-                return ze, None, None
-        L.dwconv2d_fwd(dt, xin.data_ptr(), sb, sh, sw, B, H, W, Cin, wp.data_ptr(), y.data_ptr(), Cout, Ho, Wo, k, k, s, p,
-                       part.data_ptr() if training else None, st)
-    elif pre_conv is not None:  # the caller has run the conv (fused training stem): pre-BN tensor + BatchNorm partial rows
-        y, part, nblk = pre_conv
+        return _dw_forward(xin, w32, g32, b32, rm, rv, k, s, p, act, res, res_mode, training, eps, momentum, cache, bn_apply, ver)
+    return _dense_forward(xin, w32, g32, b32, rm, rv, Cin, k, s, p, g, act, res, res_mode, training, eps, momentum, cache, bn_apply, ver, qent, True)
+
+
+def _stem_image(x):
+    """-> (tensor, hwc): uint8 (the dataset's bytes: /255 happens in the kernel) NCHW, or NHWC (hwc = 1) when channels-last; else NCHW fp32"""
+    if x.dtype == torch.uint8:
+        hwc = int(not x.is_contiguous() and x.permute(0, 2, 3, 1).is_contiguous())
+        return (x if (hwc or x.is_contiguous()) else x.contiguous()), hwc
+    return x.float().contiguous(), 0
+
+
+def _stem_forward(x, w32, g32, b32, rm, rv, act, res, res_mode, training, eps, momentum, cache, ver):
+    """the stem (3 -> Cout, 3x3, stride 2) as a dense 1x1 conv with K = 32 over the im2col rows of the image (27 window values + 5 zeros
+    per output pixel); as a 9-tap conv over an 8-channel-padded image the MFMA tiles were 86 % padding.  dW is mapped back in _conv_backward."""
+    L, st, dtype, dev = lib(), stream(), _COMPUTE_DTYPE, x.device
+    dt = code(dtype)
+    B, _, H, W = x.shape
+    Cout = w32.shape[0]
+    Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    wkey = ("stemcol", PARAM_EPOCH, w32.data_ptr(), ver[0] if ver is not None else w32._version)
+    wcol = cache.get(wkey) if (cache is not None and not training) else None
+    if wcol is None:
+        wcol = torch.zeros(Cout, 32, dtype=torch.float32, device=dev)
+        wcol[:, :27] = w32.detach().permute(0, 2, 3, 1).reshape(Cout, 27)  # column (r*3+q)*3+ci
+        if cache is not None and not training:  # eval: the im2col form of the stem weight is a constant of the forward
+            _cache_put(cache, wkey, wcol)
+    w1x1 = wcol.view(Cout, 32, 1, 1)
+    fused = dtype == torch.bfloat16 and Cout % 16 == 0 and 16 <= Cout <= 80 and STEM_FUSED and x.dtype in (torch.uint8, torch.float32)
+    if fused and not training and not res_mode:
+        # eval: gather + MFMA + folded BatchNorm + SiLU in one pass over the image (csrc/stem_fused.hip); no column tensor
+        _, ss = _eval_consts(cache, "dense", w1x1, g32, b32, rm, rv, ver, dtype, 1, 1, 32, 32, Cout, eps)
+        xs, hwc = _stem_image(x)
+        mode = 1 + hwc if xs.dtype == torch.uint8 else 0
+        ye = out_tensor(B, Cout, Ho, Wo, dtype, dev)
+        _timed(("conv_eval", dt, B, H, W, 3, Cout, 3, 2, 1, 1),
+               lambda: L.stem_conv_eval(xs.data_ptr(), mode, wcol.data_ptr(), ss[0].data_ptr(), ss[1].data_ptr(), int(act), ye.data_ptr(), ye.stride(3),
+                                        B, H, W, Cout, st))
+        return ye, None, None
+    xcol = nhwc_empty(B, 32, Ho, Wo, dtype, dev)
+    xs, hwc = _stem_image(x)
+    if fused and training:
+        # training: the same one-pass kernel writes the raw conv output, the BatchNorm partials and - its own B operand - the column
+        # tensor the weight gradient reads; the two-step form wrote the column tensor and read it back (im2col 167 us + conv 146 us)
+        mode = 1 + hwc if xs.dtype == torch.uint8 else 0
+        rows = L.stem_conv_train_rows(B, H, W)
+        ypre = nhwc_empty(B, Cout, Ho, Wo, dtype, dev)
+        part = _f32(rows * Cout * 2, dev)
+        _timed(("conv_fwd", dt, B, H, W, 3, Cout, 3, 2, 1),
+               lambda: L.stem_conv_train(xs.data_ptr(), mode, wcol.data_ptr(), ypre.data_ptr(), ypre.stride(3), xcol.data_ptr(), part.data_ptr(), B, H, W, Cout, st))
+        z, plan, saved = _bn_act_tail(xcol, w1x1, ypre, part, rows, None, g32, b32, rm, rv, 32, 1, 1, 0, 1, act, res, res_mode, training, eps, momentum,
+                                      True, None, None)
     else:
-        # fp8 MFMA forward (set_fp8_conv): e4m3 codes of the weight x the MX-quantised activation; everything after the conv - BatchNorm
-        # statistics from the partial rows, the apply pass, the bf16 backward over (xin, w_eff) - is the bf16 path's
-        f8 = (FP8_CONV and qent is not None and dtype == torch.bfloat16 and k == 3 and s == 1 and p == 1 and Cin_k == Cin
-              and bool(L.conv3x3_fp8_ok(B, H, W, Cin, Cout, g)))
-        nblk = L.conv3x3_fp8_stat_rows(B, H, W) if f8 else L.conv2d_stat_rows(dt, B, H, W, Cin_k, Cout, g, k, k, s, p)
-        if training:
-            part = _f32(nblk * Cout * 2, dev)
-        Cg_pad = Cin_k // g
-        ss_eval = None
-        if not training:
-            wp, ss_eval = _eval_consts(cache, "dense", w32, g32, b32, rm, rv, ver, dtype, k, g, Cin // g, Cg_pad, Cout, eps)
-        if f8:
-            xq, xs = fp8_input(xin)
-            wq, ws = fp8_weight(qent, Cin // g)
-            if not training and not res_mode:
-                ye = out_tensor(B, Cout, Ho, Wo, dtype, dev)
-                _timed(("conv_eval_fp8", dt, B, H, W, Cin_k, Cout, k, s, g, p),
-                       lambda: L.conv3x3_fp8_fwd(xq.data_ptr(), xs.data_ptr(), B, H, W, Cin, wq.data_ptr(), ws.data_ptr(), ye.data_ptr(), ye.stride(3), Cout, g, None,
-                                                 ss_eval[0].data_ptr(), ss_eval[1].data_ptr(), int(act), st))
-                return ye, None, None
-            _timed(("conv_fwd_fp8", dt, B, H, W, Cin_k, Cout, k, s, g),
-                   lambda: L.conv3x3_fp8_fwd(xq.data_ptr(), xs.data_ptr(), B, H, W, Cin, wq.data_ptr(), ws.data_ptr(), y.data_ptr(), y.stride(3), Cout, g,
-                                             part.data_ptr() if training else None, None, None, 0, st))
-        elif not training and not res_mode:
-            # eval: BatchNorm (running statistics) + SiLU folded into the conv epilogue - one launch, no pre-BN tensor; the packed
-            # weights and the scale/shift pair are cached until a parameter / buffer is modified in place or re-pointed
-            ye = out_tensor(B, Cout, Ho, Wo, dtype, dev)  # a pending placement (C2f / SPPF / Concat slot) is honoured in eval too
-            _timed(("conv_eval", dt, B, H, W, Cin_k, Cout, k, s, g, p),
-                   lambda: L.conv2d_fwd_affine(dt, xin.data_ptr(), sb, sh, sw, B, H, W, Cin_k, wp.data_ptr(), ss_eval[0].data_ptr(), ss_eval[1].data_ptr(),
-                                               int(act), ye.data_ptr(), ye.stride(3), Ho, Wo, Cout, g, k, k, s, p, st))
-            return ye, None, None
-        if f8:
-            pass
-        elif (not training and res_mode == 1 and dtype == torch.bfloat16
-                and L.conv2d_fwd_affine_res_ok(dt, B, H, W, Cin_k, Cout, g, k, k, s, p)):
-            # eval Bottleneck shortcut: conv + folded BatchNorm + SiLU + residual in ONE launch (the narrow resident-weight kernel)
-            rr = to_nhwc(res, dtype, dense=True)
-            ye = out_tensor(B, Cout, Ho, Wo, dtype, dev)
-            L.conv2d_fwd_affine_res(dt, xin.data_ptr(), sb, sh, sw, B, H, W, Cin_k, wp.data_ptr(), ss_eval[0].data_ptr(), ss_eval[1].data_ptr(), int(act),
-                                    rr.data_ptr(), rr.stride(3), ye.data_ptr(), ye.stride(3), Ho, Wo, Cout, g, k, k, s, p, st)
-            return ye, None, None
-        if f8:
-            pass  # the conv ran above
-        elif not training:
-            pass  # eval with a residual: conv (cached packed weights) + one BatchNorm / SiLU / residual pass below
-        elif pack_cache and training and PACK_CACHE:
-            wp = PACK_FWD.lookup(w32, w32.data_ptr(), (Cout, Cin // g, Cg_pad, k * k, k * k * Cg_pad, dt), dtype, ver[0] if ver is not None else None)
+        if xs.dtype == torch.uint8:
+            L.stem_im2col_u8(dt, xs.data_ptr(), hwc, xcol.data_ptr(), B, H, W, Ho, Wo, st)
         else:
+            L.stem_im2col(dt, xs.data_ptr(), xcol.data_ptr(), B, H, W, Ho, Wo, st)
+        # wcol is built from the already quantised stem weight and repacked per call: no quantiser entry, no version token, no pack registry
+        z, plan, saved = _dense_forward(xcol, w1x1, g32, b32, rm, rv, 32, 1, 1, 0, 1, act, res, res_mode, training, eps, momentum, cache, True, None,
+                                        None, False)
+    return z, (plan._replace(stem=True) if plan is not None else None), saved
+
+
+def _dw_forward(xin, w32, g32, b32, rm, rv, k, s, p, act, res, res_mode, training, eps, momentum, cache, bn_apply, ver):
+    """depth-wise conv (one filter per channel): the eval form with folded BatchNorm + SiLU (+res) in its epilogue, or dwconv2d_fwd + the tail"""
+    L, st, dtype, dev = lib(), stream(), xin.dtype, xin.device
+    dt = code(dtype)
+    B, C, H, W = xin.shape
+    Ho, Wo = (H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1
+    sb, sh, sw = s3(xin)
+    fused = not training and bn_apply and DW_EVAL_FUSED
+    y = None if fused else nhwc_empty(B, C, Ho, Wo, dtype, dev)  # pre-BatchNorm tensor
+    nblk = L.dw_blocks(B * Ho * Wo)
+    part = ss_eval = None
+    if training:
+        part = _f32(nblk * C * 2, dev)
+        wp = _f32(k * k * C, dev)
+        L.dw_pack_weight(w32.data_ptr(), wp.data_ptr(), C, k, k, st)
+    else:
+        wp, ss_eval = _eval_consts(cache, "dw", w32, g32, b32, rm, rv, ver, dtype, k, C, 1, 1, C, eps)
+        if fused:
+            # eval: folded BatchNorm + SiLU (+ the RepVGGDW / shortcut residual) in the depth-wise kernel's epilogue - one launch, no
+            # pre-BN tensor (12 depth-wise layers of S-3D: 12 bn_act_fwd launches and their read + write less per forward)
+            ze = out_tensor(B, C, Ho, Wo, dtype, dev)
+            rr = to_nhwc(res, dtype, dense=True) if res_mode else None
+            if rr is not None:
+                assert rr.shape == ze.shape, "residual shape mismatch"
+            L.dwconv2d_fwd_affine(dt, xin.data_ptr(), sb, sh, sw, B, H, W, C, wp.data_ptr(), ss_eval[0].data_ptr(), ss_eval[1].data_ptr(), int(act),
+                                  res_mode, rr.data_ptr() if rr is not None else None, rr.stride(3) if rr is not None else 0,
+                                  ze.data_ptr(), ze.stride(3), Ho, Wo, k, k, s, p, st)
+            return ze, None, None
+    L.dwconv2d_fwd(dt, xin.data_ptr(), sb, sh, sw, B, H, W, C, wp.data_ptr(), y.data_ptr(), C, Ho, Wo, k, k, s, p,
+                   part.data_ptr() if training else None, st)
+    return _bn_act_tail(xin, w32, y, part, nblk, ss_eval, g32, b32, rm, rv, C, k, s, p, C, act, res, res_mode, training, eps, momentum, bn_apply,
+                        ver[0] if ver is not None else None, None)
+
+
+def _dense_forward(xin, w32, g32, b32, rm, rv, Cin, k, s, p, g, act, res, res_mode, training, eps, momentum, cache, bn_apply, ver, qent, pack_cache):
+    """dense / grouped conv over the NHWC input `xin` (Cin: its channels before padding); qent: the quantiser entry of w32 (fp8w mode) or
+    None; pack_cache: training weight packs go through the registry"""
+    L, st, dtype, dev = lib(), stream(), xin.dtype, xin.device
+    dt = code(dtype)
+    B, Cin_k, H, W = xin.shape
+    Cout = w32.shape[0]
+    Ho, Wo = (H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1
+    sb, sh, sw = s3(xin)
+    wver = ver[0] if ver is not None else None
+    y = nhwc_empty(B, Cout, Ho, Wo, dtype, dev) if (training or res_mode) else None  # pre-BatchNorm tensor (the eval fast paths have none)
+    # fp8 MFMA forward (set_fp8_conv): e4m3 codes of the weight x the MX-quantised activation; everything after the conv - BatchNorm
+    # statistics from the partial rows, the apply pass, the bf16 backward over (xin, w_eff) - is the bf16 path's
+    f8 = (FP8_CONV and qent is not None and dtype == torch.bfloat16 and k == 3 and s == 1 and p == 1 and Cin_k == Cin
+          and bool(L.conv3x3_fp8_ok(B, H, W, Cin, Cout, g)))
+    nblk = L.conv3x3_fp8_stat_rows(B, H, W) if f8 else L.conv2d_stat_rows(dt, B, H, W, Cin_k, Cout, g, k, k, s, p)
+    part = _f32(nblk * Cout * 2, dev) if training else None
+    Cg_pad = Cin_k // g
+    wp = ss_eval = None
+    if not training:
+        wp, ss_eval = _eval_consts(cache, "dense", w32, g32, b32, rm, rv, ver, dtype, k, g, Cin // g, Cg_pad, Cout, eps)
+    if f8:
+        xq, xs = fp8_input(xin)
+        wq, ws = fp8_weight(qent, Cin // g)
+        if not training and not res_mode:
+            ye = out_tensor(B, Cout, Ho, Wo, dtype, dev)
+            _timed(("conv_eval_fp8", dt, B, H, W, Cin_k, Cout, k, s, g, p),
+                   lambda: L.conv3x3_fp8_fwd(xq.data_ptr(), xs.data_ptr(), B, H, W, Cin, wq.data_ptr(), ws.data_ptr(), ye.data_ptr(), ye.stride(3), Cout, g, None,
+                                             ss_eval[0].data_ptr(), ss_eval[1].data_ptr(), int(act), st))
+            return ye, None, None
+        _timed(("conv_fwd_fp8", dt, B, H, W, Cin_k, Cout, k, s, g),
+               lambda: L.conv3x3_fp8_fwd(xq.data_ptr(), xs.data_ptr(), B, H, W, Cin, wq.data_ptr(), ws.data_ptr(), y.data_ptr(), y.stride(3), Cout, g,
+                                         part.data_ptr() if training else None, None, None, 0, st))
+    elif not training and not res_mode:
+        # eval: BatchNorm (running statistics) + SiLU folded into the conv epilogue - one launch, no pre-BN tensor; the packed
+        # weights and the scale/shift pair are cached until a parameter / buffer is modified in place or re-pointed
+        ye = out_tensor(B, Cout, Ho, Wo, dtype, dev)  # a pending placement (C2f / SPPF / Concat slot) is honoured in eval too
+        _timed(("conv_eval", dt, B, H, W, Cin_k, Cout, k, s, g, p),
+               lambda: L.conv2d_fwd_affine(dt, xin.data_ptr(), sb, sh, sw, B, H, W, Cin_k, wp.data_ptr(), ss_eval[0].data_ptr(), ss_eval[1].data_ptr(),
+                                           int(act), ye.data_ptr(), ye.stride(3), Ho, Wo, Cout, g, k, k, s, p, st))
+        return ye, None, None
+    elif (not training and res_mode == 1 and dtype == torch.bfloat16
+            and L.conv2d_fwd_affine_res_ok(dt, B, H, W, Cin_k, Cout, g, k, k, s, p)):
+        # eval Bottleneck shortcut: conv + folded BatchNorm + SiLU + residual in ONE launch (the narrow resident-weight kernel)
+        rr = to_nhwc(res, dtype, dense=True)
+        ye = out_tensor(B, Cout, Ho, Wo, dtype, dev)
+        L.conv2d_fwd_affine_res(dt, xin.data_ptr(), sb, sh, sw, B, H, W, Cin_k, wp.data_ptr(), ss_eval[0].data_ptr(), ss_eval[1].data_ptr(), int(act),
+                                rr.data_ptr(), rr.stride(3), ye.data_ptr(), ye.stride(3), Ho, Wo, Cout, g, k, k, s, p, st)
+        return ye, None, None
+    else:
+        # training, or eval with a residual the epilogue kernel does not serve: conv (eval: the cached packed weights) + the tail's pass
+        if training and pack_cache and PACK_CACHE:
+            wp = PACK_FWD.lookup(w32, w32.data_ptr(), (Cout, Cin // g, Cg_pad, k * k, k * k * Cg_pad, dt), dtype, wver)
+        elif training:
             wp = torch.empty(Cout * k * k * Cg_pad, dtype=dtype, device=dev)
             L.pack_weight_fwd(dt, w32.data_ptr(), wp.data_ptr(), Cout, Cin // g, Cg_pad, k, k, st)
-        if not f8:
-            _timed(("conv_fwd", dt, B, H, W, Cin_k, Cout, k, s, g),
-                   lambda: L.conv2d_fwd(dt, xin.data_ptr(), sb, sh, sw, B, H, W, Cin_k, wp.data_ptr(), None, y.data_ptr(), Cout, Ho, Wo, Cout, g,
-                                        k, k, s, p, part.data_ptr() if training else None, st))
+        _timed(("conv_fwd", dt, B, H, W, Cin_k, Cout, k, s, g),
+               lambda: L.conv2d_fwd(dt, xin.data_ptr(), sb, sh, sw, B, H, W, Cin_k, wp.data_ptr(), None, y.data_ptr(), Cout, Ho, Wo, Cout, g,
+                                    k, k, s, p, part.data_ptr() if training else None, st))
+    return _bn_act_tail(xin, w32, y, part, nblk, ss_eval, g32, b32, rm, rv, Cin, k, s, p, g, act, res, res_mode, training, eps, momentum, bn_apply,
+                        wver, qent if f8 else None)
+
+
+def _bn_act_tail(xin, w32, y, part, nblk, ss_eval, g32, b32, rm, rv, Cin, k, s, p, g, act, res, res_mode, training, eps, momentum, bn_apply, wver,
+                 fp8_entry):
+    """BatchNorm + activation (+res) over the pre-BatchNorm tensor y of a conv that has run.  Training: statistics from the conv's `nblk`
+    partial rows `part`; eval: the folded (scale, shift) pair `ss_eval`.  -> (z, plan, saved)"""
+    L, st, dtype, dev = lib(), stream(), y.dtype, y.device
+    dt = code(dtype)
+    B, Cin_k, H, W = xin.shape
+    _, Cout, Ho, Wo = y.shape
+    M = B * Ho * Wo
+    plan = ConvPlan(B, Cin, Cin_k, H, W, Cout, Ho, Wo, k, s, p, g, g > 1 and g == Cin and g == Cout, res_mode, training, dtype, int(act), wver,
+                    fp8_entry)
     if training:
         stats = _f32(6 * Cout, dev).view(6, Cout)  # mean, invstd, scale, shift, mean_g, mean_gx
         bump_param_epoch()  # bn_finalize updates the running statistics in place
         L.bn_finalize(part.data_ptr(), nblk, Cout, M, g32.data_ptr(), b32.data_ptr(), eps, momentum, rm.data_ptr(), rv.data_ptr(),
                       stats[0].data_ptr(), stats[1].data_ptr(), stats[2].data_ptr(), stats[3].data_ptr(), st)
+    elif not bn_apply:  # eval: the fused consumer reads the cached (scale, shift) pair as rows 2 / 3 of a statistics tensor
+        stats = torch.zeros(6, Cout, dtype=torch.float32, device=dev)
+        stats[2:4].copy_(ss_eval)
     else:
-        stats = None  # eval: the cached (scale, shift) pair
-        if not bn_apply:  # the fused consumer reads rows 2 / 3 of a statistics tensor
-            stats = torch.zeros(6, Cout, dtype=torch.float32, device=dev)
-            stats[2:4].copy_(ss_eval)
+        stats = None
     if not bn_apply:  # the consumer applies BatchNorm + activation itself (FusedConvBNProjFn): hand back the pre-BN tensor
-        cfg = (B, Cin, Cin_k, H, W, Cout, Ho, Wo, k, s, p, g, dw, res_mode, training, dtype, int(act), ver[0] if ver is not None else None,
-               qent if f8 else None)
-        return y, cfg, (xin, w32, y, stats, None)
+        return y, plan, (xin, w32, y, stats, None)
     z = out_tensor(B, Cout, Ho, Wo, dtype, dev)
     rr = None
     if res_mode:
         rr = to_nhwc(res, dtype, dense=True)
         assert rr.shape == z.shape, "residual shape mismatch"
     sc_t, sh_t = (stats[2], stats[3]) if training else (ss_eval[0], ss_eval[1])
-    if _FP8_WANT and dtype == torch.bfloat16 and not res_mode and Cout % 64 == 0 and not dw:
+    if _FP8_WANT and dtype == torch.bfloat16 and not res_mode and Cout % 64 == 0 and not plan.dw:
         # the consumer is an fp8 MFMA convolution: this pass also writes z's fp8 copy (e4m3 codes + E8M0 block scales)
         zq = torch.empty(B, Ho, Wo, Cout, dtype=torch.uint8, device=dev)
         zs = torch.empty(B, Ho, Wo, L.fp8_scale_pitch(Cout), dtype=torch.uint8, device=dev)
@@ -813,28 +844,20 @@ def _cba_forward(x, w32, g32, b32, rm, rv, k, s, p, g, act, res, res_mode, train
     else:
         L.bn_act_fwd(dt, y.data_ptr(), Cout, sc_t.data_ptr(), sh_t.data_ptr(), int(act), res_mode,
                      rr.data_ptr() if rr is not None else None, rr.stride(3) if rr is not None else 0, z.data_ptr(), z.stride(3), M, Cout, st)
-    # [17]: version token of the weights as packed (stacked views / fp8 shadows carry their identity outside the tensor's own counter)
-    # [18]: the quantiser entry whose codes the fp8 MFMA forward multiplied (None on every other path): the fp8 data gradient follows it
-    cfg = (B, Cin, Cin_k, H, W, Cout, Ho, Wo, k, s, p, g, dw, res_mode, training, dtype, int(act), ver[0] if ver is not None else None,
-           qent if f8 else None)
-    return z, cfg, (xin, w32, y, stats, rr if res_mode == 2 else None)
+    return z, plan, (xin, w32, y, stats, rr if res_mode == 2 else None)
 
 
-def _cba_backward(cfg, saved, dz, need_dx, need_dres, dx_range=None, pre=None, dx_out=None):
+def _cba_backward(plan, saved, dz, need_dx, need_dres, dx_range=None, pre=None, dx_out=None):
     """-> dx, dW (fp32 OIHW), dgamma, dbeta, dres.  dx_range=(lo, hi): only output channels lo..hi feed dx
     (the one-to-one head sees a detached input, reference head.py:820)."""
     L = lib()
-    xin, w32, y, stats, rr = saved
-    stem = cfg[-1] == "stem"
-    B, Cin, Cin_k, H, W, Cout, Ho, Wo, k, s, p, g, dw, res_mode, training, dtype, act = cfg[:17]
-    if not training:
+    _, _, y, stats, rr = saved
+    B, Cout, Ho, Wo, res_mode, dtype, act = plan.B, plan.Cout, plan.Ho, plan.Wo, plan.res_mode, plan.dtype, plan.act
+    if not plan.training:
         raise Y3DError("backward through an eval-mode (running-statistics) Conv is not supported")
     if pre is not None:  # (dy, dgb): the BatchNorm part was done by the caller (FusedConvBNProjFn)
-        return _conv_backward(cfg, saved, pre[0], pre[1], None, need_dx, dx_range, dx_out)
-    dt = code(dtype)
-    st = stream()
-    dev = dz.device
-    esz = 2 if dtype == torch.bfloat16 else 4
+        return _conv_backward(plan, saved, pre[0], pre[1], None, need_dx, dx_range, dx_out)
+    dt, st, dev = code(dtype), stream(), dz.device
     M = B * Ho * Wo
     dz = to_nhwc(dz, dtype, dense=True)
     nb = L.bn_bwd_blocks(M, Cout)
@@ -854,43 +877,42 @@ def _cba_backward(cfg, saved, dz, need_dx, need_dres, dx_range=None, pre=None, d
                        dy.data_ptr(), Cout, dres.data_ptr() if dres is not None else None, Cout, M, Cout, st)
     if res_mode == 1:
         dres = dz
-    return _conv_backward(cfg, saved, dy, dgb, dres, need_dx, dx_range, dx_out)
+    return _conv_backward(plan, saved, dy, dgb, dres, need_dx, dx_range, dx_out)
 
 
-def _fp8_dgrad_plan(cfg, need_dx, dx_range):
-    """(entry, lo, hi) when the data gradient of this layer runs on the fp8 kernel, else None (the bf16 call runs)"""
-    ent = _fp8_dgrad_entry(cfg)
-    if ent is None or not need_dx:
+def _fp8_dgrad_plan(plan, need_dx, dx_range):
+    """(entry, lo, hi) when the data gradient of this layer runs on the fp8 kernel, else None (the bf16 call runs).  entry: the
+    _QuantRegistry entry whose codes it multiplies - the switch is on, the layer's forward took the fp8 kernel and the entry still holds
+    the weight version that forward packed"""
+    ent = plan.fp8_entry
+    if not (FP8_DGRAD and FP8_CONV and need_dx) or ent is None or plan.wver != ((WEIGHT_EPOCH, ent["count"]),):
         return None
-    B, Cin, Cin_k, H, W, Cout, Ho, Wo, k, s, p, g = cfg[:12]
+    Cin, Cout, g = plan.Cin, plan.Cout, plan.g
     lo, hi = dx_range if dx_range is not None else (0, Cout)
-    if Cin_k != Cin or cfg[15] != torch.bfloat16 or (k, s, p) != (3, 1, 1) or (g != 1 and (lo, hi) != (0, Cout)):
+    if plan.Cin_k != Cin or plan.dtype != torch.bfloat16 or (plan.k, plan.s, plan.p) != (3, 1, 1) or (g != 1 and (lo, hi) != (0, Cout)):
         return None
     # a window reads the slab's scale bytes as an aligned dword: lo and hi - lo in whole 128-channel units
     if (lo, hi) != (0, Cout) and (lo % 128 or (hi - lo) % 128):
         return None
-    if not lib().conv3x3_fp8_dgrad_ok(B, H, W, Cin, hi - lo, g):
+    if not lib().conv3x3_fp8_dgrad_ok(plan.B, plan.H, plan.W, Cin, hi - lo, g):
         return None
     return ent, lo, hi
 
 
-def _conv_backward(cfg, saved, dy, dgb, dres, need_dx, dx_range, dx_out=None):
-    """data and weight gradients of the conv given dy (gradient wrt its pre-BatchNorm output); cfg[17] = version token of the weights
-    as the forward packed them"""
+def _conv_backward(plan, saved, dy, dgb, dres, need_dx, dx_range, dx_out=None):
+    """data and weight gradients of the conv given dy (gradient wrt its pre-BatchNorm output)"""
     L = lib()
-    xin, w32, y, stats, rr = saved
-    stem = cfg[-1] == "stem"
-    B, Cin, Cin_k, H, W, Cout, Ho, Wo, k, s, p, g, dw, res_mode, training, dtype, act = cfg[:17]
-    wver = cfg[17]
-    dt = code(dtype)
-    st = stream()
+    xin, w32 = saved[:2]
+    B, Cin, Cin_k, H, W, Cout, Ho, Wo = plan.B, plan.Cin, plan.Cin_k, plan.H, plan.W, plan.Cout, plan.Ho, plan.Wo
+    k, s, p, g, dtype = plan.k, plan.s, plan.p, plan.g, plan.dtype
+    dt, st = code(dtype), stream()
     dev = dy.device
     esz = 2 if dtype == torch.bfloat16 else 4
     M = B * Ho * Wo
     sb, sh, sw = s3(xin)
     dx = None
     dW = torch.empty_like(w32)
-    if dw:
+    if plan.dw:
         wp = _f32(k * k * Cout, dev)
         L.dw_pack_weight(w32.data_ptr(), wp.data_ptr(), Cout, k, k, st)
         if need_dx:
@@ -901,12 +923,12 @@ def _conv_backward(cfg, saved, dy, dgb, dres, need_dx, dx_range, dx_out=None):
         L.dwconv2d_bwd_weight(dt, xin.data_ptr(), sb, sh, sw, B, H, W, Cin, dy.data_ptr(), Cout, Ho, Wo, k, k, s, p, slab.data_ptr(),
                               dW.data_ptr(), 0, st)
     else:
-        plan = _fp8_dgrad_plan(cfg, need_dx, dx_range) if not stem else None
-        if plan is not None and not (px_dense(dy) and dy.data_ptr() % 16 == 0 and dy.stride(3) % 8 == 0):
-            plan = None
-        if plan is not None:
+        f8 = _fp8_dgrad_plan(plan, need_dx, dx_range)
+        if f8 is not None and not (px_dense(dy) and dy.data_ptr() % 16 == 0 and dy.stride(3) % 8 == 0):
+            f8 = None
+        if f8 is not None:
             # fp8 data gradient (set_fp8_dgrad): the forward kernel on (dy * row scales -> MX, the forward's codes flipped and swapped)
-            qent, lo, hi = plan
+            qent, lo, hi = f8
             wqd, wsd = fp8_weight_dgrad(qent, Cin, g, lo, hi)
             # dy's fp8 copy: the stand-alone quantiser over the window's channels (a copy written by the BatchNorm-backward apply pass itself
             # measured slower than apply + this pass on the head shapes and is not part of the path: DESIGN.md 3.9)
@@ -926,11 +948,11 @@ def _conv_backward(cfg, saved, dy, dgb, dres, need_dx, dx_range, dx_out=None):
             co = hi - lo
             kp = L.conv_kpad(dt, k * k * (co // g))
             src = w32.data_ptr() + lo * (Cin // g) * k * k * 4
-            if stem or not PACK_CACHE:
+            if plan.stem or not PACK_CACHE:
                 wpd = torch.empty(Cin * kp, dtype=dtype, device=dev)
                 L.pack_weight_dgrad(dt, src, wpd.data_ptr(), co, Cin // g, g, k, k, st)
             else:
-                wpd = PACK_DGRAD.lookup(w32, src, (g, co // g, Cin // g, k * k, kp, dt), dtype, wver)
+                wpd = PACK_DGRAD.lookup(w32, src, (g, co // g, Cin // g, k * k, kp, dt), dtype, plan.wver)
             dx = dx_out if dx_out is not None else nhwc_empty(B, Cin, H, W, dtype, dev)  # dx_out: a slice of a shared gradient buffer (grad_slot)
             dsb, dsh, dsw = s3(dy)
             _timed(("conv_dgrad", dt, B, H, W, Cin, co, k, s, g),
@@ -941,7 +963,7 @@ def _conv_backward(cfg, saved, dy, dgb, dres, need_dx, dx_range, dx_out=None):
         _timed(("conv_wgrad", dt, B, H, W, Cin_k, Cout, k, s, g),
                lambda: L.conv2d_bwd_weight(dt, xin.data_ptr(), sb, sh, sw, B, H, W, Cin_k, Cin, dy.data_ptr(), Cout, Ho, Wo, Cout, g, k, k,
                                            s, p, slab.data_ptr(), ns, dW.data_ptr(), 0, st))
-    if stem:  # [Cout][(r*3+q)*3+ci | 5 zeros] -> OIHW (Cout, 3, 3, 3); the image itself gets no gradient
+    if plan.stem:  # [Cout][(r*3+q)*3+ci | 5 zeros] -> OIHW (Cout, 3, 3, 3); the image itself gets no gradient
         dW = dW.reshape(Cout, 32)[:, :27].reshape(Cout, 3, 3, 3).permute(0, 3, 1, 2).contiguous()
         dx = None
     return dx, dW, dgb[0], dgb[1], dres
@@ -1306,9 +1328,6 @@ class HeadProjFn(torch.autograd.Function):
         return (None, *dxs, *dws, *dbs)
 
 
-_IDENT = {}  # (channels, device) -> (ones, zeros): the identity BatchNorm of the eval projection
-
-
 def proj_slices_eval(x, offsets, cin, ws, bs):
     """eval form of HeadProjSlicesFn (no graph): branch j projects channels [offsets[j], offsets[j] + cin) of the ACTIVATED features x with
     its 1x1 conv + bias (head.py:637), all branches in one launch.  bf16 with 64 / 128 channels per branch: the matrix-core kernel of
@@ -1327,9 +1346,7 @@ def proj_slices_eval(x, offsets, cin, ws, bs):
     out = nhwc_empty(B, tot, H, W, dtype, x.device)
     w32 = [w.detach().float().contiguous() for w in ws]
     b32 = [b.detach().float().contiguous() for b in bs]
-    ident = _IDENT.get((Ct, x.device))
-    if ident is None:
-        ident = _IDENT[(Ct, x.device)] = (torch.ones(Ct, dtype=torch.float32, device=x.device), torch.zeros(Ct, dtype=torch.float32, device=x.device))
+    ident = _identity_bn(Ct, x.device)
     PV, IA = ctypes.c_void_p * n, ctypes.c_int * n
     L.proj_group_fwd_bn_mfma(n, cin, x.data_ptr(), x.stride(3), IA(*offsets), PV(*[t.data_ptr() for t in w32]), PV(*[t.data_ptr() for t in b32]), IA(*couts),
                              ident[0].data_ptr(), ident[1].data_ptr(), 0, out.data_ptr(), tot, B * H * W, st)
@@ -1479,7 +1496,7 @@ class FusedConvBNProjFn(torch.autograd.Function):
             L.proj_group_bwd_weight_bn(dt, n, cin, y.data_ptr(), y.stride(3), c_off, dout.data_ptr(), dout.stride(3), c_co, stats[2].data_ptr(),
                                        stats[3].data_ptr(), act, slab.data_ptr(), bslab.data_ptr(), PV(*[t.data_ptr() for t in dws]),
                                        PV(*[t.data_ptr() for t in dbs]), P, st)
-        if mfma and ctx.cfg[14]:
+        if mfma and ctx.cfg.training:
             # BatchNorm backward straight from `dout`: dz = dout . W is recomputed on the matrix cores by the reduce and the apply pass
             # (proj_bn_mfma.hip) instead of being written once and read twice (839 MB at the stride-8 level)
             nblk = L.proj_group_bn_bwd_blocks(P)
