@@ -384,6 +384,14 @@ int y3d_loss2d(int dtype, int nl, const void* const* maps, const int64_t* psw, v
                const int* W, const float* strides, int B, int nc, const float* gt, int n, const uint8_t* fg_mask,
                const int* target_gt_idx, const float* target_scores, const float* scal, float w_box, float w_cls, float w_dfl,
                float grad_scale, float* partials, float* items, void* stream);
+/* Crowded route of the 2D assigner: 1 <= n <= 512 rows per image, same arguments and the same outputs as y3d_tal2d_assign (fg_mask and
+ * target_gt_idx bit for bit), without a buffer that grows with n * A: each box looks only at the grid cells under it and the anchors
+ * resolve by claim counts.  scratch: y3d_tal2d_scratch_floats(B, n, A, topk) floats, 16-byte aligned =
+ * B * n * 42 + 7 * B * A + 2 * ceil(B * A / 256) + 8, or -1 past 2^31.  loss.Loss2dFn takes this route when n > 64 (`max_boxes`). */
+int y3d_tal2d_scratch_floats(int B, int n, int A, int topk);
+int y3d_tal2d_assign_crowded(int dtype, int nl, const void* const* maps, const int64_t* psw, const int* H, const int* W, const float* strides,
+                             int B, int nc, const float* gt, int n, int topk, float alpha, float beta, float* scratch, uint8_t* fg_mask,
+                             int* target_gt_idx, float* target_scores, float* scal, const int* n_used, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Eval-side selection (post.hip): v10Detect3d.select_candidates / extract_patches / scatter / decode (head.py:656-716,

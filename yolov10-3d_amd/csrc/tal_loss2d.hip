@@ -259,6 +259,279 @@ __global__ __launch_bounds__(256) void loss2d_final_kernel(const float* __restri
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Crowded route (y3d_tal2d_assign_crowded, up to 512 boxes per image): the same assignment without the two dense (B, n, A) planes.
+// The metric of a (box, anchor) pair is 0 unless the anchor centre lies inside the box, so a box only looks at the grid cells under it;
+// the anchors resolve by claim counts instead of walking n * topk candidates each, and whatever the dense route read back from its
+// planes (the overlaps of a multiply-claimed anchor, the winner's align / overlap) is formed again from the decoded box by the same
+// function.  The library is built with -ffp-contract=off, so the same expression gives the same bits in every kernel.
+// Scratch: B * n * (GTW + 2) + 7 * B * A + 2 * ceil(B * A / 256) floats (y3d_tal2d_scratch_floats).
+// ---------------------------------------------------------------------------------------------------------------------------------
+
+// one thread per anchor: the predicted box in pixels as metric2d_kernel forms it, and the claim words cleared
+template <typename T>
+__global__ __launch_bounds__(256) void decode2d_kernel(Levels L, float4* __restrict__ pbox, int* __restrict__ cnt, int* __restrict__ first) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long)L.B * L.A) return;
+  const int b = (int)(i / L.A), a = (int)(i - (long)b * L.A);
+  float ax, ay, st;
+  int lvl;
+  const T* p = anchor_ptr<T>(L, b, a, ax, ay, st, lvl);
+  float dl = dfl_expect<T>(p, nullptr), dtp = dfl_expect<T>(p + RM, nullptr), dr = dfl_expect<T>(p + 2 * RM, nullptr),
+        db = dfl_expect<T>(p + 3 * RM, nullptr);
+  pbox[i] = make_float4((ax - dl) * st, (ay - dtp) * st, (ax + dr) * st, (ay + db) * st);
+  cnt[i] = 0;
+  first[i] = 0x7fffffff;
+}
+
+// align and overlap of (box, anchor a of image b) in metric2d_kernel's operation order: both 0 for a padding row or a centre outside the box
+template <typename T>
+__device__ __forceinline__ void metric2d_pair(const Levels& L, int b, int a, float valid, int label, const float* box, float4 pb, float alpha,
+                                              float beta, float& al, float& ov) {
+  al = 0.f;
+  ov = 0.f;
+  if (valid == 0.f) return;
+  float ax, ay, st;
+  int lvl;
+  const T* p = anchor_ptr<T>(L, b, a, ax, ay, st, lvl);
+  float apx = ax * st, apy = ay * st;
+  float d0 = apx - box[0], d1 = apy - box[1], d2 = box[2] - apx, d3 = box[3] - apy;
+  if (!(fminf(fminf(d0, d1), fminf(d2, d3)) > 1e-9f)) return;
+  float s = sigmoid_f(TT<T>::ld(p + 4 * RM + label));
+  ov = fmaxf(ciou_f(box, pb.x, pb.y, pb.z, pb.w), 0.f);
+  float sa = alpha == 0.5f ? sqrtf(s) : (alpha == 1.f ? s : powf(s, alpha));
+  float ob = beta == 1.f ? ov : powf(ov, beta);
+  al = sa * ob;
+}
+
+// the grid cells a box can own: per level a rectangle two cells wider than the box on every side (the exact centre-in-box test is
+// metric2d_pair's), clipped to the map.  Positions 0..off[MAXL) run level-major, row-major: ascending anchor index.
+struct BoxCells { int x0[MAXL], y0[MAXL], w[MAXL], off[MAXL + 1]; };
+
+__device__ __forceinline__ void box_cells(const Levels& L, const float* box, BoxCells& c) {
+  c.off[0] = 0;
+#pragma unroll
+  for (int l = 0; l < MAXL; ++l) {
+    int w = 0, h = 0, x0 = 0, y0 = 0;
+    if (l < L.nl) {
+      const float s = L.stride[l], W = (float)L.W[l], H = (float)L.H[l];
+      x0 = (int)fminf(fmaxf(floorf(box[0] / s - 0.5f) - 1.f, 0.f), W);
+      y0 = (int)fminf(fmaxf(floorf(box[1] / s - 0.5f) - 1.f, 0.f), H);
+      int x1 = (int)fminf(fmaxf(ceilf(box[2] / s - 0.5f) + 1.f, -1.f), W - 1.f);
+      int y1 = (int)fminf(fmaxf(ceilf(box[3] / s - 0.5f) + 1.f, -1.f), H - 1.f);
+      w = max(x1 - x0 + 1, 0);
+      h = max(y1 - y0 + 1, 0);
+      if (w == 0 || h == 0) w = h = 0;
+    }
+    c.x0[l] = x0; c.y0[l] = y0; c.w[l] = w;
+    c.off[l + 1] = c.off[l] + w * h;
+  }
+}
+
+// position -> anchor index (an empty level shares its offset with the next one, which then takes the position)
+__device__ __forceinline__ int cell_anchor(const Levels& L, const BoxCells& c, int p) {
+  int o = 0, x0 = c.x0[0], y0 = c.y0[0], w = c.w[0], a0 = L.a0[0], W = L.W[0];
+#pragma unroll
+  for (int i = 1; i < MAXL; ++i)
+    if (p >= c.off[i]) { o = c.off[i]; x0 = c.x0[i]; y0 = c.y0[i]; w = c.w[i]; a0 = L.a0[i]; W = L.W[i]; }
+  int q = p - o;
+  int dy = q / w, dx = q - dy * w;
+  return a0 + (y0 + dy) * W + x0 + dx;
+}
+
+// one block per (b, g), rows slow as in topk_kernel: the k largest metrics of the box in (value desc, index asc) order over the cells
+// under it, then - when fewer than k are positive - the lowest anchor indices not yet taken, which is what the dense row's zeros give.
+// Every pick whose centre lies inside the box claims its anchor: cnt[b][a] += 1, first[b][a] = min(first, g).
+// lds_row: the metrics of the cells stay in LDS (at most A floats); otherwise every pass forms them again.
+template <typename T>
+__global__ __launch_bounds__(256) void crowded_topk_kernel(Levels L, const float* __restrict__ rec, const float4* __restrict__ pbox,
+                                                           int* __restrict__ cnt, int* __restrict__ first, int n, int k, float alpha,
+                                                           float beta, const int* __restrict__ n_used, int lds_row) {
+  extern __shared__ float sval[];
+  __shared__ float wv[4];
+  __shared__ int wp[4];
+  __shared__ int chosen_p[16], chosen_a[16];
+  const int B_ = gridDim.x / n;
+  const int g = blockIdx.x / B_, b = blockIdx.x - g * B_;
+  if (g >= rows_used(n_used, n)) return;
+  const float* r = rec + ((long)b * n + g) * GTW;
+  if (r[G_VALID] == 0.f) return;  // a padding row claims nothing
+  const int label = (int)r[G_LABEL];
+  const float box[4] = {r[G_BOX], r[G_BOX + 1], r[G_BOX + 2], r[G_BOX + 3]};
+  __shared__ BoxCells c;  // block-uniform and indexed by level: LDS, not registers (a private copy went to scratch memory)
+  if (threadIdx.x == 0) box_cells(L, box, c);
+  __syncthreads();
+  const int m = c.off[MAXL];
+  const float4* pb = pbox + (long)b * L.A;
+  const bool in_lds = lds_row != 0;
+  const int tid = threadIdx.x;
+  if (in_lds) {
+    for (int p = tid; p < m; p += 256) {
+      int a = cell_anchor(L, c, p);
+      float al, ov;
+      metric2d_pair<T>(L, b, a, 1.f, label, box, pb[a], alpha, beta, al, ov);
+      sval[p] = al;
+    }
+    __syncthreads();
+  }
+  int j = 0;
+  for (; j < k; ++j) {
+    float bv = 0.f;  // only positive metrics compete here
+    int bp = 0x7fffffff;
+    for (int p = tid; p < m; p += 256) {
+      float v;
+      if (in_lds) {
+        v = sval[p];  // taken cells were overwritten with -2
+      } else {
+        bool skip = false;
+        for (int t = 0; t < j; ++t) skip |= (chosen_p[t] == p);
+        if (skip) continue;
+        const int a = cell_anchor(L, c, p);
+        float ov;
+        metric2d_pair<T>(L, b, a, 1.f, label, box, pb[a], alpha, beta, v, ov);
+      }
+      if (v > bv) { bv = v; bp = p; }  // p ascends: the first of equal values stays
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      float v2 = __shfl_xor(bv, o, 64);
+      int p2 = __shfl_xor(bp, o, 64);
+      if (v2 > bv || (v2 == bv && p2 < bp)) { bv = v2; bp = p2; }
+    }
+    if ((tid & 63) == 0) { wv[tid >> 6] = bv; wp[tid >> 6] = bp; }
+    __syncthreads();
+    bv = wv[0];
+    bp = wp[0];
+#pragma unroll
+    for (int w = 1; w < 4; ++w)
+      if (wv[w] > bv || (wv[w] == bv && wp[w] < bp)) { bv = wv[w]; bp = wp[w]; }
+    if (bp == 0x7fffffff) break;  // block-uniform: no positive metric is left
+    if (tid == 0) {
+      chosen_p[j] = bp;
+      chosen_a[j] = cell_anchor(L, c, bp);
+      if (in_lds) sval[bp] = -2.f;
+    }
+    __syncthreads();
+  }
+  if (tid == 0) {  // the remaining picks have metric 0: lowest anchor index first, over ALL anchors of the image
+    int a = 0;
+    for (int t = j; t < k; ++t) {
+      for (bool hit = true; hit;) {
+        hit = false;
+        for (int u = 0; u < j; ++u) hit |= (chosen_a[u] == a);
+        if (hit) ++a;
+      }
+      chosen_a[t] = a < L.A ? a : -1;
+      ++a;
+    }
+  }
+  __syncthreads();
+  if (tid < k) {
+    const int a = chosen_a[tid];
+    if (a >= 0) {
+      // mask_pos = mask_topk * mask_in_gts * mask_gt (tal.py:492-497): a pick outside the box is dropped
+      float ax, ay, st;
+      int lvl;
+      anchor_ptr<T>(L, b, a, ax, ay, st, lvl);
+      float apx = ax * st, apy = ay * st;
+      float d0 = apx - box[0], d1 = apy - box[1], d2 = box[2] - apx, d3 = box[3] - apy;
+      if (fminf(fminf(d0, d1), fminf(d2, d3)) > 1e-9f) {
+        atomicAdd(cnt + (long)b * L.A + a, 1);
+        atomicMin(first + (long)b * L.A + a, g);
+      }
+    }
+  }
+}
+
+// one thread per anchor, one image per block row: an anchor claimed once goes to its claimer; claimed more than once it takes the
+// arg-max of the overlaps over ALL rows of the image, first maximum (tal.py:741-748), formed here from the decoded box.  The winner's
+// align / overlap feed the per-box normalisers (atomicMax on the non-negative float bits) and walign keeps the align for the scores.
+template <typename T>
+__global__ __launch_bounds__(256) void crowded_resolve_kernel(Levels L, const float* __restrict__ rec, const float4* __restrict__ pbox,
+                                                              const int* __restrict__ cnt, const int* __restrict__ first,
+                                                              unsigned char* __restrict__ fg, int* __restrict__ gt_idx,
+                                                              float* __restrict__ walign, unsigned* __restrict__ pa, unsigned* __restrict__ po,
+                                                              int n, float alpha, float beta, const int* __restrict__ n_used) {
+  extern __shared__ float sb[];  // per row in use: valid | box
+  const int b = blockIdx.y;
+  const int ne = rows_used(n_used, n);
+  for (int i = threadIdx.x; i < ne * 5; i += blockDim.x) {
+    int g = i / 5, j = i - g * 5;
+    sb[i] = rec[((long)b * n + g) * GTW + (j == 0 ? G_VALID : G_BOX + j - 1)];
+  }
+  __syncthreads();
+  const int a = blockIdx.x * blockDim.x + threadIdx.x;
+  if (a >= L.A) return;
+  const long i = (long)b * L.A + a;
+  const int c = cnt[i];
+  if (c == 0) {
+    fg[i] = 0;
+    gt_idx[i] = 0;
+    walign[i] = 0.f;
+    return;
+  }
+  int gsel = first[i];
+  const float4 pb = pbox[i];
+  if (c > 1) {
+    float ax, ay, st;
+    int lvl;
+    anchor_ptr<T>(L, b, a, ax, ay, st, lvl);
+    const float apx = ax * st, apy = ay * st;
+    float bv = -1.f;
+    for (int g = 0; g < ne; ++g) {
+      const float* q = sb + g * 5;
+      float ov = 0.f;
+      if (q[0] != 0.f) {
+        float d0 = apx - q[1], d1 = apy - q[2], d2 = q[3] - apx, d3 = q[4] - apy;
+        if (fminf(fminf(d0, d1), fminf(d2, d3)) > 1e-9f) ov = fmaxf(ciou_f(q + 1, pb.x, pb.y, pb.z, pb.w), 0.f);
+      }
+      if (ov > bv) { bv = ov; gsel = g; }
+    }
+  }
+  const float* r = rec + ((long)b * n + gsel) * GTW;
+  float al, ov;
+  metric2d_pair<T>(L, b, a, r[G_VALID], (int)r[G_LABEL], r + G_BOX, pb, alpha, beta, al, ov);
+  fg[i] = 1;
+  gt_idx[i] = gsel;
+  walign[i] = al;
+  atomicMax(pa + b * n + gsel, __float_as_uint(al));
+  atomicMax(po + b * n + gsel, __float_as_uint(ov));
+}
+
+// scores_kernel with the winner's align per anchor (walign) in place of the dense plane: same outputs, same block partials
+__global__ __launch_bounds__(256) void crowded_scores_kernel(const unsigned char* __restrict__ fg, const int* __restrict__ gt_idx,
+                                                             const float* __restrict__ walign, const float* __restrict__ rec,
+                                                             const unsigned* __restrict__ pa, const unsigned* __restrict__ po,
+                                                             float* __restrict__ tscores, float* __restrict__ part, int B, int n, int A, int nc,
+                                                             float eps) {
+  __shared__ float s0[256], s1[256];
+  long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  float ts = 0.f, nf = 0.f;
+  if (i < (long)B * A) {
+    int b = (int)(i / A);
+    int lab = -1;
+    float norm = 0.f;
+    if (fg[i]) {
+      int g = gt_idx[i];
+      lab = (int)rec[((long)b * n + g) * GTW + G_LABEL];
+      norm = walign[i] * __uint_as_float(po[b * n + g]) / (__uint_as_float(pa[b * n + g]) + eps);
+      ts = norm;
+      nf = 1.f;
+    }
+    for (int c = 0; c < nc; ++c) tscores[i * nc + c] = c == lab ? norm : 0.f;
+  }
+  s0[threadIdx.x] = ts;
+  s1[threadIdx.x] = nf;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (threadIdx.x < s) { s0[threadIdx.x] += s0[threadIdx.x + s]; s1[threadIdx.x] += s1[threadIdx.x + s]; }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) { part[blockIdx.x * 2] = s0[0]; part[blockIdx.x * 2 + 1] = s1[0]; }
+}
+
+long crowded_scratch_floats(long B, long n, long A) { return B * n * (GTW + 2) + 7 * B * A + 2 * ((B * A + 255) / 256) + 8; }
+
 int fill2d(Levels& L, int dtype, int nl, const void* const* maps, const int64_t* psw, void* const* grads, const int64_t* gsw, const int* H,
            const int* W, const float* strides, int B, int nc) {
   Y3D_CHECK(nl >= 1 && nl <= MAXL, "tal2d: 1..%d levels", MAXL);
@@ -307,6 +580,53 @@ int y3d_tal2d_assign(int dtype, int nl, const void* const* maps, const int64_t* 
   int nblk = cdiv((long)B * A, 256);
   hipLaunchKernelGGL(resolve_kernel, dim3(nblk), dim3(256), 0, st, cand, align, ovl, fg_mask, target_gt_idx, pa, po, B, n, A, topk, n_used);
   hipLaunchKernelGGL(scores_kernel, dim3(nblk), dim3(256), 0, st, fg_mask, target_gt_idx, align, rec, pa, po, target_scores, part, B, n, A, nc, 1e-9f);
+  hipLaunchKernelGGL(scal_kernel, dim3(1), dim3(64), 0, st, part, nblk, scal);
+  Y3D_LAUNCH_CHECK();
+  return Y3D_OK;
+}
+
+// floats of scratch of y3d_tal2d_assign_crowded: records + normalisers per box; decoded box, claim count, first claimer and the
+// winner's align per anchor; block partials.  Nothing grows with n * A; topk needs no storage (the picks turn into claims in place).
+int y3d_tal2d_scratch_floats(int B, int n, int A, int topk) {
+  (void)topk;
+  long v = crowded_scratch_floats(B, n, A);
+  return v < (1L << 31) ? (int)v : -1;
+}
+
+int y3d_tal2d_assign_crowded(int dtype, int nl, const void* const* maps, const int64_t* psw, const int* H, const int* W, const float* strides,
+                             int B, int nc, const float* gt, int n, int topk, float alpha, float beta, float* scratch, uint8_t* fg_mask,
+                             int* target_gt_idx, float* target_scores, float* scal, const int* n_used, void* stream) {
+  Levels L;
+  if (fill2d(L, dtype, nl, maps, psw, nullptr, nullptr, H, W, strides, B, nc)) return Y3D_ERR_INVALID;
+  Y3D_CHECK(n >= 1 && n <= 512, "tal2d_assign_crowded: 1..512 ground-truth boxes per image (got %d)", n);
+  Y3D_CHECK(topk >= 1 && topk <= 16, "tal2d_assign_crowded: topk in 1..16");
+  const int A = L.A;
+  Y3D_CHECK(crowded_scratch_floats(B, n, A) < (1L << 31), "tal2d_assign_crowded: scratch exceeds 2^31 floats");
+  Y3D_CHECK(((uintptr_t)scratch & 15) == 0, "tal2d_assign_crowded: scratch must be 16-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  float* rec = scratch;
+  float4* pbox = (float4*)(rec + (long)B * n * GTW);  // GTW % 4 == 0: 16-byte aligned
+  int* cnt = (int*)(pbox + (long)B * A);
+  int* first = cnt + (long)B * A;
+  float* walign = (float*)(first + (long)B * A);
+  unsigned* pa = (unsigned*)(walign + (long)B * A);
+  unsigned* po = pa + (long)B * n;
+  float* part = (float*)(po + (long)B * n);
+  const int nblk = cdiv((long)B * A, 256);
+  const bool fits = (size_t)A * sizeof(float) <= 96 * 1024;  // as topk_kernel: the cells' metrics in LDS, else formed again by every pass
+  const size_t sm_row = fits ? (size_t)A * sizeof(float) : 0, sm_box = (size_t)n * 5 * sizeof(float);
+  dim3 ga(cdiv(A, 256), B);
+  hipLaunchKernelGGL(gt2d_prep_kernel, dim3(cdiv((long)B * n, 64)), dim3(64), 0, st, gt, rec, pa, po, B, n, nc);
+#define Y3D_CROWDED(T)                                                                                                                      \
+  hipLaunchKernelGGL(decode2d_kernel<T>, dim3(nblk), dim3(256), 0, st, L, pbox, cnt, first);                                                \
+  hipLaunchKernelGGL(crowded_topk_kernel<T>, dim3(B * n), dim3(256), sm_row, st, L, rec, pbox, cnt, first, n, topk, alpha, beta, n_used,    \
+                     fits ? 1 : 0);                                                                                                         \
+  hipLaunchKernelGGL(crowded_resolve_kernel<T>, ga, dim3(256), sm_box, st, L, rec, pbox, cnt, first, fg_mask, target_gt_idx, walign, pa, po, \
+                     n, alpha, beta, n_used)
+  if (dtype == Y3D_BF16) { Y3D_CROWDED(bf16_t); } else { Y3D_CROWDED(float); }
+#undef Y3D_CROWDED
+  hipLaunchKernelGGL(crowded_scores_kernel, dim3(nblk), dim3(256), 0, st, fg_mask, target_gt_idx, walign, rec, pa, po, target_scores, part, B, n,
+                     A, nc, 1e-9f);
   hipLaunchKernelGGL(scal_kernel, dim3(1), dim3(64), 0, st, part, nblk, scal);
   Y3D_LAUNCH_CHECK();
   return Y3D_OK;

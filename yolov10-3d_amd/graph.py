@@ -88,7 +88,7 @@ class GraphedTrainStep:
     callable that was registered when it was constructed.
 
     Static shapes: the per-box label tensors (`ddp.PER_BOX_KEYS` + `batch_idx`) are padded to `label_capacity` rows (default: 64 per
-    image, the assigner's own limit); padding rows carry batch_idx = -1, which no image matches.  `step(batch)` copies the batch into
+    image, the assigner's own limit, or the `max_boxes` of the model's 2D loss where that is set); padding rows carry batch_idx = -1, which no image matches.  `step(batch)` copies the batch into
     the static buffers and replays.  Left to the caller, eagerly, after the replay: `ema.update` (its decay ramp is a host-side
     function of the update count) and learning-rate changes through `opt.set_hyper` (in-place writes of the device tables).
     After every replay the host-side bookkeeping the captured Python code would have done is redone: BatchNorm `num_batches_tracked`
@@ -102,7 +102,9 @@ class GraphedTrainStep:
         self.model, self.opt, self.max_norm, self.reducer = model, opt, max_norm, reducer
         self.box_keys = tuple(k for k in (("batch_idx",) + PER_BOX_KEYS) if k in batch)
         B = batch["img"].shape[0]
-        self.cap = int(label_capacity or 64 * B)
+        crit = getattr(model, "criterion", None)
+        per_image = getattr(crit, "max_boxes", None) or getattr(getattr(model, "args", None), "max_boxes", None) or 64
+        self.cap = int(label_capacity or per_image * B)
         self.static = {}
         for k, v in batch.items():
             if not torch.is_tensor(v):

@@ -29,6 +29,16 @@ from .modules import make_anchors
 
 _OVERFLOW_PENDING = []  # (event, pinned int32[1], cap) of pad_targets launches whose per-image box count has not been looked at yet
 TARGET_CAP = 64  # rows per image the assigner kernels take (tal_loss3d.hip / tal_loss2d.hip)
+CROWDED_CAPS = tuple(range(128, 513, 64))  # `max_boxes` of the 2D losses: rows per image on the crowded route of tal_loss2d.hip
+
+
+def check_max_boxes(max_boxes):
+    """the opt-in per-image capacity of the 2D losses: None (64 rows, the dense assigner) or a multiple of 64 in 128..512"""
+    if max_boxes is None:
+        return None
+    if isinstance(max_boxes, bool) or not isinstance(max_boxes, int) or max_boxes not in CROWDED_CAPS:
+        raise ValueError(f"max_boxes must be None or a multiple of 64 in 128..512 (got {max_boxes!r})")
+    return max_boxes
 
 
 def check_target_overflow(wait=False):
@@ -46,15 +56,18 @@ def check_target_overflow(wait=False):
         n = int(host[0])
         if n > cap:
             _OVERFLOW_PENDING[:] = keep
-            raise Y3DError(f"pad_targets: an image of a recent batch has {n} ground-truth boxes, the assigner kernels take at most {cap} per "
-                           f"image (KITTI's max_objs is 50); its last {n - cap} boxes were not trained on")
+            if cap == TARGET_CAP:
+                raise Y3DError(f"pad_targets: an image of a recent batch has {n} ground-truth boxes, the assigner kernels take at most {cap} per "
+                               f"image (KITTI's max_objs is 50); its last {n - cap} boxes were not trained on")
+            raise Y3DError(f"pad_targets: an image of a recent batch has {n} ground-truth boxes, the capacity in use is {cap} per image "
+                           f"(the 2D losses' max_boxes); its last {n - cap} boxes were not trained on")
     _OVERFLOW_PENDING[:] = keep
 
 
 def pad_targets(rows, B, width, scale_xy, cap=TARGET_CAP):
     """utils/loss.py:795-810 on the HIP kernel `y3d_pad_targets`: ragged rows (nbox, 1+width) -> (B, cap, width) + the device-side
     largest per-image box count.  The reference sizes the padded tensor with a host-side `counts.max()`; here the capacity is fixed
-    (`cap`, the assigner kernels' limit of 64 rows; KITTI's max_objs is 50, data/datasets/kitti.py:23) and the count stays on the
+    (`cap`: the assigner kernels' limit of 64 rows, KITTI's max_objs is 50, data/datasets/kitti.py:23; or the 2D losses' `max_boxes`) and the count stays on the
     device, so the step has no host synchronisation.  An image with more than `cap` boxes (crowded 2D data, mosaics) is NOT trained
     on silently truncated targets: the true count travels to a pinned host word asynchronously and `check_target_overflow` raises
     (ADVICE round 2).  -> (gt (B, cap, width) fp32, n_used (1,) int32: min(largest count, cap))"""
@@ -551,7 +564,8 @@ class Loss2dFn(torch.autograd.Function):
         c_gsw = (ctypes.c_int64 * nl)(*[no] * nl)
         c_H, c_W = (ctypes.c_int * nl)(*Hs), (ctypes.c_int * nl)(*Ws)
         c_st = (ctypes.c_float * nl)(*strides)
-        nsc = L.tal3d_scratch_floats(B, n, A, topk)
+        crowded = n > TARGET_CAP  # more rows than the dense assigner takes (`max_boxes`): the route without (B, n, A) planes
+        nsc = L.tal2d_scratch_floats(B, n, A, topk) if crowded else L.tal3d_scratch_floats(B, n, A, topk)
         if nsc < 0:
             raise Y3DError("Loss2dFn: assignment scratch exceeds 2^31 floats")
         scratch = torch.empty(nsc, dtype=torch.float32, device=dev)
@@ -559,8 +573,9 @@ class Loss2dFn(torch.autograd.Function):
         gi = torch.empty(B, A, dtype=torch.int32, device=dev)
         ts = torch.empty(B, A, nc, dtype=torch.float32, device=dev)
         scal = torch.empty(2, dtype=torch.float32, device=dev)
-        L.tal2d_assign(dt, nl, c_maps, c_psw, c_H, c_W, c_st, B, nc, gt.data_ptr(), n, topk, alpha, beta, scratch.data_ptr(), fg.data_ptr(),
-                       gi.data_ptr(), ts.data_ptr(), scal.data_ptr(), n_used.data_ptr() if n_used is not None else None, st)
+        assign = L.tal2d_assign_crowded if crowded else L.tal2d_assign
+        assign(dt, nl, c_maps, c_psw, c_H, c_W, c_st, B, nc, gt.data_ptr(), n, topk, alpha, beta, scratch.data_ptr(), fg.data_ptr(),
+               gi.data_ptr(), ts.data_ptr(), scal.data_ptr(), n_used.data_ptr() if n_used is not None else None, st)
         nblk = (B * A + 255) // 256
         part = torch.empty(nblk * 3, dtype=torch.float32, device=dev)
         items = torch.empty(3, dtype=torch.float32, device=dev)
@@ -580,11 +595,14 @@ class Loss2dFn(torch.autograd.Function):
 
 
 class v8DetectionLoss:
-    """utils/loss.py:157-257 (+BboxLoss :73-113) on the HIP kernels of tal_loss2d.hip"""
+    """utils/loss.py:157-257 (+BboxLoss :73-113) on the HIP kernels of tal_loss2d.hip.
+    max_boxes (or `model.args.max_boxes`): ground-truth rows per image.  None: 64 and the dense assigner; a multiple of 64 in 128..512
+    (crowded 2D data, mosaics): the targets are padded to that many rows and the assignment takes the crowded route."""
 
-    def __init__(self, model, tal_topk=10):
+    def __init__(self, model, tal_topk=10, max_boxes=None):
         m = model.model[-1]
         self.hyp = model.args
+        self.max_boxes = check_max_boxes(max_boxes if max_boxes is not None else getattr(model.args, "max_boxes", None))
         self.stride = [float(s) for s in m.stride]
         self.nc, self.no, self.reg_max = m.nc, m.no, m.reg_max
         if self.reg_max != 16:
@@ -596,7 +614,7 @@ class v8DetectionLoss:
         rows = torch.cat((batch["batch_idx"].view(-1, 1), batch["cls"].view(-1, 1), batch["bboxes"]), 1).to(dev).float()
         if rows.shape[0] == 0:
             return None
-        return pad_targets(rows, B, 5, (W * self.stride[0], H * self.stride[0]))
+        return pad_targets(rows, B, 5, (W * self.stride[0], H * self.stride[0]), cap=self.max_boxes or TARGET_CAP)
 
     def __call__(self, preds, batch, targets=None):
         feats = preds[1] if isinstance(preds, tuple) else preds
@@ -625,9 +643,10 @@ class v8DetectionLoss:
 class v10DetectLoss:
     """utils/loss.py:727-737"""
 
-    def __init__(self, model):
-        self.one2many = v8DetectionLoss(model, tal_topk=10)
-        self.one2one = v8DetectionLoss(model, tal_topk=1)
+    def __init__(self, model, max_boxes=None):
+        self.one2many = v8DetectionLoss(model, tal_topk=10, max_boxes=max_boxes)
+        self.one2one = v8DetectionLoss(model, tal_topk=1, max_boxes=max_boxes)
+        self.max_boxes = self.one2many.max_boxes
 
     def __call__(self, preds, batch):
         f0 = preds["one2many"][1] if isinstance(preds["one2many"], tuple) else preds["one2many"]
