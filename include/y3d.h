@@ -457,6 +457,20 @@ int y3d_kitti_encode_labels(const double* rec, const int* img_i, const double* i
                             double* bboxes, float* center_2d, float* size_2d, double* center_3d, double* size_3d, double* depth,
                             int64_t* heading_bin, double* heading_res, float* batch_idx, int* counts, double* calib, double* ratio_pad,
                             void* stream);
+/* Input pipeline, label side of WaymoDataset.__getitem__ (data/datasets/waymo.py:186-290, load_object :292-372; dataset = 0) and
+ * Omni3Dataset.__getitem__ (data/datasets/omni3d.py:175-279, load_object :281-352; dataset = 1) with their collate_fn, one workgroup
+ * per image (json3d_labels.hip), in the plan and the output layout of y3d_kitti_encode_labels.  rec (N, 24) float64 object records,
+ * images back to back, each image's primary objects then its mixup partner's, in annotation order: [cls id (0 .. n_cls-1, -1 for any
+ * other category), x1, y1, x2, y2 (float32 values), h, w, l, pos x, y, z (the bottom-face centre), ry, num_lidar, behind_camera,
+ * valid3D, depth_error, truncation, visibility, 0 ...] (the five after num_lidar are read for Omni3D only).  img_i (B, 7) and img_f
+ * (B, 19) as y3d_kitti_encode_labels takes them, but P2 holds the float64 calibration of the JSON when the image is not mirrored and
+ * the float32 values of Calibration.flip when it is.  Waymo's 2D box is recomputed from the projected corners of the 3D box
+ * (recompute_bbox_2d, waymo.py:365-372), Omni3D's is the annotated one; mean_size (n_cls, 3) is the dataset's table. */
+int y3d_json3d_encode_labels(const double* rec, const int* img_i, const double* img_f, int B, int dataset, int out_w, int out_h,
+                             double min_depth, double max_depth, int use_camera_dis, const double* mean_size, int n_cls, int max_objs,
+                             int64_t* cls, double* bboxes, float* center_2d, float* size_2d, double* center_3d, double* size_3d,
+                             double* depth, int64_t* heading_bin, double* heading_res, float* batch_idx, int* counts, double* calib,
+                             double* ratio_pad, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * KITTI AP evaluation (kitti_eval.hip) — the evaluator behind KITTIDataset.get_stats (data/datasets/kitti.py:444-450):
