@@ -471,6 +471,26 @@ int y3d_json3d_encode_labels(const double* rec, const int* img_i, const double* 
                              int64_t* cls, double* bboxes, float* center_2d, float* size_2d, double* center_3d, double* size_3d,
                              double* depth, int64_t* heading_bin, double* heading_res, float* batch_idx, int* counts, double* calib,
                              double* ratio_pad, void* stream);
+/* 2D input pipeline, image side of YOLODataset.__getitem__ (data/base.py load_image :147-182; data/augment.py Mosaic._mosaic4
+ * :208-242, RandomPerspective :384-435, MixUp :337-344, RandomHSV :605-624, RandomFlip :651-681, Format._format_img :950-957) for a
+ * batch, one launch (yolo2d_batch.hip states the arithmetic; float64, + - * / and floor only).  src: DEVICE table of n_src device
+ * pointers to decoded (H, W, 3) uint8 images.  rec_i (B, 112) int32: two layers (the sample, its MixUp partner) of [tiles, canvas
+ * side, 4 x (src index, h0, w0, resized h, w, x1a, y1a, x2a, y2a, padw, padh, 0)], then at 100: flipud, fliplr, bgr, hsv, mix.
+ * rec_f (B, 16) float64: the two layers' inverse matrices (2x3, output -> canvas), the MixUp ratio r.  lut (B, 3, 256) uint8: the
+ * hue / saturation / value tables.  imgsz: a multiple of 4.  mode 0: out (B, 3, imgsz, imgsz) fp32 in [0, 1]; mode 1: out
+ * (B, imgsz, imgsz, 3) uint8 (feeds y3d_stem_im2col_u8). */
+int y3d_yolo2d_image_aug(const unsigned char* const* src, int n_src, const int* rec_i, const double* rec_f, const unsigned char* lut, int B,
+                         int imgsz, int mode, void* out, void* stream);
+/* 2D input pipeline, label side of the same sample (Mosaic._update_labels / _cat_labels :292-323, RandomPerspective.apply_bboxes /
+ * box_candidates :437-460, :562-581, the flips, Format) and collate_fn (data/dataset.py:206-223), one workgroup per image.  rec
+ * (n_rec, 5) float32 label rows [cls, x, y, w, h] normalised.  lab_i (B, 20) int32: (first row, rows) of the eight tiles (mosaic tiles
+ * 0..3, then the partner's), the two layers' flags (bit 0 present, bit 1 mosaic: canvas clip + zero-area filter, bit 2 training: warp +
+ * box_candidates + flips), flips (bit 0 up-down, bit 1 left-right), 0.  lab_f (B, 48) float32: (w, h, padw, padh) of the eight tiles,
+ * then per layer (M 2x3, scale, 0).  Outputs in a static layout of cap (64, 128 .. 512) rows per image, survivors first in the
+ * reference's order, the rest batch_idx = -1 and zeros: cls (B*cap) f32, bboxes (B*cap, 4) f32 xywh normalised, batch_idx f32;
+ * counts (B) int32 = the true number of survivors, which may exceed cap (the surplus is not stored). */
+int y3d_yolo2d_encode_labels(const float* rec, int n_rec, const int* lab_i, const float* lab_f, int B, int imgsz, int cap, float* cls,
+                             float* bboxes, float* batch_idx, int* counts, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * KITTI AP evaluation (kitti_eval.hip) — the evaluator behind KITTIDataset.get_stats (data/datasets/kitti.py:444-450):

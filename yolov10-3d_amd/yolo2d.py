@@ -1,0 +1,481 @@
+"""2D training batches on the device — the data path of the six `v10` models.
+
+Mirrors `YOLODataset.__getitem__` + `collate_fn` of the reference for detection: `load_image` and its mosaic buffer
+(data/base.py:147-182, 251-266), `v8_transforms` (data/augment.py:973-1007: Mosaic, RandomPerspective, MixUp, RandomHSV, the two
+RandomFlip), `Format` (:915-957) and `collate_fn` (data/dataset.py:206-223).  The plan is that of `kitti.py` / `json3d.py`: the host
+reads the files and replays every random draw in the reference's order (`sample_augment`), one launch builds the images
+(`y3d_yolo2d_image_aug`) and one the labels (`y3d_yolo2d_encode_labels`, csrc/yolo2d_batch.hip), in a static layout of
+`max_boxes or 64` rows per image that `v10DetectLoss.targets` and `GraphedTrainStep` take unchanged.
+
+Labels follow the reference's float32 arithmetic box by box.  Images follow the arithmetic stated in the kernel's header and in
+tests/yolo2d_ref.py (float64 bilinear resize / warp, a float HSV round trip); that is not OpenCV's fixed-point interpolation nor its
+integer HSV tables, and how far the two lie apart has not been measured (tools/make_golden_yolo2d.py --cv2).
+
+Not covered (each raises Y3DError where it can be asked for): rect=True, segments / keypoints / obb, copy_paste > 0,
+perspective != 0, Albumentations, the RNG streams of multi-worker loaders, the mosaic 3 / 9 grids.
+"""
+from __future__ import annotations
+
+import math
+import random
+
+import torch
+
+from . import loss as _loss
+from . import ops
+from ._lib import Y3DError, lib
+
+IMG_FORMATS = {"bmp", "dng", "jpeg", "jpg", "mpo", "png", "tif", "tiff", "webp", "pfm"}  # data/utils.py
+# the 2D data hyper-parameters of cfg/default.yaml
+DATA_ARGS = dict(mosaic=1.0, mixup=0.5, degrees=0.0, translate=0.1, scale=0.4, shear=0.0, perspective=0.0, hsv_h=0.015, hsv_s=0.7,
+                 hsv_v=0.4, flipud=0.0, fliplr=0.5, bgr=0.0, copy_paste=0.0)
+# Refusal-only arguments.  They are no hyper-parameters of default.yaml: they name what a caller of the reference can ask for elsewhere
+# (Mosaic(n=...), an installed albumentations, DataLoader(num_workers=...)) and this module does not do.  Any other value raises.
+_UNSUPPORTED = dict(mosaic_grid=4, albumentations=False, workers=0)
+BASE_CAP = 64
+# record widths of the two kernels (include/y3d.h)
+_TILE, _LAYER, _REC_I, _REC_F, _LAB_I, _LAB_F = 12, 50, 112, 16, 20, 48
+
+
+def data_args(**over):
+    """DATA_ARGS with overrides, as the attribute namespace sample_augment / build_batch read.  Besides the fourteen hyper-parameters it
+    carries three refusal-only arguments, `mosaic_grid=4`, `albumentations=False` and `workers=0`: they exist so that a request for a
+    3 / 9 mosaic, for Albumentations or for a multi-worker loader's RNG streams is refused with Y3DError and not silently ignored."""
+    from types import SimpleNamespace
+    bad = set(over) - set(DATA_ARGS) - set(_UNSUPPORTED)
+    if bad:
+        raise ValueError(f"data_args: unknown argument(s) {sorted(bad)}")
+    return SimpleNamespace(**{**DATA_ARGS, **_UNSUPPORTED, **over})
+
+
+def _check_args(args):
+    if getattr(args, "copy_paste", 0.0):
+        raise Y3DError("yolo2d: copy_paste > 0 needs segments, which are not supported")
+    if getattr(args, "perspective", 0.0):
+        raise Y3DError("yolo2d: perspective != 0 (warpPerspective) is not supported")
+    if getattr(args, "mosaic_grid", 4) != 4:
+        raise Y3DError("yolo2d: only the 2 x 2 mosaic is supported (no 3 / 9 grids)")
+    if getattr(args, "albumentations", False):
+        raise Y3DError("yolo2d: Albumentations transforms are not supported")
+    if getattr(args, "workers", 0):
+        raise Y3DError("yolo2d: the draws replay a workers=0 loader; multi-worker RNG streams are not supported")
+
+
+def img2label_path(path):
+    """data/utils.py img2label_paths: the last /images/ becomes /labels/, the extension .txt"""
+    import os
+    sa, sb = f"{os.sep}images{os.sep}", f"{os.sep}labels{os.sep}"
+    return sb.join(path.rsplit(sa, 1)).rsplit(".", 1)[0] + ".txt"
+
+
+def read_labels(path):
+    """A YOLO txt label file -> (n, 5) float32 rows [cls, x, y, w, h] (normalised xywh); a missing or empty file is a background image"""
+    import os
+    import numpy as np
+    if not os.path.isfile(path):
+        return np.zeros((0, 5), np.float32)
+    rows = [ln.split() for ln in open(path).read().strip().splitlines() if len(ln)]
+    if not rows:
+        return np.zeros((0, 5), np.float32)
+    if any(len(r) != 5 for r in rows):
+        raise Y3DError(f"yolo2d: {path}: rows of {sorted({len(r) for r in rows})} columns; segments / keypoints / obb labels are not supported")
+    lb = np.array(rows, dtype=np.float32)
+    if lb.min() < 0 or lb[:, 1:].max() > 1:
+        raise Y3DError(f"yolo2d: {path}: negative or non-normalised label values")
+    return lb
+
+
+class Split:
+    """The images of a directory (recursive) or of list files, sorted as the reference sorts them, with their label rows, their sizes
+    and the reference's `buffer` of recently loaded indices (`load_image`: append on load, drop the oldest at
+    min(ni, batch * 8, 1000)), from which Mosaic picks its three other tiles."""
+
+    def __init__(self, img_dir_or_list, imgsz=640, batch=16, augment=True, rect=False, task="detect"):
+        import glob
+        import os
+        from pathlib import Path
+        if rect:
+            raise Y3DError("yolo2d: rect=True (rectangular batches) is not supported")
+        if task != "detect":
+            raise Y3DError(f"yolo2d: task {task!r}: segments / keypoints / obb are not supported")
+        if int(imgsz) % 4 or int(imgsz) < 4:
+            raise Y3DError(f"yolo2d: imgsz {imgsz} must be a multiple of 4")
+        f = []
+        for p in img_dir_or_list if isinstance(img_dir_or_list, (list, tuple)) else [img_dir_or_list]:
+            p = Path(p)
+            if p.is_dir():
+                f += glob.glob(str(p / "**" / "*.*"), recursive=True)
+            elif p.is_file():
+                parent = str(p.parent) + os.sep
+                f += [x.replace("./", parent) if x.startswith("./") else x for x in open(p).read().strip().splitlines()]
+            else:
+                raise FileNotFoundError(f"{p} does not exist")
+        self.im_files = sorted(x.replace("/", os.sep) for x in f if x.split(".")[-1].lower() in IMG_FORMATS)
+        if not self.im_files:
+            raise FileNotFoundError(f"No images found in {img_dir_or_list}")
+        self.label_files = [img2label_path(x) for x in self.im_files]
+        self.labels = [read_labels(x) for x in self.label_files]
+        self.ni = len(self.im_files)
+        self.imgsz, self.batch, self.augment = int(imgsz), int(batch), bool(augment)
+        self.buffer = []
+        self.max_buffer_length = min((self.ni, self.batch * 8, 1000)) if self.augment else 0
+        self._held = set()  # indices whose resized image the reference holds in `ims`: loading them again does not touch the buffer
+        self._hw0 = {}
+
+    def __len__(self):
+        return self.ni
+
+    def size(self, i):
+        """(h0, w0) of image i, from the file header"""
+        if i not in self._hw0:
+            from PIL import Image
+            with Image.open(self.im_files[i]) as im:
+                w, h = im.size
+                if im.getexif().get(0x0112, 1) in (5, 6, 7, 8):  # EXIF orientations that transpose: cv2.imread applies them
+                    w, h = h, w
+                self._hw0[i] = (h, w)
+        return self._hw0[i]
+
+    def load(self, i):
+        """`load_image` without the pixels: ((h0, w0), (h, w) after the resize to long side imgsz), and the buffer update"""
+        h0, w0 = self.size(i)
+        r = self.imgsz / max(h0, w0)
+        h, w = (h0, w0) if r == 1 else (min(math.ceil(h0 * r), self.imgsz), min(math.ceil(w0 * r), self.imgsz))
+        if i not in self._held and self.augment:
+            self._held.add(i)
+            self.buffer.append(i)
+            if len(self.buffer) >= self.max_buffer_length:
+                self._held.discard(self.buffer.pop(0))
+        return (h0, w0), (h, w)
+
+    def decode(self, i, device):
+        """image i as a (h0, w0, 3) uint8 RGB tensor on `device`, its EXIF orientation applied as cv2.imread applies it"""
+        import numpy as np
+        from PIL import Image, ImageOps
+        with Image.open(self.im_files[i]) as im:
+            return torch.from_numpy(np.array(ImageOps.exif_transpose(im).convert("RGB"))).to(device)
+
+
+def rotation_matrix_2d(angle, scale):
+    """cv2.getRotationMatrix2D(angle=angle, center=(0, 0), scale=scale) in its closed form -> (2, 3) float64"""
+    import numpy as np
+    a = angle * math.pi / 180
+    alpha, beta = math.cos(a) * scale, math.sin(a) * scale
+    return np.array([[alpha, beta, (1 - alpha) * 0.0 - beta * 0.0], [-beta, alpha, beta * 0.0 + (1 - alpha) * 0.0]], np.float64)
+
+
+def invert_affine(M):
+    """The inverse cv2.warpAffine computes of a forward 2x3 map, in float64 -> (6,) output -> source"""
+    import numpy as np
+    m = np.asarray(M, np.float64)[:2].reshape(6).copy()
+    D = m[0] * m[4] - m[1] * m[3]
+    D = 1.0 / D if D != 0 else 0.0
+    A11, A22 = m[4] * D, m[0] * D
+    m[0] = A11
+    m[1] *= -D
+    m[3] *= -D
+    m[4] = A22
+    b1 = -m[0] * m[2] - m[1] * m[5]
+    b2 = -m[3] * m[2] - m[4] * m[5]
+    m[2], m[5] = b1, b2
+    return m
+
+
+def _pre_transform(split, index, hw, args):
+    """`pre_transform` of v8_transforms for an image already loaded: Mosaic (or, when its draw misses, RandomPerspective's LetterBox),
+    then the eight `random.uniform` of `affine_transform` (all drawn, also at zero range) and M = T @ S @ R @ P @ C in float32"""
+    import numpy as np
+    s = split.imgsz
+    rec = {"index": int(index), "p_mosaic": random.uniform(0, 1)}
+    rec["mosaic"] = not (rec["p_mosaic"] > args.mosaic)
+    tiles = []
+    if rec["mosaic"]:
+        others = random.choices(list(split.buffer), k=3)
+        frames = [index] + others
+        sizes = [hw] + [split.load(i) for i in others]
+        border = (-s // 2, -s // 2)
+        yc_u, xc_u = (random.uniform(-x, 2 * s + x) for x in border)  # y first, as the reference's generator draws them
+        yc, xc = int(yc_u), int(xc_u)
+        for i, (fi, ((h0, w0), (h, w))) in enumerate(zip(frames, sizes)):
+            if i == 0:
+                x1a, y1a, x2a, y2a = max(xc - w, 0), max(yc - h, 0), xc, yc
+                x1b, y1b = w - (x2a - x1a), h - (y2a - y1a)
+            elif i == 1:
+                x1a, y1a, x2a, y2a = xc, max(yc - h, 0), min(xc + w, s * 2), yc
+                x1b, y1b = 0, h - (y2a - y1a)
+            elif i == 2:
+                x1a, y1a, x2a, y2a = max(xc - w, 0), yc, xc, min(s * 2, yc + h)
+                x1b, y1b = w - (x2a - x1a), 0
+            else:
+                x1a, y1a, x2a, y2a = xc, yc, min(xc + w, s * 2), min(s * 2, yc + h)
+                x1b, y1b = 0, 0
+            padw, padh = x1a - x1b, y1a - y1b
+            tiles.append(dict(frame=int(fi), h0=h0, w0=w0, h=h, w=w, x1a=x1a, y1a=y1a, x2a=x2a, y2a=y2a, padw=padw, padh=padh,
+                              lab_padw=float(padw), lab_padh=float(padh)))
+        rec.update(others=[int(i) for i in others], yc=yc, xc=xc, yc_u=yc_u, xc_u=xc_u, canvas=2 * s)
+    else:
+        (h0, w0), (h, w) = hw
+        r = min(s / h, s / w)
+        if r != 1.0:
+            raise Y3DError(f"yolo2d: letter-box ratio {r} after load_image's resize (expected 1)")
+        dw, dh = (s - w) / 2, (s - h) / 2
+        top, left = int(round(dh - 0.1)), int(round(dw - 0.1))
+        tiles.append(dict(frame=int(index), h0=h0, w0=w0, h=h, w=w, x1a=left, y1a=top, x2a=left + w, y2a=top + h, padw=left, padh=top,
+                          lab_padw=float(dw), lab_padh=float(dh)))
+        rec.update(others=[], yc=-1, xc=-1, yc_u=-1.0, xc_u=-1.0, canvas=s)
+    rec["tiles"] = tiles
+    C = np.eye(3, dtype=np.float32)
+    C[0, 2] = -rec["canvas"] / 2
+    C[1, 2] = -rec["canvas"] / 2
+    P = np.eye(3, dtype=np.float32)
+    d = [random.uniform(-args.perspective, args.perspective), random.uniform(-args.perspective, args.perspective)]
+    P[2, 0], P[2, 1] = d[0], d[1]
+    R = np.eye(3, dtype=np.float32)
+    a = random.uniform(-args.degrees, args.degrees)
+    sc = random.uniform(1 - args.scale, 1 + args.scale)
+    R[:2] = rotation_matrix_2d(a, sc)
+    S = np.eye(3, dtype=np.float32)
+    d += [a, sc, random.uniform(-args.shear, args.shear), random.uniform(-args.shear, args.shear)]
+    S[0, 1] = math.tan(d[4] * math.pi / 180)
+    S[1, 0] = math.tan(d[5] * math.pi / 180)
+    T = np.eye(3, dtype=np.float32)
+    d += [random.uniform(0.5 - args.translate, 0.5 + args.translate), random.uniform(0.5 - args.translate, 0.5 + args.translate)]
+    T[0, 2] = d[6] * s
+    T[1, 2] = d[7] * s
+    M = T @ S @ R @ P @ C
+    rec.update(affine=[float(v) for v in d], scale=float(sc), M=M, M_inv=invert_affine(M), warp=True)
+    return rec
+
+
+def _letterbox_only(split, index, hw):
+    """the `val` transform: LetterBox(scaleup=False), no warp"""
+    import numpy as np
+    s = split.imgsz
+    (h0, w0), (h, w) = hw
+    r = min(min(s / h, s / w), 1.0)
+    if r != 1.0:
+        raise Y3DError(f"yolo2d: letter-box ratio {r} after load_image's resize (expected 1)")
+    dw, dh = (s - w) / 2, (s - h) / 2
+    top, left = int(round(dh - 0.1)), int(round(dw - 0.1))
+    tile = dict(frame=int(index), h0=h0, w0=w0, h=h, w=w, x1a=left, y1a=top, x2a=left + w, y2a=top + h, padw=left, padh=top,
+                lab_padw=float(dw), lab_padh=float(dh))
+    return dict(index=int(index), p_mosaic=-1.0, mosaic=False, others=[], yc=-1, xc=-1, yc_u=-1.0, xc_u=-1.0, canvas=s, tiles=[tile], affine=[], scale=1.0,
+                M=np.eye(3, dtype=np.float32), M_inv=np.array([1.0, 0, 0, 0, 1.0, 0]), warp=False)
+
+
+def sample_augment(split, index, args, mode="train"):
+    """Every random decision of `dataset[index]` in the reference's order, for a `workers=0` loader seeded through `random.seed` and
+    `np.random.seed`.  From `random`: the mosaic probability, `choices(buffer, k=3)`, yc, xc, the eight uniforms of `affine_transform`
+    (two perspective, angle, scale, two shear, two translate), the MixUp probability and its `randint`, then — after the partner's own
+    `pre_transform` — the two flips and Format's bgr draw; from `np.random`: `beta(32, 32)` and the HSV `uniform(-1, 1, 3)`.
+    -> a plain dict: `pre` (and `pre2` for the MixUp partner): index, p_mosaic, mosaic, others, yc, xc, canvas, tiles (frame, sizes,
+    canvas rectangle, pads), affine (the eight draws), scale, M (3, 3) float32, M_inv (6,) float64; p_mixup, mix, partner, r; hsv_u
+    (3,), hsv_gain (3,) or None; p_flipud, flipud, p_fliplr, fliplr; p_bgr, rgb."""
+    import numpy as np
+    _check_args(args)
+    if mode not in ("train", "val"):
+        raise ValueError("mode must be 'train' or 'val'")
+    index = int(index)
+    if not 0 <= index < split.ni:
+        raise IndexError(f"yolo2d: index {index} of {split.ni} images")
+    if (mode == "train") != split.augment:
+        raise Y3DError(f"yolo2d: mode {mode!r} needs a Split built with augment={mode == 'train'}")
+    hw = split.load(index)
+    out = dict(mode=mode, index=index, pre2=None, p_mixup=-1.0, mix=False, partner=-1, r=1.0, hsv_u=None, hsv_gain=None, p_flipud=-1.0,
+               flipud=False, p_fliplr=-1.0, fliplr=False)
+    if mode == "val":
+        out["pre"] = _letterbox_only(split, index, hw)
+    else:
+        out["pre"] = _pre_transform(split, index, hw, args)
+        out["p_mixup"] = random.uniform(0, 1)
+        out["mix"] = not (out["p_mixup"] > args.mixup)
+        if out["mix"]:
+            out["partner"] = random.randint(0, split.ni - 1)
+            out["pre2"] = _pre_transform(split, out["partner"], split.load(out["partner"]), args)
+            out["r"] = float(np.random.beta(32.0, 32.0))
+        if args.hsv_h or args.hsv_s or args.hsv_v:
+            out["hsv_u"] = np.random.uniform(-1, 1, 3)
+            out["hsv_gain"] = out["hsv_u"] * [args.hsv_h, args.hsv_s, args.hsv_v] + 1
+        out["p_flipud"] = random.random()
+        out["flipud"] = out["p_flipud"] < args.flipud
+        out["p_fliplr"] = random.random()
+        out["fliplr"] = out["p_fliplr"] < args.fliplr
+    out["p_bgr"] = random.uniform(0, 1)
+    out["rgb"] = out["p_bgr"] > (args.bgr if mode == "train" else 0.0)
+    return out
+
+
+def hsv_luts(gain):
+    """The three tables of RandomHSV (augment.py:617-620) for gains r (3,) float64 -> (3, 256) uint8"""
+    import numpy as np
+    r = np.asarray(gain, np.float64)
+    x = np.arange(0, 256, dtype=r.dtype)
+    return np.stack([((x * r[0]) % 180).astype(np.uint8), np.clip(x * r[1], 0, 255).astype(np.uint8), np.clip(x * r[2], 0, 255).astype(np.uint8)])
+
+
+def image_records(samples, slot):
+    """sample_augment's records -> (rec_i (B, 112) int32, rec_f (B, 16) float64, lut (B, 3, 256) uint8) of y3d_yolo2d_image_aug;
+    slot: frame index -> position in the pointer table"""
+    import numpy as np
+    B = len(samples)
+    ri, rf, lut = np.zeros((B, _REC_I), np.int32), np.zeros((B, _REC_F), np.float64), np.zeros((B, 3, 256), np.uint8)
+    for b, s in enumerate(samples):
+        for l, pre in enumerate((s["pre"], s["pre2"])):
+            if pre is None:
+                continue
+            o = l * _LAYER
+            ri[b, o], ri[b, o + 1] = len(pre["tiles"]), pre["canvas"]
+            for k, t in enumerate(pre["tiles"]):
+                ri[b, o + 2 + k * _TILE:o + 2 + k * _TILE + 11] = (slot[t["frame"]], t["h0"], t["w0"], t["h"], t["w"], t["x1a"], t["y1a"],
+                                                                   t["x2a"], t["y2a"], t["padw"], t["padh"])
+            rf[b, l * 6:l * 6 + 6] = pre["M_inv"]
+        hsv = s["hsv_gain"] is not None
+        ri[b, 100:105] = (int(s["flipud"]), int(s["fliplr"]), int(not s["rgb"]), int(hsv), int(s["pre2"] is not None))
+        rf[b, 12] = s["r"]
+        if hsv:
+            lut[b] = hsv_luts(s["hsv_gain"])
+    return ri, rf, lut
+
+
+def label_records(split, samples, rec_start):
+    """sample_augment's records -> (lab_i (B, 20) int32, lab_f (B, 48) float32) of y3d_yolo2d_encode_labels; rec_start[frame] = first
+    row of the frame's labels in the uploaded label table"""
+    import numpy as np
+    B = len(samples)
+    li, lf = np.zeros((B, _LAB_I), np.int32), np.zeros((B, _LAB_F), np.float32)
+    for b, s in enumerate(samples):
+        for l, pre in enumerate((s["pre"], s["pre2"])):
+            if pre is None:
+                continue
+            for k, t in enumerate(pre["tiles"]):
+                q = l * 4 + k
+                li[b, 2 * q], li[b, 2 * q + 1] = rec_start[t["frame"]], len(split.labels[t["frame"]])
+                lf[b, 4 * q:4 * q + 4] = (t["w"], t["h"], t["lab_padw"], t["lab_padh"])
+            li[b, 16 + l] = 1 | (2 if pre["mosaic"] else 0) | (4 if pre["warp"] else 0)
+            lf[b, 32 + l * 8:32 + l * 8 + 6] = np.asarray(pre["M"], np.float32)[:2].reshape(6)
+            lf[b, 32 + l * 8 + 6] = pre["scale"]
+        li[b, 18] = int(s["flipud"]) | (int(s["fliplr"]) << 1)
+    return li, lf
+
+
+def _up(a, device):
+    import numpy as np
+    return torch.from_numpy(np.ascontiguousarray(a)).to(device)
+
+
+def pack_images(imgs, rec_i, rec_f, lut, imgsz, device):
+    """Host side of augment_images: the decoded (H, W, 3) uint8 device images of the pointer table and the three record arrays ->
+    dict of device tensors (one upload each)"""
+    if torch.device(device).type != "cuda":
+        raise Y3DError("pack_images: the images are built on a HIP device (no host fallback)")
+    if not imgs or any((not t.is_cuda) or t.dtype != torch.uint8 or t.dim() != 3 or t.shape[2] != 3 for t in imgs):
+        raise Y3DError("pack_images: images must be (H, W, 3) uint8 tensors on a HIP device")
+    imgs = [t.contiguous() for t in imgs]
+    B = rec_i.shape[0]
+    if rec_i.shape != (B, _REC_I) or rec_f.shape != (B, _REC_F) or lut.shape != (B, 3, 256):
+        raise Y3DError("pack_images: record arrays of the wrong shape")
+    for b in range(B):  # every tile must name an image of the table, with that image's size
+        for l in range(2):
+            for k in range(int(rec_i[b, l * _LAYER])):
+                t = rec_i[b, l * _LAYER + 2 + k * _TILE:l * _LAYER + 2 + (k + 1) * _TILE]
+                if not 0 <= t[0] < len(imgs) or tuple(imgs[t[0]].shape[:2]) != (int(t[1]), int(t[2])):
+                    raise Y3DError("pack_images: a tile record does not match its image")
+    src = torch.tensor([t.data_ptr() for t in imgs], dtype=torch.int64).to(device)
+    return {"imgs": imgs, "src": src, "rec_i": _up(rec_i, device), "rec_f": _up(rec_f, device), "lut": _up(lut, device), "imgsz": int(imgsz)}
+
+
+def augment_images(packed, mode="uint8"):
+    """The image work of B samples, one HIP launch, no host synchronisation (capturable): allocates the output and launches.
+    mode "uint8": (B, S, S, 3) uint8 for the stem (`y3d_stem_im2col_u8` divides by 255); "float": (B, 3, S, S) float32 in [0, 1]."""
+    ri = packed["rec_i"]
+    if not ri.is_cuda:
+        raise Y3DError("augment_images: the packed records must live on a HIP device (no host fallback)")
+    B, S, dev = ri.shape[0], packed["imgsz"], ri.device
+    if mode == "float":
+        out = torch.empty(B, 3, S, S, dtype=torch.float32, device=dev)
+    elif mode == "uint8":
+        out = torch.empty(B, S, S, 3, dtype=torch.uint8, device=dev)
+    else:
+        raise ValueError("mode must be 'float' or 'uint8'")
+    lib().yolo2d_image_aug(packed["src"].data_ptr(), packed["src"].shape[0], ri.data_ptr(), packed["rec_f"].data_ptr(), packed["lut"].data_ptr(),
+                           B, S, 0 if mode == "float" else 1, out.data_ptr(), ops.stream())
+    return out
+
+
+def pack_labels(label_rows, lab_i, lab_f, device):
+    """Host side of encode_labels: the (n, 5) float32 label table and the two record arrays -> dict of device tensors"""
+    import numpy as np
+    if torch.device(device).type != "cuda":
+        raise Y3DError("pack_labels: the label encoder runs on a HIP device (no host fallback)")
+    rows = np.asarray(label_rows, np.float32).reshape(-1, 5)
+    n = len(rows)
+    if lab_i.shape[1:] != (_LAB_I,) or lab_f.shape != (lab_i.shape[0], _LAB_F):
+        raise Y3DError("pack_labels: record arrays of the wrong shape")
+    seg = lab_i[:, :16].reshape(-1, 2)
+    if (seg < 0).any() or (seg.sum(1)[seg[:, 1] > 0] > n).any():
+        raise Y3DError("pack_labels: a tile's label rows lie outside the label table")
+    return {"rec": _up(rows if n else np.zeros((1, 5), np.float32), device), "n_rec": n, "lab_i": _up(lab_i, device), "lab_f": _up(lab_f, device)}
+
+
+def encode_labels(packed, imgsz, max_boxes=None):
+    """The label work of B samples + `collate_fn`, one HIP launch, no host synchronisation (capturable).  -> static layout of
+    cap = max_boxes or 64 rows per image: `cls` (B*cap, 1) float32, `bboxes` (B*cap, 4) float32 xywh normalised, `batch_idx` (B*cap)
+    float32 (-1 on unused rows, which are zeros and which `y3d_pad_targets` skips), `counts` (B,) int32: the true number of boxes of
+    each image — one with more than cap keeps its first cap in the reference's order and shows the surplus here."""
+    cap = _loss.check_max_boxes(max_boxes) or BASE_CAP
+    li = packed["lab_i"]
+    if not li.is_cuda or not packed["rec"].is_cuda or not packed["lab_f"].is_cuda:
+        raise Y3DError("encode_labels: the packed labels must live on a HIP device (no host fallback)")
+    B, dev = li.shape[0], li.device
+    o = {"cls": torch.empty(B * cap, 1, dtype=torch.float32, device=dev), "bboxes": torch.empty(B * cap, 4, dtype=torch.float32, device=dev),
+         "batch_idx": torch.empty(B * cap, dtype=torch.float32, device=dev), "counts": torch.empty(B, dtype=torch.int32, device=dev)}
+    lib().yolo2d_encode_labels(packed["rec"].data_ptr(), int(packed["n_rec"]), li.data_ptr(), packed["lab_f"].data_ptr(), B, int(imgsz), cap,
+                               o["cls"].data_ptr(), o["bboxes"].data_ptr(), o["batch_idx"].data_ptr(), o["counts"].data_ptr(), ops.stream())
+    return o
+
+
+def compact_labels(static, counts, max_boxes=None):
+    """Static layout -> the ragged tensors `collate_fn` returns, in its dtypes: cls (N, 1) float32, bboxes (N, 4) float32, batch_idx
+    (N,) float32; an image contributes min(count, cap) rows.  A batch without a single box gives cls of shape (0,), as torch.cat of
+    Format's empty tensors does.  counts: host ints (B,)."""
+    cap = _loss.check_max_boxes(max_boxes) or BASE_CAP
+    dev = static["cls"].device
+    rows = torch.cat([torch.arange(b * cap, b * cap + min(int(c), cap)) for b, c in enumerate(counts)]).to(dev)
+    out = {k: static[k].index_select(0, rows) for k in ("cls", "bboxes", "batch_idx")}
+    if rows.numel() == 0:
+        out["cls"] = out["cls"].reshape(0)
+    return out
+
+
+def build_batch(split, indices, args, device, mode="train", max_boxes=None, compact=False, img_mode="uint8"):
+    """`collate_fn([dataset[i] for i in indices])` of the reference's YOLODataset (task detect) over `split`, with the image and label
+    work on the device.  -> {"img", "cls", "bboxes", "batch_idx", "counts", "im_file", "ori_shape", "resized_shape"}; the per-box keys in
+    encode_labels' static layout, or with compact=True (one read-back of the counts) in collate_fn's ragged shapes.  img_mode
+    "uint8": (B, S, S, 3) uint8 in Format's channel order for the stem; "float": (B, 3, S, S) float32 in [0, 1]."""
+    import numpy as np
+    if torch.device(device).type != "cuda":
+        raise Y3DError("build_batch: the batch is built on a HIP device (no host fallback)")
+    if img_mode not in ("uint8", "float"):
+        raise ValueError("img_mode must be 'uint8' or 'float'")
+    _loss.check_max_boxes(max_boxes)
+    samples = [sample_augment(split, i, args, mode) for i in indices]
+    frames = sorted({t["frame"] for x in samples for pre in (x["pre"], x["pre2"]) if pre is not None for t in pre["tiles"]})
+    slot = {f: n for n, f in enumerate(frames)}
+    imgs = [split.decode(f, device) for f in frames]
+    ri, rf, lut = image_records(samples, slot)
+    img = augment_images(pack_images(imgs, ri, rf, lut, split.imgsz, device), img_mode)
+    rec_start, row = {}, 0
+    for f in frames:
+        rec_start[f] = row
+        row += len(split.labels[f])
+    rows = np.concatenate([split.labels[f] for f in frames])
+    li, lf = label_records(split, samples, rec_start)
+    lab = encode_labels(pack_labels(rows, li, lf, device), split.imgsz, max_boxes)
+    s = split.imgsz
+    batch = {"img": img, "im_file": [split.im_files[x["index"]] for x in samples], "ori_shape": [split.size(x["index"]) for x in samples],
+             "resized_shape": [(s, s) for _ in samples], "counts": lab["counts"]}
+    if compact:
+        batch.update(compact_labels(lab, lab["counts"].tolist(), max_boxes))
+    else:
+        batch.update({k: lab[k] for k in ("cls", "bboxes", "batch_idx")})
+    return batch
