@@ -491,6 +491,29 @@ int y3d_yolo2d_image_aug(const unsigned char* const* src, int n_src, const int* 
  * counts (B) int32 = the true number of survivors, which may exceed cap (the surplus is not stored). */
 int y3d_yolo2d_encode_labels(const float* rec, int n_rec, const int* lab_i, const float* lab_f, int B, int imgsz, int cap, float* cls,
                              float* bboxes, float* batch_idx, int* counts, void* stream);
+/* Rectangular letter-box of decoded images into one (H, W) canvas, H != W allowed (letterbox.hip states the arithmetic): the image side
+ * of a rect=True validation sample (data/base.py load_image :147-182 + data/augment.py LetterBox.__call__ :696-742, Format._format_img
+ * :950-957) and of the predictor's preprocess (engine/predictor.py:115-156).  src_table: DEVICE table of n_src device pointers to
+ * decoded (h0, w0, 3) uint8 images, as y3d_yolo2d_image_aug takes it.  rec (B, 8) int32 = [src index, h0, w0, new_h, new_w, top, left,
+ * swap_rb]: the source resized to (new_h, new_w) (a plain copy when that is (h0, w0)) lands at (top, left), everything else is 114;
+ * swap_rb exchanges channels 0 and 2.  W: a multiple of 4.  mode 0: out (B, 3, H, W) fp32 in [0, 1]; mode 1: out (B, H, W, 3) uint8
+ * (feeds y3d_stem_im2col_u8).  A record whose source index is outside the table or whose sizes are below 1 gives an all-114 image. */
+int y3d_letterbox_image(const unsigned char* const* src_table, int n_src, const int* rec, int B, int H, int W, int mode, void* out,
+                        void* stream);
+/* Label side of a rect=True validation sample: LetterBox._update_labels (data/augment.py:744-750) + Format (:915-948) + collate_fn
+ * (data/dataset.py:206-223), float32, one workgroup per image.  rec (n_rec, 5) float32 label rows [cls, x, y, w, h] normalised; lab_i
+ * (B, 2) int32 = [first row, rows]; lab_f (B, 4) float32 = [w, h, padw, padh]: the resized image's size and the fractional pads dw, dh.
+ * xywh -> xyxy, x (w, h), + (padw, padh), -> xywh, x (1/W, 1/H); no filter.  Outputs in the layout of y3d_yolo2d_encode_labels: cap
+ * (64, 128 .. 512) rows per image in file order, the rest batch_idx = -1 and zeros; counts (B) int32 = the true number of rows. */
+int y3d_letterbox_labels(const float* rec, int n_rec, const int* lab_i, const float* lab_f, int B, int H, int W, int cap, float* cls,
+                         float* bboxes, float* batch_idx, int* counts, void* stream);
+/* The predictor's row work (models/yolov10/predict.py:23-35; utils/ops.py scale_boxes :107-124, clip_boxes :127-145), one workgroup
+ * per image.  preds (B, K, 6) fp32 [x1, y1, x2, y2, conf, cls] in the letter-boxed frame (v10postprocess + xywh2xyxy); meta (B, 5) fp32
+ * = [h0, w0, gain, padw, padh].  A row is kept when conf > `conf` (strict) and, when n_cls > 0, its class equals one of classes (n_cls)
+ * int32 (NULL when n_cls = 0).  Kept rows: x = (x - padw) / gain clipped to [0, w0], y = (y - padh) / gain clipped to [0, h0], fp32 with
+ * IEEE division.  out (B, K, 6): the kept rows first, in input order, the rest zeros (out must not be preds); counts (B) int32. */
+int y3d_predict_rows(const float* preds, const float* meta, float conf, const int* classes, int n_cls, int B, int K, float* out, int* counts,
+                     void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * KITTI AP evaluation (kitti_eval.hip) — the evaluator behind KITTIDataset.get_stats (data/datasets/kitti.py:444-450):

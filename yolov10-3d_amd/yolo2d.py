@@ -11,7 +11,12 @@ Labels follow the reference's float32 arithmetic box by box.  Images follow the 
 tests/yolo2d_ref.py (float64 bilinear resize / warp, a float HSV round trip); that is not OpenCV's fixed-point interpolation nor its
 integer HSV tables, and how far the two lie apart has not been measured (tools/make_golden_yolo2d.py --cv2).
 
-Not covered (each raises Y3DError where it can be asked for): rect=True, segments / keypoints / obb, copy_paste > 0,
+Rectangular validation batches (the validator's `rect=True` dataset: `set_rectangle`, data/base.py:226-249, and `LetterBox` with
+`rect_shape`, data/augment.py:696-750) are a class of their own, `RectSplit`: `build_batch(rect_split, ...)` letter-boxes each batch into
+its own stride-multiple (H, W) canvas (`y3d_letterbox_image`, `y3d_letterbox_labels`, csrc/letterbox.hip) and returns the `ratio_pad`
+that `metrics.BoxStats.update_2d` reads.  `Split(rect=True)` itself keeps raising.
+
+Not covered (each raises Y3DError where it can be asked for): rect training batches, segments / keypoints / obb, copy_paste > 0,
 perspective != 0, Albumentations, the RNG streams of multi-worker loaders, the mosaic 3 / 9 grids.
 """
 from __future__ import annotations
@@ -35,6 +40,7 @@ _UNSUPPORTED = dict(mosaic_grid=4, albumentations=False, workers=0)
 BASE_CAP = 64
 # record widths of the two kernels (include/y3d.h)
 _TILE, _LAYER, _REC_I, _REC_F, _LAB_I, _LAB_F = 12, 50, 112, 16, 20, 48
+_LB_REC = 8  # y3d_letterbox_image: src, h0, w0, new_h, new_w, top, left, swap_rb
 
 
 def data_args(**over):
@@ -451,13 +457,16 @@ def build_batch(split, indices, args, device, mode="train", max_boxes=None, comp
     """`collate_fn([dataset[i] for i in indices])` of the reference's YOLODataset (task detect) over `split`, with the image and label
     work on the device.  -> {"img", "cls", "bboxes", "batch_idx", "counts", "im_file", "ori_shape", "resized_shape"}; the per-box keys in
     encode_labels' static layout, or with compact=True (one read-back of the counts) in collate_fn's ragged shapes.  img_mode
-    "uint8": (B, S, S, 3) uint8 in Format's channel order for the stem; "float": (B, 3, S, S) float32 in [0, 1]."""
+    "uint8": (B, S, S, 3) uint8 in Format's channel order for the stem; "float": (B, 3, S, S) float32 in [0, 1].
+    A `RectSplit` (mode "val" only) gives the validator's rectangular batch instead: see `_build_rect_batch`."""
     import numpy as np
     if torch.device(device).type != "cuda":
         raise Y3DError("build_batch: the batch is built on a HIP device (no host fallback)")
     if img_mode not in ("uint8", "float"):
         raise ValueError("img_mode must be 'uint8' or 'float'")
     _loss.check_max_boxes(max_boxes)
+    if isinstance(split, RectSplit):
+        return _build_rect_batch(split, indices, args, device, mode, max_boxes, compact, img_mode)
     samples = [sample_augment(split, i, args, mode) for i in indices]
     frames = sorted({t["frame"] for x in samples for pre in (x["pre"], x["pre2"]) if pre is not None for t in pre["tiles"]})
     slot = {f: n for n, f in enumerate(frames)}
@@ -474,6 +483,216 @@ def build_batch(split, indices, args, device, mode="train", max_boxes=None, comp
     s = split.imgsz
     batch = {"img": img, "im_file": [split.im_files[x["index"]] for x in samples], "ori_shape": [split.size(x["index"]) for x in samples],
              "resized_shape": [(s, s) for _ in samples], "counts": lab["counts"]}
+    if compact:
+        batch.update(compact_labels(lab, lab["counts"].tolist(), max_boxes))
+    else:
+        batch.update({k: lab[k] for k in ("cls", "bboxes", "batch_idx")})
+    return batch
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# Rectangular batches (the validator's dataset) and the letter-box both they and predict.Predictor go through
+# ------------------------------------------------------------------------------------------------------------------------------
+def letterbox_params(shape, new_shape, auto=False, scaleup=True, stride=32):
+    """`LetterBox(new_shape, auto, scaleup=scaleup, stride=stride)` (data/augment.py:696-732, center=True, no scaleFill) on an image of
+    `shape` (h, w), without the pixels: Python's round (half to even) wherever the reference rounds.  -> dict: r, new_unpad (w, h) as
+    the reference holds it, dw, dh (halved: the label pads), top, bottom, left, right, canvas (H, W)."""
+    h, w = int(shape[0]), int(shape[1])
+    if isinstance(new_shape, int):
+        new_shape = (new_shape, new_shape)
+    H, W = int(new_shape[0]), int(new_shape[1])
+    r = min(H / h, W / w)
+    if not scaleup:
+        r = min(r, 1.0)
+    new_unpad = int(round(w * r)), int(round(h * r))
+    dw, dh = W - new_unpad[0], H - new_unpad[1]
+    if auto:
+        dw, dh = dw % int(stride), dh % int(stride)  # np.mod of two ints
+    dw, dh = dw / 2, dh / 2
+    top, bottom = int(round(dh - 0.1)), int(round(dh + 0.1))
+    left, right = int(round(dw - 0.1)), int(round(dw + 0.1))
+    return dict(r=r, new_unpad=new_unpad, dw=dw, dh=dh, top=top, bottom=bottom, left=left, right=right,
+                canvas=(new_unpad[1] + top + bottom, new_unpad[0] + left + right))
+
+
+class RectSplit(Split):
+    """The validator's dataset: a `Split` without augmentation whose images are sorted by aspect ratio and grouped into batches that
+    each get their own stride-multiple shape — `set_rectangle` (data/base.py:226-249) replayed on the sizes `Split.size` reports.
+    `batch_shapes[k]` is the (H, W) canvas of rect batch k; `batch_of(i)` the batch of (reordered) index i; `batches()` the index lists in
+    loader order, which is what `build_batch` takes one at a time."""
+
+    def __init__(self, img_dir_or_list, imgsz=640, batch=16, stride=32, pad=0.5):
+        import numpy as np
+        super().__init__(img_dir_or_list, imgsz, batch, augment=False)
+        self.stride, self.pad = int(stride), pad
+        if self.stride < 1 or self.stride % 4:
+            raise Y3DError(f"yolo2d: rect stride {stride}: the canvas width must be a multiple of 4")
+        bi = np.floor(np.arange(self.ni) / self.batch).astype(int)
+        nb = bi[-1] + 1
+        s = np.array([self.size(i) for i in range(self.ni)])  # hw
+        ar = s[:, 0] / s[:, 1]
+        irect = ar.argsort()
+        self.irect = irect
+        self.im_files = [self.im_files[i] for i in irect]
+        self.label_files = [self.label_files[i] for i in irect]
+        self.labels = [self.labels[i] for i in irect]
+        self._hw0 = {n: (int(s[i, 0]), int(s[i, 1])) for n, i in enumerate(irect)}
+        ar = ar[irect]
+        shapes = [[1, 1]] * nb
+        for i in range(nb):
+            ari = ar[bi == i]
+            mini, maxi = ari.min(), ari.max()
+            if maxi < 1:
+                shapes[i] = [maxi, 1]
+            elif mini > 1:
+                shapes[i] = [1, 1 / mini]
+        self.batch_shapes = np.ceil(np.array(shapes) * self.imgsz / self.stride + self.pad).astype(int) * self.stride
+        self.batch_index = bi
+
+    def batch_of(self, index):
+        index = int(index)
+        if not 0 <= index < self.ni:
+            raise IndexError(f"yolo2d: index {index} of {self.ni} images")
+        return int(self.batch_index[index])
+
+    def batches(self):
+        return [[int(i) for i in range(k * self.batch, min((k + 1) * self.batch, self.ni))] for k in range(int(self.batch_index[-1]) + 1)]
+
+
+def rect_sample(split, index):
+    """`dataset[index]` of the rect=True validation dataset without pixels and labels: `get_image_and_label` (data/base.py:255-266) +
+    LetterBox(new_shape, scaleup=False) on `rect_shape` + Format's bgr draw (one `random.uniform`, as the square `val` path).
+    -> dict: index, batch, h0, w0, h, w (after load_image's resize), canvas (H, W), top, left, dw, dh, ratio_pad, p_bgr, rgb."""
+    index = int(index)
+    k = split.batch_of(index)
+    (h0, w0), (h, w) = split.load(index)
+    H, W = (int(v) for v in split.batch_shapes[k])
+    lb = letterbox_params((h, w), (H, W), auto=False, scaleup=False)
+    if lb["r"] != 1.0 or lb["new_unpad"] != (w, h):
+        raise Y3DError(f"yolo2d: rect letter-box ratio {lb['r']} after load_image's resize (expected 1)")
+    p_bgr = random.uniform(0, 1)
+    return dict(index=index, batch=k, h0=h0, w0=w0, h=h, w=w, canvas=(H, W), top=lb["top"], left=lb["left"], dw=lb["dw"], dh=lb["dh"],
+                ratio_pad=((h / h0, w / w0), (lb["left"], lb["top"])), p_bgr=p_bgr, rgb=p_bgr > 0.0)
+
+
+def pack_letterbox(imgs, rec, H, W, device):
+    """Host side of letterbox_images: the decoded (h0, w0, 3) uint8 device images of the pointer table and the (B, 8) int32 records
+    [src, h0, w0, new_h, new_w, top, left, swap_rb] for an (H, W) canvas -> dict of device tensors.  Every record must name an image of
+    the table with that image's size, and place its resized image inside the canvas."""
+    import numpy as np
+    if torch.device(device).type != "cuda":
+        raise Y3DError("pack_letterbox: the images are built on a HIP device (no host fallback)")
+    H, W = int(H), int(W)
+    if H < 1 or W < 4 or W % 4:
+        raise Y3DError(f"pack_letterbox: canvas {H} x {W}: the width must be a multiple of 4")
+    if not imgs or any((not torch.is_tensor(t)) or (not t.is_cuda) or t.dtype != torch.uint8 or t.dim() != 3 or t.shape[2] != 3 for t in imgs):
+        raise Y3DError("pack_letterbox: images must be (H, W, 3) uint8 tensors on a HIP device")
+    imgs = [t.contiguous() for t in imgs]
+    rec = np.ascontiguousarray(rec, dtype=np.int32)
+    if rec.ndim != 2 or rec.shape[1] != _LB_REC or not len(rec):
+        raise Y3DError("pack_letterbox: records of the wrong shape")
+    for r in rec:
+        if not 0 <= r[0] < len(imgs) or tuple(imgs[r[0]].shape[:2]) != (int(r[1]), int(r[2])) or min(r[1:5]) < 1:
+            raise Y3DError("pack_letterbox: a record does not match its image")
+        if r[5] < 0 or r[6] < 0 or r[5] + r[3] > H or r[6] + r[4] > W:
+            raise Y3DError("pack_letterbox: a record places its image outside the canvas")
+    src = torch.tensor([t.data_ptr() for t in imgs], dtype=torch.int64).to(device)
+    return {"imgs": imgs, "src": src, "rec": _up(rec, device), "H": H, "W": W}
+
+
+def letterbox_images(packed, mode="uint8"):
+    """B images letter-boxed into one (H, W) canvas, one HIP launch, no host synchronisation (capturable): allocates the output and
+    launches.  mode "uint8": (B, H, W, 3) uint8 for the stem; "float": (B, 3, H, W) float32 in [0, 1]."""
+    rec = packed["rec"]
+    if not rec.is_cuda:
+        raise Y3DError("letterbox_images: the packed records must live on a HIP device (no host fallback)")
+    B, H, W, dev = rec.shape[0], packed["H"], packed["W"], rec.device
+    if W % 4:
+        raise Y3DError(f"letterbox_images: canvas width {W} must be a multiple of 4")
+    if mode == "float":
+        out = torch.empty(B, 3, H, W, dtype=torch.float32, device=dev)
+    elif mode == "uint8":
+        out = torch.empty(B, H, W, 3, dtype=torch.uint8, device=dev)
+    else:
+        raise ValueError("mode must be 'float' or 'uint8'")
+    lib().letterbox_image(packed["src"].data_ptr(), packed["src"].shape[0], rec.data_ptr(), B, H, W, 0 if mode == "float" else 1,
+                          out.data_ptr(), ops.stream())
+    return out
+
+
+def pack_letterbox_labels(label_rows, lab_i, lab_f, device):
+    """Host side of letterbox_labels: the (n, 5) float32 label table, lab_i (B, 2) int32 [first row, rows] and lab_f (B, 4) float32
+    [w, h, padw, padh] -> dict of device tensors"""
+    import numpy as np
+    if torch.device(device).type != "cuda":
+        raise Y3DError("pack_letterbox_labels: the label encoder runs on a HIP device (no host fallback)")
+    rows = np.asarray(label_rows, np.float32).reshape(-1, 5)
+    n = len(rows)
+    lab_i, lab_f = np.ascontiguousarray(lab_i, dtype=np.int32), np.ascontiguousarray(lab_f, dtype=np.float32)
+    if lab_i.ndim != 2 or lab_i.shape[1] != 2 or lab_f.shape != (lab_i.shape[0], 4) or not len(lab_i):
+        raise Y3DError("pack_letterbox_labels: record arrays of the wrong shape")
+    if (lab_i < 0).any() or (lab_i.sum(1)[lab_i[:, 1] > 0] > n).any():
+        raise Y3DError("pack_letterbox_labels: an image's label rows lie outside the label table")
+    return {"rec": _up(rows if n else np.zeros((1, 5), np.float32), device), "n_rec": n, "lab_i": _up(lab_i, device), "lab_f": _up(lab_f, device)}
+
+
+def letterbox_labels(packed, H, W, max_boxes=None):
+    """The validation label chain of B samples + `collate_fn`, one HIP launch, no host synchronisation (capturable), in encode_labels'
+    static layout of cap = max_boxes or 64 rows per image; normalised by the (H, W) canvas."""
+    cap = _loss.check_max_boxes(max_boxes) or BASE_CAP
+    li = packed["lab_i"]
+    if not li.is_cuda or not packed["rec"].is_cuda or not packed["lab_f"].is_cuda:
+        raise Y3DError("letterbox_labels: the packed labels must live on a HIP device (no host fallback)")
+    B, dev = li.shape[0], li.device
+    o = {"cls": torch.empty(B * cap, 1, dtype=torch.float32, device=dev), "bboxes": torch.empty(B * cap, 4, dtype=torch.float32, device=dev),
+         "batch_idx": torch.empty(B * cap, dtype=torch.float32, device=dev), "counts": torch.empty(B, dtype=torch.int32, device=dev)}
+    lib().letterbox_labels(packed["rec"].data_ptr(), int(packed["n_rec"]), li.data_ptr(), packed["lab_f"].data_ptr(), B, int(H), int(W), cap,
+                           o["cls"].data_ptr(), o["bboxes"].data_ptr(), o["batch_idx"].data_ptr(), o["counts"].data_ptr(), ops.stream())
+    return o
+
+
+def rect_records(split, samples, slot, rec_start):
+    """rect_sample's records -> (rec (B, 8) int32 of y3d_letterbox_image, lab_i (B, 2) int32, lab_f (B, 4) float32 of
+    y3d_letterbox_labels); slot: index -> position in the pointer table, rec_start: index -> first row in the label table"""
+    import numpy as np
+    B = len(samples)
+    rec, li, lf = np.zeros((B, _LB_REC), np.int32), np.zeros((B, 2), np.int32), np.zeros((B, 4), np.float32)
+    for b, s in enumerate(samples):
+        rec[b] = (slot[s["index"]], s["h0"], s["w0"], s["h"], s["w"], s["top"], s["left"], int(not s["rgb"]))
+        li[b] = (rec_start[s["index"]], len(split.labels[s["index"]]))
+        lf[b] = (s["w"], s["h"], s["dw"], s["dh"])
+    return rec, li, lf
+
+
+def _build_rect_batch(split, indices, args, device, mode, max_boxes, compact, img_mode):
+    """`collate_fn([dataset[i] for i in indices])` of the validator's rect=True YOLODataset: all indices of one rect batch, letter-boxed
+    (ratio 1 after load_image's resize) into that batch's (H, W) canvas.  -> the keys of the square path, `resized_shape` = (H, W) per
+    image, and `ratio_pad` = ((h / h0, w / w0), (left, top)) per image as `BoxStats.update_2d` reads it.  img_mode "uint8":
+    (B, H, W, 3) uint8; "float": (B, 3, H, W) float32."""
+    import numpy as np
+    _check_args(args)
+    if mode != "val":
+        raise Y3DError(f"yolo2d: a RectSplit builds validation batches only (mode {mode!r}); rect training batches are not supported")
+    indices = [int(i) for i in indices]
+    if not indices:
+        raise Y3DError("yolo2d: an empty rect batch")
+    ks = {split.batch_of(i) for i in indices}
+    if len(ks) != 1:
+        raise Y3DError(f"yolo2d: indices of rect batches {sorted(ks)}: a rect batch has one shape, build them one at a time")
+    samples = [rect_sample(split, i) for i in indices]
+    H, W = samples[0]["canvas"]
+    frames = sorted(set(indices))
+    slot = {f: n for n, f in enumerate(frames)}
+    imgs = [split.decode(f, device) for f in frames]
+    rec_start, row = {}, 0
+    for f in frames:
+        rec_start[f] = row
+        row += len(split.labels[f])
+    rec, li, lf = rect_records(split, samples, slot, rec_start)
+    img = letterbox_images(pack_letterbox(imgs, rec, H, W, device), img_mode)
+    lab = letterbox_labels(pack_letterbox_labels(np.concatenate([split.labels[f] for f in frames]), li, lf, device), H, W, max_boxes)
+    batch = {"img": img, "im_file": [split.im_files[i] for i in indices], "ori_shape": [(s["h0"], s["w0"]) for s in samples],
+             "resized_shape": [(H, W) for _ in samples], "ratio_pad": [s["ratio_pad"] for s in samples], "counts": lab["counts"]}
     if compact:
         batch.update(compact_labels(lab, lab["counts"].tolist(), max_boxes))
     else:
