@@ -514,6 +514,19 @@ int y3d_letterbox_labels(const float* rec, int n_rec, const int* lab_i, const fl
  * IEEE division.  out (B, K, 6): the kept rows first, in input order, the rest zeros (out must not be preds); counts (B) int32. */
 int y3d_predict_rows(const float* preds, const float* meta, float conf, const int* classes, int n_cls, int B, int K, float* out, int* counts,
                      void* stream);
+/* The 3D predictor's row pass (predict3d.hip), one workgroup per image: KITTI decode, confidence / class filter, ordered compaction,
+ * the eight box corners and their projection.  preds (B, K, 37) fp32, calib (B, 6), ratio (B, 2), inv_trans (B, 2, 3) or NULL,
+ * mean_size (nc, 3), use_camera_dis: as y3d_kitti_decode takes them, and every kept row's 14 values are that kernel's bit for bit.
+ * P2 (B, 12): the full 3 x 4 projection of the original image, float32 values promoted to double.  A row is kept when
+ * !(score < conf) and, when n_cls > 0, (int)preds[.., 36] equals one of classes (n_cls) int32 (NULL when n_cls = 0).  For the j-th
+ * kept row of image b, in input order: rows[b, j, 0:14] f64 [cls, alpha, x1, y1, x2, y2, h, w, l, x, y, z, ry, score];
+ * corners3d[b, j, 8, 3] f64, camera coordinates, Object3d.generate_corners3d's order (kitti_utils.py:98-114; y is the bottom face);
+ * corners_img[b, j, 8, 2] f64 = Calibration.corners3d_to_img_boxes' boxes_corner (kitti_utils.py:266-284; the division is done
+ * whatever its sign).  Slots j >= counts[b] of all three are zeros; counts (B) int32.  No output may overlap an input or
+ * another output: the entry compares the byte ranges and refuses. */
+int y3d_predict3d_rows(const float* preds, int B, int K, const double* calib, const double* P2, const double* ratio,
+                       const double* inv_trans, const double* mean_size, int nc, int use_camera_dis, double conf, const int* classes,
+                       int n_cls, double* rows, double* corners3d, double* corners_img, int* counts, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * KITTI AP evaluation (kitti_eval.hip) — the evaluator behind KITTIDataset.get_stats (data/datasets/kitti.py:444-450):

@@ -4,6 +4,10 @@ Mirrors `KITTIDataset.decode_preds` / `decode_preds_eval` (data/datasets/kitti.p
 from `_prepare_preds` (models/yolov10_3D/val.py:210-214) on CPU with a python loop and `.item()` per detection: heading-bin argmax +
 residual -> alpha, size residual + class mean size, centre back-projection through the (inverse-affine'd) calibration, rotation_y,
 score = sigmoid(cls) * exp(-depth log-variance), threshold.  Here it is one launch over all B*K rows (`y3d_kitti_decode`).
+
+Further down: the one-to-many depth fusion, the image and label sides of the training / validation batches (`build_batch`), the
+unlabelled test split (`build_test_batch`, which `predict.Predictor3d.predict_split` reads) and `save_results`, the writer of the
+files a KITTI submission and `kitti_eval.eval_from_scratch` read.
 """
 from __future__ import annotations
 
@@ -446,3 +450,57 @@ def build_batch(root_or_split_file, indices, args, device, mode="train", compact
     else:
         batch.update({k: lab[k] for k in PER_BOX})
     return batch
+
+
+def save_results(results, output_dir="./outputs", class_name=("Car", "Pedestrian", "Cyclist")):
+    """`KITTIDataset.save_results` (kitti.py:452-464) to the byte: {im_file: rows [cls, alpha, x1, y1, x2, y2, h, w, l, x, y, z, ry,
+    score]} -> output_dir/preds/<im_file>, one line per row: the class name, '0.0 0', then every further value as ' {:.2f}'.
+    -> the directory written (what `kitti_eval.eval_from_scratch` takes as det_dir)"""
+    import os
+    output_dir = os.path.join(output_dir, "preds")
+    os.makedirs(output_dir, exist_ok=True)
+    for img_file, rows in results.items():
+        with open(os.path.join(output_dir, img_file), "w") as f:
+            for row in rows:
+                f.write("{} 0.0 0".format(class_name[int(row[0])]))
+                for v in row[1:]:
+                    f.write(" {:.2f}".format(v))
+                f.write("\n")
+    return output_dir
+
+
+def build_test_batch(root_or_split_file, indices, device, img_mode="uint8", resolution=RESOLUTION):
+    """`collate_fn([dataset[i] for i in indices])` of the reference's KITTIDataset for the unlabelled `testing/` split (kitti.py:116-135,
+    :186-206, :395-431 with split == 'test': no augmentation, no labels): PNGs and calibrations are read on the host, the images resized
+    by augment_images.  root_or_split_file: a split file (ImageSets/test.txt) or the KITTI root.  -> `img`, `calib` (B, 6) float64 (the
+    six constants x ratio, :405-407), `info`, `im_file`, `ori_shape`, `ratio_pad` (B, 2, 2) float64 as build_batch(mode="val") gives
+    them, and `P2` (B, 3, 4) float32, the projection of the original image (what the predictor's decode and corners need)."""
+    import os
+    import numpy as np
+    from PIL import Image
+    if torch.device(device).type != "cuda":
+        raise Y3DError("build_test_batch: the batch is built on a HIP device (no host fallback)")
+    if not len(indices):
+        raise Y3DError("build_test_batch: no frames")
+    data, ids = _split(root_or_split_file, "test")
+    path = lambda sub, i, ext: os.path.join(data, sub, f"{i:06d}.{ext}")
+    res = np.array([int(resolution[0]), int(resolution[1])])
+    imgs, P2s, info, ratio_pad, calib = [], [], [], [], []
+    for pos in indices:
+        im = Image.open(path("image_2", ids[pos], "png"))
+        img_size = np.array(im.size)
+        P = read_calib(path("calib", ids[pos], "txt"))
+        trans_inv = get_affine_transform(img_size / 2, img_size, resolution, inv=True)[1]
+        rp = np.array([res / img_size, np.array([0, 0])])
+        c = calib_params(P)
+        calib.append([c[0] * rp[0, 0], c[1] * rp[0, 1], c[2] * rp[0, 0], c[3] * rp[0, 1], c[4] * rp[0, 0], c[5] * rp[0, 1]])
+        imgs.append(torch.from_numpy(np.array(im.convert("RGB"))).to(device))
+        P2s.append(P)
+        ratio_pad.append(rp)
+        info.append({"img_id": ids[pos], "img_size": img_size, "trans_inv": trans_inv})
+    B = len(imgs)
+    img = augment_images(imgs, [None] * B, [False] * B, [d["trans_inv"] for d in info], resolution, mode="float" if img_mode == "float" else "uint8")
+    up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a)).to(device=device, dtype=dt)
+    return {"img": img, "calib": up(np.array(calib, np.float64), torch.float64), "info": info, "im_file": [f"{d['img_id']:06d}.txt" for d in info],
+            "ori_shape": [d["img_size"][::-1] for d in info], "ratio_pad": up(np.stack(ratio_pad).astype(np.float64), torch.float64),
+            "P2": up(np.stack(P2s), torch.float32)}
