@@ -582,6 +582,22 @@ int y3d_match_predictions(const float* iou, const int* gt_cls, int n_gt, const i
 int y3d_box_match_batch(int mode, const void* preds, const unsigned char* keep, int B, int K, const double* meta, int img_h, int img_w,
                         int single_cls, const float* gt_img, const float* gt_cls, const float* gt_box, int n_gt, const float* thr,
                         int n_thr, int* tp, double* conf, int* cls, int* status, void* stream);
+/* ConfusionMatrix.process_batch (utils/metrics.py:319-376) for one validation batch, one workgroup per image: the batch arguments of
+ * y3d_box_match_batch (the same box preparation and fp32 IoU, bit for bit), nc classes, a row takes part iff kept and its confidence
+ * > conf (strict; fp32 for mode 0, f64 for mode 1), pairs with iou > (float)iou_thres (strict, >= 0) are matched by two argmax passes
+ * whatever their classes (ties: the higher gt index, then the higher detection index).  ADDS into matrix (nc + 1, nc + 1) int32,
+ * [predicted, true], index nc = background, with integer atomics.  An image without gts adds nothing (neither validator calls
+ * process_batch for it); an image without a single match does not count its detections (the reference's `if n:`).  K may be 0 (every
+ * gt is missed).  status (2) int32: [0] atomicMax of the gt count of an image above the limit (it adds nothing), [1] set when a
+ * class outside [0, nc) was met (that box is not counted). */
+int y3d_confusion_batch(int mode, const void* preds, const unsigned char* keep, int B, int K, const double* meta, int img_h, int img_w,
+                        int single_cls, const float* gt_img, const float* gt_cls, const float* gt_box, int n_gt, int nc, double conf,
+                        double iou_thres, int* matrix, int* status, void* stream);
+/* The drop-in's single image: gt_box (n_gt, 4) prepared xyxy fp32, gt_cls (n_gt) int32, det (n_det, 6) [x1, y1, x2, y2, conf, cls] fp32
+ * or (det_f64) f64, or NULL (`detections=None`).  As above, except that an image without gts counts every detection above conf as
+ * matrix[cls, nc] (utils/metrics.py:330-336). */
+int y3d_confusion_image(const float* gt_box, const int* gt_cls, int n_gt, const void* det, int det_f64, int n_det, int nc, double conf,
+                        double iou_thres, int* matrix, int* status, void* stream);
 /* ap_per_class core: n detections sorted by (class, confidence descending); ucls (nc) int32 classes with targets, nl (nc) f64 = n_l + eps;
  * x_ap (n_ap <= 129) / x_curve (n_curve <= 1024) f64 ascending grids -> ap (nc, n_thr), p_curve / r_curve (nc, n_curve) f64 */
 int y3d_ap_per_class(const int* tp, const double* conf, const int* cls, int64_t n, const int* ucls, const double* nl, int nc, int n_thr,

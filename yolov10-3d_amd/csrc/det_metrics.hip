@@ -18,6 +18,26 @@
 // or j the last index -> fp[j]; otherwise slope * (x - xp[j]) + fp[j], slope = (fp[j+1] - fp[j]) / (xp[j+1] - xp[j]).  Each grid point
 // has exactly one owning sample j, so the kernels write every point once: a sample owns the grid points in [xp[j], xp[j+1]).
 //
+// Confusion matrix.  ConfusionMatrix.process_batch (utils/metrics.py:319-376), fed per image by both validators' update_metrics
+// (models/yolo/detect/val.py:137, :151; models/yolov10_3D/val.py:138, :156).  Boxes and IoUs are the matcher's own (the same device
+// functions), so every IoU is bit for bit the one behind the tp masks.  A detection takes part iff its row is kept and conf_row > conf
+// (strict, in the row's precision: fp32 for 2D rows, fp64 for 3D rows); candidate pairs are those with iou > (float)iou_thres (strict),
+// whatever their classes.  The two np.unique steps amount to two argmax passes: each detection keeps its best gt, then each gt keeps the
+// best of the detections that chose it; a detection that loses does not fall back to its second-best gt.  Both passes are LDS claims
+// (atomicMax of the IoU bits, then of the detection index among the holders of that maximum).  Counting: a matched gt i with detection
+// d -> matrix[cls(d), cls(i)]; an unmatched gt -> matrix[nc, cls(i)]; when the image has at least one match, every participating
+// detection left unmatched -> matrix[cls(d), nc].  When the image has NO match its detections add nothing: that is the reference's
+// `if n:` guard (:373) and is kept on purpose.  An image with gts and no rows (the validators' `detections=None` call) counts every gt
+// as missed, as does one whose rows all fail the filter.  An image WITHOUT gts: the batched entry adds nothing, because neither
+// validator calls process_batch for it (`if nl:`); the single-image entry behind the drop-in counts matrix[cls(d), nc] for every
+// participating detection (:330-336).  single_cls zeroes the detection class only, as both validators do.
+// Deliberate tie rules where the reference is implementation-defined (argsort()[::-1] of an unstable sort) - what a stable sort,
+// reversed, gives: an IoU tie between two gts of one detection goes to the higher gt index; an IoU tie between two detections that chose
+// one gt goes to the higher detection index.
+// All writes to the matrix are integer atomicAdds, so two runs give identical matrices.  status[0]: atomicMax of the gt count of an
+// image above DM_MAX_GT (that image adds nothing); status[1]: set when a class outside [0, nc) was met (the reference raises IndexError;
+// such a box is not counted).
+//
 // Limits: DM_MAX_GT gts and DM_MAX_DET detections per image, DM_MAX_THR thresholds.  No kernel uses scratch (all run-time indexed
 // state is in LDS).
 #include "common.h"
@@ -35,7 +55,7 @@ constexpr int DM_BLOCK = 256;
 constexpr int DM_MAX_AP_PTS = 129;     // np.trapz's add.reduce: one pairwise block (<= 128 terms)
 constexpr int DM_MAX_CURVE_PTS = 1024;
 
-enum { MODE_2D = 0, MODE_3D = 1, MODE_IOU = 2 };
+enum { MODE_2D = 0, MODE_3D = 1, MODE_IOU = 2, MODE_XYXY = 3 };
 
 // box_iou (utils/metrics.py:53-75) for one pair, a = gt, b = det, fp32 in the reference's operation order
 __device__ __forceinline__ float pair_iou(float a1x, float a1y, float a2x, float a2y, float b1x, float b1y, float b2x, float b2y, float eps) {
@@ -77,6 +97,63 @@ __device__ double block_suffix_max(double v, double* s) {
   return s[tid];
 }
 
+// The image's gts in batch order (ordered compaction of batch_idx == b), prepared as _prepare_batch / decode_batch_eval do; shared by
+// the matcher and the confusion kernel.  P has meta, gt_img, gt_cls, gt_box, n_gt, img_h, img_w.  Returns the image's gt count, which
+// may exceed DM_MAX_GT: only the first DM_MAX_GT are stored.  Every lane of the workgroup must call it.
+template <int MODE, class P>
+__device__ __forceinline__ int load_gts(const P& p, int b, float (*s_gb)[4], int* s_gc, int* s_scan) {
+  const int tid = threadIdx.x;
+  int ng = 0;
+  float h0 = 0.f, w0 = 0.f, gain = 1.f, padw = 0.f, padh = 0.f;
+  if (MODE == MODE_2D) {
+    const double* m = p.meta + (size_t)b * 5;
+    h0 = (float)m[0]; w0 = (float)m[1]; gain = (float)m[2]; padw = (float)m[3]; padh = (float)m[4];
+  } else {
+    h0 = (float)p.meta[(size_t)b * 2]; w0 = (float)p.meta[(size_t)b * 2 + 1];
+  }
+  for (int base = 0; base < p.n_gt; base += DM_BLOCK) {
+    const int i = base + tid;
+    const int f = (i < p.n_gt && p.gt_img[i] == (float)b) ? 1 : 0;
+    const int incl = block_scan_sum<false>(f, s_scan);
+    const int pos = ng + incl - f;
+    if (f && pos < DM_MAX_GT) {
+      const float* q = p.gt_box + (size_t)i * 4;
+      const float dw = q[2] / 2.f, dh = q[3] / 2.f;
+      float x1 = q[0] - dw, y1 = q[1] - dh, x2 = q[0] + dw, y2 = q[1] + dh;
+      if (MODE == MODE_2D) {  // xywh2xyxy(bbox) * imgsz[[1, 0, 1, 0]], then scale_boxes: - pad, / gain, clip to ori_shape
+        const float W = (float)p.img_w, H = (float)p.img_h;
+        x1 = x1 * W; y1 = y1 * H; x2 = x2 * W; y2 = y2 * H;
+        x1 = (x1 - padw) / gain; y1 = (y1 - padh) / gain; x2 = (x2 - padw) / gain; y2 = (y2 - padh) / gain;
+        x1 = fminf(fmaxf(x1, 0.f), w0); y1 = fminf(fmaxf(y1, 0.f), h0); x2 = fminf(fmaxf(x2, 0.f), w0); y2 = fminf(fmaxf(y2, 0.f), h0);
+      } else {                // xywh2xyxy(bbox) * ori_shape[[1, 0, 1, 0]]; exact in the reference's fp64, rounded once by box_iou
+        x1 = x1 * w0; y1 = y1 * h0; x2 = x2 * w0; y2 = y2 * h0;
+      }
+      s_gb[pos][0] = x1; s_gb[pos][1] = y1; s_gb[pos][2] = x2; s_gb[pos][3] = y2;
+      s_gc[pos] = (int)p.gt_cls[i];
+    }
+    ng += s_scan[DM_BLOCK - 1];
+    __syncthreads();
+  }
+  return ng;
+}
+
+// Row r = b * K + k of a batched mode as the validators prepare it: the fp32 xyxy box box_iou sees and the class (0 under single_cls)
+template <int MODE, class P>
+__device__ __forceinline__ void prep_det(const P& p, int b, size_t r, float& x1, float& y1, float& x2, float& y2, int& c) {
+  if (MODE == MODE_2D) {  // _prepare_pred: scale_boxes on a clone of the row
+    const float* q = (const float*)p.preds + r * 6;
+    const double* mt = p.meta + (size_t)b * 5;
+    const float h0 = (float)mt[0], w0 = (float)mt[1], gain = (float)mt[2], padw = (float)mt[3], padh = (float)mt[4];
+    x1 = (q[0] - padw) / gain; y1 = (q[1] - padh) / gain; x2 = (q[2] - padw) / gain; y2 = (q[3] - padh) / gain;
+    x1 = fminf(fmaxf(x1, 0.f), w0); y1 = fminf(fmaxf(y1, 0.f), h0); x2 = fminf(fmaxf(x2, 0.f), w0); y2 = fminf(fmaxf(y2, 0.f), h0);
+    c = p.single_cls ? 0 : (int)q[5];
+  } else {                // decode row: box cols 2:6 (fp64, cast by box_iou), class col 0
+    const double* q = (const double*)p.preds + r * 14;
+    x1 = (float)q[2]; y1 = (float)q[3]; x2 = (float)q[4]; y2 = (float)q[5];
+    c = p.single_cls ? 0 : (int)q[0];
+  }
+}
+
 struct MatchP {
   const void* preds;          // MODE_2D (B, K, 6) f32 | MODE_3D (B, K, 14) f64 | MODE_IOU (n_gt, K) f32 IoU matrix
   const unsigned char* keep;  // (B, K) or NULL
@@ -111,36 +188,7 @@ __global__ void __launch_bounds__(DM_BLOCK) box_match_kernel(MatchP p) {
     ng = p.n_gt;  // host-checked <= DM_MAX_GT
     for (int g = tid; g < ng; g += DM_BLOCK) s_gc[g] = p.gt_cls_i[g];
   } else {
-    float h0 = 0.f, w0 = 0.f, gain = 1.f, padw = 0.f, padh = 0.f;
-    if (MODE == MODE_2D) {
-      const double* m = p.meta + (size_t)b * 5;
-      h0 = (float)m[0]; w0 = (float)m[1]; gain = (float)m[2]; padw = (float)m[3]; padh = (float)m[4];
-    } else {
-      h0 = (float)p.meta[(size_t)b * 2]; w0 = (float)p.meta[(size_t)b * 2 + 1];
-    }
-    for (int base = 0; base < p.n_gt; base += DM_BLOCK) {
-      const int i = base + tid;
-      const int f = (i < p.n_gt && p.gt_img[i] == (float)b) ? 1 : 0;
-      const int incl = block_scan_sum<false>(f, s_scan);
-      const int pos = ng + incl - f;
-      if (f && pos < DM_MAX_GT) {
-        const float* q = p.gt_box + (size_t)i * 4;
-        const float dw = q[2] / 2.f, dh = q[3] / 2.f;
-        float x1 = q[0] - dw, y1 = q[1] - dh, x2 = q[0] + dw, y2 = q[1] + dh;
-        if (MODE == MODE_2D) {  // xywh2xyxy(bbox) * imgsz[[1, 0, 1, 0]], then scale_boxes: - pad, / gain, clip to ori_shape
-          const float W = (float)p.img_w, H = (float)p.img_h;
-          x1 = x1 * W; y1 = y1 * H; x2 = x2 * W; y2 = y2 * H;
-          x1 = (x1 - padw) / gain; y1 = (y1 - padh) / gain; x2 = (x2 - padw) / gain; y2 = (y2 - padh) / gain;
-          x1 = fminf(fmaxf(x1, 0.f), w0); y1 = fminf(fmaxf(y1, 0.f), h0); x2 = fminf(fmaxf(x2, 0.f), w0); y2 = fminf(fmaxf(y2, 0.f), h0);
-        } else {                // xywh2xyxy(bbox) * ori_shape[[1, 0, 1, 0]]; exact in the reference's fp64, rounded once by box_iou
-          x1 = x1 * w0; y1 = y1 * h0; x2 = x2 * w0; y2 = y2 * h0;
-        }
-        s_gb[pos][0] = x1; s_gb[pos][1] = y1; s_gb[pos][2] = x2; s_gb[pos][3] = y2;
-        s_gc[pos] = (int)p.gt_cls[i];
-      }
-      ng += s_scan[DM_BLOCK - 1];
-      __syncthreads();
-    }
+    ng = load_gts<MODE>(p, b, s_gb, s_gc, s_scan);
     if (ng > DM_MAX_GT) {  // refused: get_stats raises; never index past the tables
       if (tid == 0) atomicMax(p.status, ng);
       ng = 0;
@@ -167,18 +215,7 @@ __global__ void __launch_bounds__(DM_BLOCK) box_match_kernel(MatchP p) {
       } else {
         float x1, y1, x2, y2;
         int c;
-        if (MODE == MODE_2D) {  // _prepare_pred: scale_boxes on a clone of the row
-          const float* q = (const float*)p.preds + r * 6;
-          const double* mt = p.meta + (size_t)b * 5;
-          const float h0 = (float)mt[0], w0 = (float)mt[1], gain = (float)mt[2], padw = (float)mt[3], padh = (float)mt[4];
-          x1 = (q[0] - padw) / gain; y1 = (q[1] - padh) / gain; x2 = (q[2] - padw) / gain; y2 = (q[3] - padh) / gain;
-          x1 = fminf(fmaxf(x1, 0.f), w0); y1 = fminf(fmaxf(y1, 0.f), h0); x2 = fminf(fmaxf(x2, 0.f), w0); y2 = fminf(fmaxf(y2, 0.f), h0);
-          c = p.single_cls ? 0 : (int)q[5];
-        } else {                // decode row: box cols 2:6 (fp64, cast by box_iou), class col 0
-          const double* q = (const double*)p.preds + r * 14;
-          x1 = (float)q[2]; y1 = (float)q[3]; x2 = (float)q[4]; y2 = (float)q[5];
-          c = p.single_cls ? 0 : (int)q[0];
-        }
+        prep_det<MODE>(p, b, r, x1, y1, x2, y2, c);
         for (int g = 0; g < ng; ++g) {
           if (s_gc[g] != c) continue;
           const float v = pair_iou(s_gb[g][0], s_gb[g][1], s_gb[g][2], s_gb[g][3], x1, y1, x2, y2, p.eps);
@@ -222,6 +259,129 @@ __global__ void __launch_bounds__(DM_BLOCK) box_match_kernel(MatchP p) {
       p.cls[r] = c;
     }
   }
+}
+
+struct ConfP {
+  const void* preds;          // MODE_2D (B, K, 6) f32 | MODE_3D (B, K, 14) f64 | MODE_XYXY (K, 6) f32 or f64 (det_f64), NULL with K = 0
+  const unsigned char* keep;  // (B, K) or NULL
+  const double* meta;         // as MatchP (NULL in MODE_XYXY)
+  const float* gt_img;        // (n_gt), NULL in MODE_XYXY
+  const float* gt_cls;        // (n_gt) float as collated, NULL in MODE_XYXY
+  const int* gt_cls_i;        // MODE_XYXY: (n_gt) int32 classes
+  const float* gt_box;        // (n_gt, 4): normalised xywh | MODE_XYXY: prepared xyxy
+  int B, K, n_gt, img_h, img_w, single_cls, nc, det_f64;
+  int count_empty;            // an image without gts counts its detections as false positives (the drop-in; the validators skip it)
+  float eps, iou_thres;
+  double conf;
+  int* matrix;                // (nc + 1, nc + 1), added into
+  int* status;                // [0] atomicMax'd with the gt count of an image above DM_MAX_GT, [1] set by a class outside [0, nc)
+};
+
+// One workgroup per image; the rules are in the file header.
+template <int MODE>
+__global__ void __launch_bounds__(DM_BLOCK) confusion_kernel(ConfP p) {
+  __shared__ float s_gb[DM_MAX_GT][4];
+  __shared__ int s_gc[DM_MAX_GT];
+  __shared__ unsigned s_gmax[DM_MAX_GT];  // the bits of the largest IoU among the detections that chose the gt (IoUs here are > 0)
+  __shared__ int s_gdet[DM_MAX_GT];       // the gt's detection, -1 = unmatched
+  __shared__ int s_best[DM_MAX_DET];      // the detection's gt, -1 = none above the threshold, -2 = the row takes no part
+  __shared__ float s_m[DM_MAX_DET];
+  __shared__ int s_dc[DM_MAX_DET];
+  __shared__ int s_scan[DM_BLOCK];
+  __shared__ int s_any;
+  const int tid = threadIdx.x, b = blockIdx.x, K = p.K, nc = p.nc, ld = p.nc + 1;
+
+  // 1. the image's gts, exactly the matcher's
+  int ng;
+  if (MODE == MODE_XYXY) {
+    ng = p.n_gt;  // host-checked <= DM_MAX_GT
+    for (int g = tid; g < ng; g += DM_BLOCK) {
+      const float* q = p.gt_box + (size_t)g * 4;
+      s_gb[g][0] = q[0]; s_gb[g][1] = q[1]; s_gb[g][2] = q[2]; s_gb[g][3] = q[3];
+      s_gc[g] = p.gt_cls_i[g];
+    }
+  } else {
+    ng = load_gts<MODE>(p, b, s_gb, s_gc, s_scan);
+    if (ng > DM_MAX_GT) {  // refused: the image adds nothing and reading the matrix raises; never index past the tables
+      if (tid == 0) atomicMax(p.status, ng);
+      return;
+    }
+  }
+  if (ng == 0 && !p.count_empty) return;  // neither validator calls process_batch for an image without gts
+  for (int g = tid; g < ng; g += DM_BLOCK) { s_gmax[g] = 0u; s_gdet[g] = -1; }
+  if (tid == 0) s_any = ng == 0 ? 1 : 0;  // utils/metrics.py:330-336 counts every detection of an image without gts
+  __syncthreads();
+
+  // 2. each participating detection's best gt above the threshold, whatever the classes (ties -> the higher gt index), and the
+  //    largest IoU among each gt's claimants
+  for (int k = tid; k < K; k += DM_BLOCK) {
+    const size_t r = (size_t)b * K + k;
+    bool part = MODE == MODE_XYXY || p.keep == nullptr || p.keep[r] != 0;
+    float x1 = 0.f, y1 = 0.f, x2 = 0.f, y2 = 0.f;
+    int c = 0;
+    if (part) {
+      if (MODE == MODE_XYXY) {
+        if (p.det_f64) {
+          const double* q = (const double*)p.preds + r * 6;
+          x1 = (float)q[0]; y1 = (float)q[1]; x2 = (float)q[2]; y2 = (float)q[3];
+          part = q[4] > p.conf;
+          c = (int)q[5];
+        } else {
+          const float* q = (const float*)p.preds + r * 6;
+          x1 = q[0]; y1 = q[1]; x2 = q[2]; y2 = q[3];
+          part = q[4] > (float)p.conf;
+          c = (int)q[5];
+        }
+      } else {
+        prep_det<MODE>(p, b, r, x1, y1, x2, y2, c);
+        if (MODE == MODE_2D) part = ((const float*)p.preds)[r * 6 + 4] > (float)p.conf;
+        else part = ((const double*)p.preds)[r * 14 + 13] > p.conf;
+      }
+      if (part && (c < 0 || c >= nc)) {
+        p.status[1] = 1;
+        part = false;
+      }
+    }
+    int best = -1;
+    float m = 0.f;
+    if (part) {
+      for (int g = 0; g < ng; ++g) {
+        const float v = pair_iou(s_gb[g][0], s_gb[g][1], s_gb[g][2], s_gb[g][3], x1, y1, x2, y2, p.eps);
+        if (v > p.iou_thres && v >= m) { m = v; best = g; }
+      }
+      if (best >= 0) {
+        atomicMax(&s_gmax[best], __float_as_uint(m));
+        s_any = 1;
+      }
+    }
+    s_best[k] = part ? best : -2;
+    s_m[k] = m;
+    s_dc[k] = c;
+  }
+  __syncthreads();
+
+  // 3. each gt keeps the best of the detections that chose it (ties -> the higher detection index)
+  for (int k = tid; k < K; k += DM_BLOCK) {
+    const int best = s_best[k];
+    if (best >= 0 && __float_as_uint(s_m[k]) == s_gmax[best]) atomicMax(&s_gdet[best], k);
+  }
+  __syncthreads();
+
+  // 4. counts
+  for (int g = tid; g < ng; g += DM_BLOCK) {
+    const int gc = s_gc[g], d = s_gdet[g];
+    if (gc < 0 || gc >= nc) {
+      p.status[1] = 1;
+      continue;
+    }
+    atomicAdd(&p.matrix[(d >= 0 ? s_dc[d] : nc) * ld + gc], 1);
+  }
+  if (s_any)  // the reference's `if n:` guard: without a single match in the image its detections are not counted
+    for (int k = tid; k < K; k += DM_BLOCK) {
+      const int best = s_best[k];
+      if (best == -2 || (best >= 0 && s_gdet[best] == k)) continue;
+      atomicAdd(&p.matrix[s_dc[k] * ld + nc], 1);
+    }
 }
 
 __global__ void box_iou_kernel(const float* a, int na, const float* bx, int nb, float eps, float* out) {
@@ -447,6 +607,42 @@ int y3d_box_match_batch(int mode, const void* preds, const unsigned char* keep, 
   p.tp = tp; p.conf = conf; p.cls = cls; p.status = status;
   if (mode == MODE_2D) hipLaunchKernelGGL(box_match_kernel<MODE_2D>, dim3(B), dim3(DM_BLOCK), 0, (hipStream_t)stream, p);
   else hipLaunchKernelGGL(box_match_kernel<MODE_3D>, dim3(B), dim3(DM_BLOCK), 0, (hipStream_t)stream, p);
+  Y3D_LAUNCH_CHECK();
+  return Y3D_OK;
+}
+
+int y3d_confusion_batch(int mode, const void* preds, const unsigned char* keep, int B, int K, const double* meta, int img_h, int img_w,
+                        int single_cls, const float* gt_img, const float* gt_cls, const float* gt_box, int n_gt, int nc, double conf,
+                        double iou_thres, int* matrix, int* status, void* stream) {
+  Y3D_CHECK(mode == MODE_2D || mode == MODE_3D, "confusion_batch: mode must be 0 (2D) or 1 (3D), got %d", mode);
+  Y3D_CHECK(K >= 0 && K <= DM_MAX_DET, "confusion_batch: %d detections per image (at most %d)", K, DM_MAX_DET);
+  Y3D_CHECK(B >= 0 && n_gt >= 0 && nc >= 1 && (K == 0 || preds) && meta && matrix && status, "confusion_batch: bad arguments");
+  Y3D_CHECK(n_gt == 0 || (gt_img && gt_cls && gt_box), "confusion_batch: null gt arrays");
+  Y3D_CHECK(iou_thres >= 0.0, "confusion_batch: iou_thres must not be negative");
+  if (B == 0) return Y3D_OK;
+  ConfP p{};
+  p.preds = preds; p.keep = keep; p.meta = meta; p.gt_img = gt_img; p.gt_cls = gt_cls; p.gt_box = gt_box;
+  p.B = B; p.K = K; p.n_gt = n_gt; p.img_h = img_h; p.img_w = img_w; p.single_cls = single_cls ? 1 : 0; p.nc = nc;
+  p.eps = 1e-7f; p.iou_thres = (float)iou_thres; p.conf = conf; p.matrix = matrix; p.status = status;
+  if (mode == MODE_2D) hipLaunchKernelGGL(confusion_kernel<MODE_2D>, dim3(B), dim3(DM_BLOCK), 0, (hipStream_t)stream, p);
+  else hipLaunchKernelGGL(confusion_kernel<MODE_3D>, dim3(B), dim3(DM_BLOCK), 0, (hipStream_t)stream, p);
+  Y3D_LAUNCH_CHECK();
+  return Y3D_OK;
+}
+
+int y3d_confusion_image(const float* gt_box, const int* gt_cls, int n_gt, const void* det, int det_f64, int n_det, int nc, double conf,
+                        double iou_thres, int* matrix, int* status, void* stream) {
+  Y3D_CHECK(n_gt >= 0 && n_gt <= DM_MAX_GT, "confusion_image: %d labels (at most %d)", n_gt, DM_MAX_GT);
+  Y3D_CHECK(n_det >= 0 && n_det <= DM_MAX_DET, "confusion_image: %d detections (at most %d)", n_det, DM_MAX_DET);
+  Y3D_CHECK(nc >= 1 && matrix && status && (n_gt == 0 || (gt_box && gt_cls)), "confusion_image: bad arguments");
+  Y3D_CHECK(iou_thres >= 0.0, "confusion_image: iou_thres must not be negative");
+  if (det == nullptr) n_det = 0;  // the validators' `detections=None`
+  if (n_gt == 0 && n_det == 0) return Y3D_OK;
+  ConfP p{};
+  p.preds = det; p.gt_cls_i = gt_cls; p.gt_box = gt_box; p.det_f64 = det_f64 ? 1 : 0; p.count_empty = 1;
+  p.B = 1; p.K = n_det; p.n_gt = n_gt; p.nc = nc;
+  p.eps = 1e-7f; p.iou_thres = (float)iou_thres; p.conf = conf; p.matrix = matrix; p.status = status;
+  hipLaunchKernelGGL(confusion_kernel<MODE_XYXY>, dim3(1), dim3(DM_BLOCK), 0, (hipStream_t)stream, p);
   Y3D_LAUNCH_CHECK();
   return Y3D_OK;
 }

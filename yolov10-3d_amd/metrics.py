@@ -10,6 +10,9 @@ one launch per `get_stats` computes every class's AP and recall / precision curv
 Deliberate tie rules where the reference is implementation-defined (its argsorts are unstable quicksorts): an IoU tie between two
 class-matched labels of one detection goes to the higher gt index; detections of equal confidence keep accumulation order (image,
 then row).  Limits: `max_gts()` gts and `max_dets()` detections per image.
+
+`ConfusionMatrix` (utils/metrics.py:281) is what both validators feed when `plots` is on (the default): one launch per validation
+batch adds into an int32 matrix on the device; its tie rules are in the class docstring.
 """
 from __future__ import annotations
 
@@ -424,3 +427,150 @@ class BoxStats:
         if isinstance(metrics, Det3dMetrics):
             metrics.metric3d = metric3d
         return metrics.results_dict
+
+
+def _targets(batch, who):
+    """batch_idx (n), cls (n), bboxes (n, 4) of a collated batch as contiguous float32 device tensors"""
+    idx = batch["batch_idx"].detach().reshape(-1)
+    cls = batch["cls"].detach().reshape(-1)
+    box = batch["bboxes"].detach().reshape(-1, 4)
+    _on_device(who, idx, cls, box)
+    if not (idx.numel() == cls.numel() == box.shape[0]):
+        raise Y3DError(f"{who}: batch_idx / cls / bboxes disagree ({idx.numel()}, {cls.numel()}, {box.shape[0]})")
+    return idx.float().contiguous(), cls.float().contiguous(), box.float().contiguous()
+
+
+class ConfusionMatrix:
+    """utils/metrics.py:281 for detection, accumulated on the device (csrc/det_metrics.hip, `y3d_confusion_batch`).
+
+        cm = ConfusionMatrix(nc=80, conf=args.conf)
+        for batch in loader:
+            cm.update_2d(preds, batch)              # what DetectionValidator.update_metrics feeds it (models/yolo/detect/val.py:137, :151)
+            # or cm.update_3d(rows, keep, batch)    # YOLOv10_3DDetectionValidator.update_metrics (models/yolov10_3D/val.py:138, :156)
+        cm.matrix                                   # (nc + 1, nc + 1) float64 numpy [predicted, true], index nc = background
+
+    `update_*` take exactly what `BoxStats.update_*` take, launch one kernel per batch and never wait for the device; like the
+    validators they skip an image without gts.  `process_batch(detections, gt_bboxes, gt_cls)` is the reference's method on device
+    tensors (prepared xyxy boxes, one image).  Reading `matrix` is the only read-back; it raises when an image had more than
+    `max_gts()` gts or a class lay outside [0, nc).
+
+    A detection takes part iff its confidence > conf (strict; float32 for 2D rows and float32 drop-in detections, float64 for 3D rows
+    and float64 drop-in detections); pairs with IoU > float32(iou_thres) are matched whatever their classes: each detection keeps its
+    best gt, then each gt keeps the best of the detections that chose it.  An image without a single match does not count its
+    detections (the reference's `if n:`).  Deliberate tie rules where the reference is implementation-defined (its argsort is an
+    unstable quicksort), what a stable sort, reversed, gives: an IoU tie between two gts of one detection goes to the higher gt index,
+    an IoU tie between two detections on one gt goes to the higher detection index.  `plot()` and task="classify" are not supported."""
+
+    def __init__(self, nc, conf=0.25, iou_thres=0.45, task="detect", device=None):
+        if task != "detect":
+            raise Y3DError(f"ConfusionMatrix: task {task!r} is not supported (detect only)")
+        self.device = torch.device(device if device is not None else "cuda")
+        if self.device.type != "cuda":
+            raise Y3DError(f"ConfusionMatrix accumulates on a HIP device, not {self.device}")
+        self.task, self.nc = task, int(nc)
+        if self.nc < 1:
+            raise Y3DError(f"ConfusionMatrix: nc = {nc}")
+        self.conf = 0.25 if conf in (None, 0.001) else conf  # apply 0.25 if default val conf is passed (utils/metrics.py:304)
+        self.iou_thres = iou_thres
+        if not float(self.iou_thres) >= 0.0:
+            raise Y3DError(f"ConfusionMatrix: iou_thres = {iou_thres} (must not be negative)")
+        self._m = self._status = None
+
+    def _buffers(self):
+        if self._m is None:
+            self._m = torch.zeros(self.nc + 1, self.nc + 1, dtype=torch.int32, device=self.device)
+            self._status = torch.zeros(2, dtype=torch.int32, device=self.device)
+        return self._m, self._status
+
+    def reset(self):
+        if self._m is not None:
+            self._m.zero_()
+            self._status.zero_()
+
+    @property
+    def matrix(self):
+        """(nc + 1, nc + 1) float64 numpy, the reference's dtype; the one read-back"""
+        m, status = self._buffers()
+        h = torch.cat((status, m.reshape(-1))).cpu().numpy()
+        if h[0] > 0:
+            raise Y3DError(f"ConfusionMatrix: an image has {int(h[0])} gts; at most {max_gts()} are supported")
+        if h[1]:
+            raise Y3DError(f"ConfusionMatrix: a class outside [0, {self.nc}) was met")
+        return h[2:].reshape(self.nc + 1, self.nc + 1).astype(np.float64)
+
+    def tp_fp(self):
+        """utils/metrics.py:382: true and false positives per class, background removed"""
+        m = self.matrix
+        tp = m.diagonal()
+        fp = m.sum(1) - tp
+        return tp[:-1], fp[:-1]
+
+    def plot(self, *a, **k):
+        raise Y3DError("ConfusionMatrix.plot: plotting is not supported; read .matrix")
+
+    def print(self):
+        for row in self.matrix:
+            print(" ".join(map(str, row)))
+
+    def process_batch(self, detections, gt_bboxes, gt_cls):
+        """utils/metrics.py:319: detections (N, 6) [x1, y1, x2, y2, conf, cls] or None, gt_bboxes (M, 4) xyxy, gt_cls (M); one image"""
+        who = "ConfusionMatrix.process_batch"
+        _on_device(who, gt_cls)
+        n_gt = int(gt_cls.shape[0])
+        det, n_det, f64 = None, 0, 0
+        if detections is not None:
+            _on_device(who, detections)
+            if detections.dim() != 2 or detections.shape[1] != 6:
+                raise Y3DError(f"{who}: expected (N, 6) detections, got {tuple(detections.shape)} (oriented boxes are not supported)")
+            f64 = int(detections.dtype == torch.float64)
+            det = detections.detach().contiguous() if f64 else detections.detach().float().contiguous()
+            n_det = int(det.shape[0])
+        if n_gt > max_gts() or n_det > max_dets():
+            raise Y3DError(f"{who}: {n_gt} labels / {n_det} detections; at most {max_gts()} / {max_dets()} per image")
+        gb = gc = None
+        if n_gt:
+            _on_device(who, gt_bboxes)
+            gb = gt_bboxes.detach().reshape(-1, 4).float().contiguous()
+            gc = gt_cls.detach().reshape(-1).to(torch.int32).contiguous()
+            if gb.shape[0] != n_gt:
+                raise Y3DError(f"{who}: {n_gt} classes but {gb.shape[0]} boxes")
+        m, status = self._buffers()
+        lib().confusion_image(gb.data_ptr() if n_gt else None, gc.data_ptr() if n_gt else None, n_gt, det.data_ptr() if det is not None and n_det else None,
+                              f64, n_det, self.nc, float(self.conf), float(self.iou_thres), m.data_ptr(), status.data_ptr(), ops.stream())
+
+    def _launch(self, mode, preds, keep, meta, imgsz, tgt, single_cls):
+        idx, cls, box = tgt
+        m, status = self._buffers()
+        B, K = int(preds.shape[0]), int(preds.shape[1])
+        lib().confusion_batch(mode, preds.data_ptr() if K else None, keep.data_ptr() if keep is not None and K else None, B, K, meta.data_ptr(),
+                              int(imgsz[0]), int(imgsz[1]), int(bool(single_cls)), idx.data_ptr(), cls.data_ptr(), box.data_ptr(), idx.numel(),
+                              self.nc, float(self.conf), float(self.iou_thres), m.data_ptr(), status.data_ptr(), ops.stream())
+
+    def update_2d(self, preds, batch, single_cls=False):
+        """the confusion-matrix part of DetectionValidator.update_metrics; arguments as `BoxStats.update_2d`"""
+        who = "ConfusionMatrix.update_2d"
+        if preds.dim() != 3 or preds.shape[-1] != 6:
+            raise Y3DError(f"{who}: expected (B, K, 6) predictions, got {tuple(preds.shape)}")
+        BoxStats._check_k(preds, who)
+        _on_device(who, preds)
+        B = int(preds.shape[0])
+        tgt = _targets(batch, who)
+        imgsz = tuple(batch["img"].shape[2:]) if "img" in batch else tuple(batch["imgsz"])
+        ori = _host_rows(batch["ori_shape"], B, who)[:, :2]
+        rp = _host_rows(batch["ratio_pad"], B, who)
+        meta = _upload(np.concatenate((ori, rp[:, [0, 2, 3]]), 1), self.device)
+        self._launch(0, preds.detach().float().contiguous(), None, meta, imgsz, tgt, single_cls)
+
+    def update_3d(self, rows, keep, batch, single_cls=False):
+        """the confusion-matrix part of YOLOv10_3DDetectionValidator.update_metrics; arguments as `BoxStats.update_3d`"""
+        who = "ConfusionMatrix.update_3d"
+        if rows.dim() != 3 or rows.shape[-1] != 14 or keep is None or tuple(keep.shape) != tuple(rows.shape[:2]):
+            raise Y3DError(f"{who}: expected (B, K, 14) rows and a (B, K) keep mask, got {tuple(rows.shape)} / "
+                           f"{None if keep is None else tuple(keep.shape)}")
+        BoxStats._check_k(rows, who)
+        _on_device(who, rows, keep)
+        B = int(rows.shape[0])
+        tgt = _targets(batch, who)
+        meta = _upload(_host_rows(batch["ori_shape"], B, who)[:, :2], self.device)
+        self._launch(1, rows.detach().to(torch.float64).contiguous(), keep.detach().to(torch.bool).contiguous().view(torch.uint8), meta,
+                     (0, 0), tgt, single_cls)

@@ -1,0 +1,200 @@
+"""One-call validators: a model and a split in, the reference validators' results out.
+
+    results = val.Validator3d(model, kitti_root)()                      # YOLOv10_3DDetectionValidator (models/yolov10_3D/val.py)
+    results = val.Validator2d(model, yolo2d.RectSplit(img_dir, 640))()  # DetectionValidator with the YOLOv10 post-process
+
+Both run the stages the library already has, in the reference's order, per batch: the validation batch builder (`kitti.build_batch` /
+`json3d.build_batch` / `yolo2d.build_batch`, mode="val"), the eval forward (through `graph.GraphedForward` with graph=True), the
+NMS-free post-process, `metrics.BoxStats.update_*` and, with `plots` (the reference's default), `metrics.ConfusionMatrix.update_*`.
+The batches are built with compact=True (the builders' one read-back of the per-image label counts): `BoxStats` counts every row of
+`batch["cls"]` as a target, so the padding rows of the static layout must not reach it.  Beyond that nothing is copied to the host
+inside the loop and no stage waits for the device; the 3D rows are read back once after the last batch.  After the call: `metrics` (a `Det3dMetrics`, which both validators of this fork build, with
+`speed` and `confusion_matrix` set as `finalize_metrics` sets them), `confusion_matrix`, `seen`, `nt_per_class`, `speed` (ms per
+image under the reference's keys, from device events read once after the loop; `loss` stays 0.0) and, for 3D, `results`.
+There is no host fallback: the model must live on a HIP device."""
+from __future__ import annotations
+
+import os
+
+import numpy as np
+import torch
+
+from . import json3d, kitti, kitti_eval, metrics, yolo2d
+from ._lib import Y3DError
+from .graph import GraphedForward
+from .predict import _mean_sizes, raw_rows, raw_rows3d
+
+
+def _is_3d(model):
+    from .modules import v10Detect3d
+    return isinstance(model.model[-1], v10Detect3d)
+
+
+class _Validator:
+    def __init__(self, model, want_3d, conf, max_det, single_cls, plots, graph):
+        who = type(self).__name__
+        if not hasattr(model, "model") or _is_3d(model) != want_3d:
+            raise Y3DError(f"{who}: a {'3D' if want_3d else '2D'} model is expected ({'Validator2d' if want_3d else 'Validator3d'} takes the "
+                           f"{'2D' if want_3d else '3D'} models)")
+        self.device = next(model.parameters()).device
+        if self.device.type != "cuda":
+            raise Y3DError(f"{who}: the model must live on a HIP device, not {self.device} (no host fallback)")
+        self.model, self.nc = model, int(model.yaml["nc"])
+        self.conf, self.max_det, self.single_cls, self.plots, self.graph = float(conf), int(max_det), bool(single_cls), bool(plots), bool(graph)
+        self._graphs = {}
+        self.metrics = self.confusion_matrix = self.nt_per_class = None
+        self.seen = 0
+        self.speed = {"preprocess": 0.0, "inference": 0.0, "loss": 0.0, "postprocess": 0.0}
+
+    def _raw(self, img):
+        """img (B, H, W, 3) uint8 -> the post-processed rows of the eval forward, eagerly or replayed from one hipGraph per shape"""
+        if not self.graph:
+            with torch.no_grad():
+                return self._rows(img)
+        key = tuple(img.shape)
+        if key not in self._graphs:
+            self._graphs[key] = GraphedForward(self._rows, img)
+        return self._graphs[key](img)
+
+    def _start(self):
+        self.stats = metrics.BoxStats(self.nc, single_cls=self.single_cls, device=self.device)
+        self.confusion_matrix = metrics.ConfusionMatrix(self.nc, conf=self.conf, device=self.device)
+        self.seen = 0
+        self._events = []
+
+    def _mark(self):
+        e = torch.cuda.Event(enable_timing=True)
+        e.record()
+        return e
+
+    def _finish(self, metric3d):
+        self.metrics = metrics.Det3dMetrics(names=self.model.names)
+        res = self.stats.get_stats(self.metrics, metric3d)  # the first wait for the device
+        self.seen, self.nt_per_class = self.stats.seen, self.stats.nt_per_class
+        ms = np.zeros(3)
+        for ev in self._events:
+            ms += [a.elapsed_time(b) for a, b in zip(ev[:-1], ev[1:])]
+        per = ms / max(self.seen, 1)
+        self.speed = {"preprocess": float(per[0]), "inference": float(per[1]), "loss": 0.0, "postprocess": float(per[2])}
+        self.metrics.speed = self.speed  # finalize_metrics (models/yolo/detect/val.py:162-165)
+        self.metrics.confusion_matrix = self.confusion_matrix
+        return res
+
+    def __call__(self):
+        was_training = self.model.training
+        self.model.eval()
+        try:
+            return self._run()
+        finally:
+            self.model.train(was_training)
+
+
+class Validator3d(_Validator):
+    """`YOLOv10_3DDetectionValidator` for a KITTI root or split file (dataset="kitti") or a Waymo / Omni3D split JSON.
+
+    Per batch of `batch` consecutive dataset positions: the val batch, the eval forward, `v10_3Dpostprocess`,
+    `kitti.decode_preds_device` with the dataset's mean sizes and threshold = conf, `BoxStats.update_3d`, and
+    `ConfusionMatrix.update_3d` when `plots`.  The kept rows become `self.results` ({im_file: rows}) with one read-back after the loop.
+    KITTI: `metrics/3D` = `kitti_eval.get_stats(results, label_dir or <root>/training/label_2)`.  Waymo and Omni3D: the reference's
+    metric shells out to a TensorFlow environment, so `metrics/3D` keeps `Det3dMetrics`' initial value, 0.
+    `resolution` applies to KITTI; the other two datasets have the fixed `json3d.RESOLUTION`.  `speed`: preprocess = the batch builder,
+    inference = the eval forward (with graph=True the replay, which includes `v10_3Dpostprocess`), postprocess = the rest."""
+
+    def __init__(self, model, root_or_split, args=None, dataset="kitti", batch=16, conf=0.001, max_det=50, single_cls=False, plots=True,
+                 resolution=kitti.RESOLUTION, label_dir=None, graph=False):
+        super().__init__(model, True, conf, max_det, single_cls, plots, graph)
+        if dataset not in ("kitti", "waymo", "omni3d"):
+            raise Y3DError(f"Validator3d: dataset {dataset!r} (kitti, waymo or omni3d)")
+        if int(batch) < 1:
+            raise Y3DError(f"Validator3d: batch = {batch}")
+        self.source, self.dataset, self.batch = root_or_split, dataset, int(batch)
+        self.args = args if args is not None else kitti.data_args()
+        self.resolution = (int(resolution[0]), int(resolution[1])) if dataset == "kitti" else json3d.RESOLUTION
+        self.label_dir = label_dir
+        self.mean_sizes = kitti.CLS_MEAN_SIZE if dataset == "kitti" else json3d.CLS_MEAN_SIZE[dataset]
+        self.results = {}
+
+    def _rows(self, img):
+        return raw_rows3d(self.model, img.permute(0, 3, 1, 2), self.max_det)
+
+    def _dataset(self):
+        """-> (number of images, position -> the original image's (cu, cv, fu, fv, tx, ty), as the reference's get_calib holds them)"""
+        if self.dataset == "kitti":
+            data, ids = kitti._split(self.source, "val")
+            return len(ids), lambda pos: kitti.calib_params(kitti.read_calib(os.path.join(data, "calib", f"{ids[pos]:06d}.txt"))), data
+        sp = json3d.read_split(self.source, self.dataset, bool(getattr(self.args, "overfit", False)))
+
+        def calib(pos):
+            P = sp.P2(sp.ids[pos])
+            return (P[0, 2], P[1, 2], P[0, 0], P[1, 1], P[0, 3] / -P[0, 0], P[1, 3] / -P[1, 1])
+
+        return len(sp), calib, None
+
+    def _batch(self, idx):
+        if self.dataset == "kitti":
+            return kitti.build_batch(self.source, idx, self.args, self.device, mode="val", compact=True, resolution=self.resolution)
+        return json3d.build_batch(self.source, idx, self.args, self.device, dataset=self.dataset, mode="val", compact=True)
+
+    def _run(self):
+        n, calib, data = self._dataset()
+        self._start()
+        ms = _mean_sizes(self.mean_sizes, self.device)
+        files, kept = [], []
+        for s in range(0, n, self.batch):
+            idx = list(range(s, min(s + self.batch, n)))
+            t0 = self._mark()
+            b = self._batch(idx)
+            t1 = self._mark()
+            raw = self._raw(b["img"])
+            t2 = self._mark()
+            c6 = metrics._upload(np.array([calib(p) for p in idx], np.float64), self.device)
+            inv = metrics._upload(np.stack([np.asarray(i["trans_inv"], np.float64).reshape(2, 3) for i in b["info"]]), self.device)
+            rows, keep = kitti.decode_preds_device(raw, c6, b["ratio_pad"], inv, threshold=self.conf, cls_mean_size=ms)
+            self.stats.update_3d(rows, keep, b)
+            if self.plots:
+                self.confusion_matrix.update_3d(rows, keep, b, single_cls=self.single_cls)
+            self._events.append((t0, t1, t2, self._mark()))
+            files += list(b["im_file"])
+            kept.append(torch.cat((rows, keep.unsqueeze(-1).to(rows.dtype)), -1))
+        self.results = {}
+        if kept:  # the one read-back of the rows
+            host = torch.cat(kept).cpu()
+            self.results = {f: host[i, host[i, :, 14] != 0, :14].tolist() for i, f in enumerate(files)}
+        metric3d = 0
+        if self.dataset == "kitti":
+            metric3d = kitti_eval.get_stats(self.results, self.label_dir or os.path.join(data, "label_2"))
+        return self._finish(metric3d)
+
+
+class Validator2d(_Validator):
+    """`DetectionValidator` as the YOLOv10 validator runs it, on a `yolo2d.RectSplit`.
+
+    Per rect batch of `rect_split.batches()`: `yolo2d.build_batch(mode="val")`, the eval forward, `v10postprocess` + `xywh2xyxy`
+    (`predict.raw_rows`), `BoxStats.update_2d`, and `ConfusionMatrix.update_2d` when `plots`.  Returns `get_stats(Det3dMetrics(...))`:
+    the fork's own validator builds `Det3dMetrics` for the 2D models too, so `metrics/3D` is 0.  `speed` as `Validator3d`."""
+
+    def __init__(self, model, rect_split, args=None, conf=0.001, max_det=300, single_cls=False, plots=True, graph=False):
+        super().__init__(model, False, conf, max_det, single_cls, plots, graph)
+        if not isinstance(rect_split, yolo2d.RectSplit):
+            raise Y3DError("Validator2d: a yolo2d.RectSplit is expected")
+        self.split = rect_split
+        self.args = args if args is not None else yolo2d.data_args()
+
+    def _rows(self, img):
+        return raw_rows(self.model, img.permute(0, 3, 1, 2), self.max_det)
+
+    def _run(self):
+        self._start()
+        for items in self.split.batches():
+            t0 = self._mark()
+            b = yolo2d.build_batch(self.split, items, self.args, self.device, mode="val", compact=True)
+            t1 = self._mark()
+            preds = self._raw(b["img"])
+            t2 = self._mark()
+            view = {k: v for k, v in b.items() if k != "img"}  # the image is (B, H, W, 3) uint8 here: BoxStats reads the canvas from imgsz
+            view["imgsz"] = tuple(int(v) for v in b["resized_shape"][0])
+            self.stats.update_2d(preds, view)
+            if self.plots:
+                self.confusion_matrix.update_2d(preds, view, single_cls=self.single_cls)
+            self._events.append((t0, t1, t2, self._mark()))
+        return self._finish(0)
