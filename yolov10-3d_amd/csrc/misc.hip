@@ -28,8 +28,9 @@ __global__ void maxpool_fwd_kernel(const T* __restrict__ x, long xsb, long xsh, 
     int h = rem / W, w = rem - h * W;
     float best[CE];
     int bi[CE];
+    const int first = max(0, pad - h) * k + max(0, pad - w);  // first in-map tap: the arg-max of a window of -inf only (ATen's maxidx start)
 #pragma unroll
-    for (int j = 0; j < CE; ++j) { best[j] = -INFINITY; bi[j] = 0; }
+    for (int j = 0; j < CE; ++j) { best[j] = -INFINITY; bi[j] = first; }
     for (int r = 0; r < k; ++r) {
       int hh = h - pad + r;
       if (hh < 0 || hh >= H) continue;
