@@ -608,7 +608,8 @@ int y3d_attn_bwd(int dtype, const void* qkv, int64_t qsw, const void* out, int64
   dim3 grid(cdiv(N, 128), B * nh), block(128);
   hipStream_t st = (hipStream_t)stream;
   const int n32 = (N + 31) & ~31;
-  if (dtype == Y3D_BF16 && y3d_get_tile_kernels() && qsw % 4 == 0 && osw % 4 == 0 && dsw % 4 == 0 && gsw % 4 == 0 && (dv_extra == nullptr || esw % 1 == 0) &&
+  // dv_extra is read element by element in every kernel: esw and its address need no alignment
+  if (dtype == Y3D_BF16 && y3d_get_tile_kernels() && qsw % 4 == 0 && osw % 4 == 0 && dsw % 4 == 0 && gsw % 4 == 0 &&
       ((uintptr_t)qkv & 15) == 0 && ((uintptr_t)out & 7) == 0 && ((uintptr_t)dout & 7) == 0 && ((uintptr_t)dqkv & 7) == 0) {
     static bool attr_set = false;
     if (!attr_set) {

@@ -403,7 +403,7 @@ int y3d_proj_group_fwd_bn_mfma(int nb, int cin, const void* y_pre, int64_t ysw, 
                                const int* couts, const float* scale, const float* shift, int act, void* out, int64_t osw, int64_t P,
                                void* stream) {
   Y3D_CHECK(nb >= 1 && nb <= PB_MAXB && (cin == 64 || cin == 128), "proj_group_fwd_bn_mfma: 1..16 branches of 64 or 128 channels");
-  Y3D_CHECK(y_pre && out && scale && shift && P >= 1 && ysw % 8 == 0 && ((uintptr_t)y_pre & 15) == 0, "proj_group_fwd_bn_mfma: null / misaligned argument");
+  Y3D_CHECK(y_pre && out && w && b && scale && shift && P >= 1 && ysw % 8 == 0 && ((uintptr_t)y_pre & 15) == 0, "proj_group_fwd_bn_mfma: null / misaligned argument");
   PFP p;
   p.y = (const bf16_t*)y_pre; p.out = (bf16_t*)out;
   int off = 0;

@@ -267,8 +267,10 @@ extern "C" {
 static int proj_group_fwd_impl(int dtype, int nb, int cin, const void* x, int64_t xsw, const int* xoff, const float* const* w,
                                const float* const* b, const int* couts, void* y, int64_t ysw, int64_t P, BNP bn, void* stream) {
   ProjG g;
+  Y3D_CHECK(w && b && x && y && xoff && couts, "proj_group_fwd: null argument (the kernel adds b[br][o] without a test: a bias is required)");
   int ctot = fill(g, nb, cin, w, b, nullptr, nullptr, xoff, couts);
   if (ctot < 0) return ctot;
+  for (int i = 0; i < nb; ++i) Y3D_CHECK(w[i] && b[i], "proj_group_fwd: branch %d has no weight / bias", i);
   Y3D_CHECK(dtype == Y3D_BF16 || dtype == Y3D_F32, "proj_group_fwd: bad dtype");
   Y3D_CHECK(cin % (dtype == Y3D_BF16 ? 8 : 4) == 0 && ysw >= ctot, "proj_group_fwd: channel alignment");
   dim3 grid(cdiv(P, 32 * 4), 1, nb);  // PXB = 4 pixels per thread
@@ -296,8 +298,12 @@ int y3d_proj_group_fwd_bn(int dtype, int nb, int cin, const void* y_pre, int64_t
 int y3d_proj_group_bwd_data(int dtype, int nb, int cin, const void* dy, int64_t dsw, const int* xoff, const float* const* w,
                             const int* couts, void* dx, int64_t xsw, int64_t P, void* stream) {
   ProjG g;
+  Y3D_CHECK(w && dy && dx && xoff && couts, "proj_group_bwd_data: null argument");
   int ctot = fill(g, nb, cin, w, nullptr, nullptr, nullptr, xoff, couts);
   if (ctot < 0) return ctot;
+  // as the forward: the kernel stores 16-byte chunks at c < cin and reads ctot gradients per pixel
+  Y3D_CHECK(dtype == Y3D_BF16 || dtype == Y3D_F32, "proj_group_bwd_data: bad dtype");
+  Y3D_CHECK(cin % (dtype == Y3D_BF16 ? 8 : 4) == 0 && dsw >= ctot, "proj_group_bwd_data: channel alignment");
   long total = P * (cin / (dtype == Y3D_BF16 ? 8 : 4));
   dim3 grid(ew_grid(total), 1, nb);
   size_t sm = (size_t)24 * cin * 4;
@@ -318,8 +324,12 @@ static int proj_group_bwd_weight_impl(int dtype, int nb, int cin, const void* x,
                                       void* stream) {
   ProjG g;
   const float* dummy[MAXB] = {nullptr};
+  Y3D_CHECK(x && dy && slab && bslab && dw && db && xoff && couts, "proj_group_bwd_weight: null argument");
   int ctot = fill(g, nb, cin, dummy, nullptr, dw, db, xoff, couts);
   if (ctot < 0) return ctot;
+  // as the forward: the kernel loads 16-byte chunks at c < cin and reads ctot gradients per pixel
+  Y3D_CHECK(dtype == Y3D_BF16 || dtype == Y3D_F32, "proj_group_bwd_weight: bad dtype");
+  Y3D_CHECK(cin % (dtype == Y3D_BF16 ? 8 : 4) == 0 && dsw >= ctot, "proj_group_bwd_weight: channel alignment");
   int nblk = y3d_proj_group_blocks(P);
   int ppb = (int)((P + nblk - 1) / nblk);
   Y3D_CHECK((long)ppb * (xsw > dsw ? xsw : dsw) < (1L << 31), "proj_group_bwd_weight: a block's pixel range exceeds 32-bit element offsets");
