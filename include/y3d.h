@@ -457,6 +457,20 @@ int y3d_kitti_encode_labels(const double* rec, const int* img_i, const double* i
                             double* bboxes, float* center_2d, float* size_2d, double* center_3d, double* size_3d, double* depth,
                             int64_t* heading_bin, double* heading_res, float* batch_idx, int* counts, double* calib, double* ratio_pad,
                             void* stream);
+/* Batch plan over a KITTI split held on the device (kitti_cache.hip, kitti.DeviceSplit), one thread per image: the per-image tables of
+ * y3d_kitti_image_aug and y3d_kitti_encode_labels from the split's frame tables and one table of draws.  Frame tables, on the device,
+ * indexed by dataset position (N frames): img_off (N) int64 byte offsets into arena (every frame (H, W, 3) uint8 RGB); frame_hw (N, 2)
+ * int32 (H, W); rec_span (N, 2) int32 = (first row, line count) in the split's label records; P2 (N, 2, 12) float32 = the calibration
+ * as read and the one of the mirrored image.  draws (B, 16) float64 on the device, draws_host the same table in host memory:
+ * [position, mixup partner or -1, flip, crop scale, trans (6), trans_inv (6)]; positions and partners outside [0, N) are refused from
+ * draws_host before the launch.  Outputs, on the device: src / src2 (B) pointers = arena + img_off (src2: NULL without a partner), hw
+ * (B, 2), flip (B) int32, trans_inv (B, 6) as y3d_kitti_image_aug takes them; img_i (B, 7) = (first row, lines, partner's first row,
+ * partner's lines, flip, W, H) and img_f (B, 19) = (P2[position][flip] widened, trans, scale) as y3d_kitti_encode_labels takes them,
+ * the rows counted in the split's records; mixed (B) uint8. */
+int y3d_kitti_plan_batch(const int64_t* img_off, const int* frame_hw, const int* rec_span, const float* P2, int N,
+                         const unsigned char* arena, const double* draws_host, const double* draws, int B, const unsigned char** src,
+                         const unsigned char** src2, int* hw, int* flip, double* trans_inv, int* img_i, double* img_f,
+                         unsigned char* mixed, void* stream);
 /* Input pipeline, label side of WaymoDataset.__getitem__ (data/datasets/waymo.py:186-290, load_object :292-372; dataset = 0) and
  * Omni3Dataset.__getitem__ (data/datasets/omni3d.py:175-279, load_object :281-352; dataset = 1) with their collate_fn, one workgroup
  * per image (json3d_labels.hip), in the plan and the output layout of y3d_kitti_encode_labels.  rec (N, 24) float64 object records,

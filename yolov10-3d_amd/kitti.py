@@ -5,9 +5,10 @@ from `_prepare_preds` (models/yolov10_3D/val.py:210-214) on CPU with a python lo
 residual -> alpha, size residual + class mean size, centre back-projection through the (inverse-affine'd) calibration, rotation_y,
 score = sigmoid(cls) * exp(-depth log-variance), threshold.  Here it is one launch over all B*K rows (`y3d_kitti_decode`).
 
-Further down: the one-to-many depth fusion, the image and label sides of the training / validation batches (`build_batch`), the
-unlabelled test split (`build_test_batch`, which `predict.Predictor3d.predict_split` reads) and `save_results`, the writer of the
-files a KITTI submission and `kitti_eval.eval_from_scratch` read.
+Further down: the one-to-many depth fusion, the image and label sides of the training / validation batches (`build_batch`), the same
+batches from a split decoded once and kept on the device (`DeviceSplit`, `plan_batch`, `epoch_indices`), the unlabelled test split
+(`build_test_batch`, which `predict.Predictor3d.predict_split` reads) and `save_results`, the writer of the files a KITTI submission
+and `kitti_eval.eval_from_scratch` read.
 """
 from __future__ import annotations
 
@@ -388,10 +389,14 @@ def build_batch(root_or_split_file, indices, args, device, mode="train", compact
     images mixed / mirrored / cropped by augment_images and the labels encoded by encode_labels.  root_or_split_file: a split file
     (ImageSets/<split>.txt) or the KITTI root (then ImageSets/<mode>.txt).  -> every key collate_fn returns except ori_img and depth_map;
     the per-box keys in encode_labels' static layout, or with compact=True (one read-back of the counts) in collate_fn's ragged shapes.
-    img_mode "uint8": (B, H, W, 3) uint8 for the stem; "float": the reference's (B, 3, H, W) float32."""
+    img_mode "uint8": (B, H, W, 3) uint8 for the stem; "float": the reference's (B, 3, H, W) float32.
+    root_or_split_file may also be a `DeviceSplit`: the same batch from the split held on the device, without any file access."""
     import os
     import numpy as np
     from PIL import Image
+    if isinstance(root_or_split_file, DeviceSplit):  # the split is resident on the device: no file is touched
+        root_or_split_file.check_device(device)
+        return root_or_split_file.build_batch(indices, args, mode=mode, compact=compact, img_mode=img_mode, resolution=resolution)
     if getattr(args, "load_depth_maps", False):
         raise Y3DError("build_batch: depth maps (load_depth_maps) are not supported")
     if torch.device(device).type != "cuda":
@@ -450,6 +455,237 @@ def build_batch(root_or_split_file, indices, args, device, mode="train", compact
     else:
         batch.update({k: lab[k] for k in PER_BOX})
     return batch
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# the split resident on the device: decoded once, then a batch is the draws, one small upload and three launches
+# ------------------------------------------------------------------------------------------------------------------------------
+_DRAW_W = 16  # a row of the draw table: position, partner (-1: none), flip, scale, trans (6), trans_inv (6)
+_ALIGN = 16  # every frame starts on a multiple of 16 bytes of the arena
+PLAN_TABLES = (("src", torch.int64, ()), ("src2", torch.int64, ()), ("hw", torch.int32, (2,)), ("flip", torch.int32, ()),
+         ("trans_inv", torch.float64, (6,)), ("img_i", torch.int32, (7,)), ("img_f", torch.float64, (19,)), ("mixed", torch.uint8, ()))
+
+
+def epoch_indices(n, batch, shuffle=True, seed=0, drop_last=False):
+    """The batches of one epoch over n dataset positions: a list of index lists that covers every position once (drop_last: without the
+    short last batch).  shuffle: a permutation from a generator of its own seeded with `seed`, so np.random's global state — the stream
+    `sample_augment` replays — is not touched."""
+    import numpy as np
+    n, batch = int(n), int(batch)
+    if batch < 1 or n < 0:
+        raise Y3DError(f"epoch_indices: batch = {batch}, n = {n}")
+    order = np.random.RandomState(int(seed)).permutation(n) if shuffle else np.arange(n)
+    out = [[int(i) for i in order[s:s + batch]] for s in range(0, n, batch)]
+    if drop_last and out and len(out[-1]) < batch:
+        out.pop()
+    return out
+
+
+def plan_batch(split, draws, draws_dev=None, out=None):
+    """The per-image tables of `y3d_kitti_image_aug` and `y3d_kitti_encode_labels` for a table of draws over a DeviceSplit, one HIP
+    launch (`y3d_kitti_plan_batch`).  draws: (B, 16) float64 on the host (numpy or tensor), rows [position, partner or -1, flip, scale,
+    trans (6), trans_inv (6)]; draws_dev: the same table on the device (uploaded here when None).  Positions and partners outside the
+    split are refused from the host table.  out: optionally the eight output tensors (at least B rows each; the first B are written).
+    -> dict src, src2 (B) int64, hw (B, 2) int32, flip (B) int32, trans_inv (B, 6) float64, img_i (B, 7) int32, img_f (B, 19) float64,
+    mixed (B) uint8."""
+    host = torch.as_tensor(draws)
+    if host.dim() != 2 or host.shape[1] != _DRAW_W or host.dtype != torch.float64 or host.is_cuda or not host.is_contiguous():
+        raise Y3DError(f"plan_batch: the draws are a contiguous (B, {_DRAW_W}) float64 table on the host, got {tuple(host.shape)} {host.dtype}")
+    B, dev = host.shape[0], split.device
+    if draws_dev is None:
+        draws_dev = host.to(dev)
+    if draws_dev.shape != host.shape or draws_dev.dtype != torch.float64 or draws_dev.device != dev or not draws_dev.is_contiguous():
+        raise Y3DError("plan_batch: the device copy of the draws must match the host table and live on the split's device")
+    if out is None:
+        out = {k: torch.empty(B, *s, dtype=dt, device=dev) for k, dt, s in PLAN_TABLES}
+    for k, dt, s in PLAN_TABLES:
+        t = out[k]
+        if t.dtype != dt or t.device != dev or t.dim() != 1 + len(s) or t.shape[0] < B or tuple(t.shape[1:]) != s or not t.is_contiguous():
+            raise Y3DError(f"plan_batch: output {k} must be a contiguous ({B}+, {', '.join(map(str, s))}) {dt} tensor on {dev}")
+    lib().kitti_plan_batch(split.img_off.data_ptr(), split.frame_hw.data_ptr(), split.rec_span.data_ptr(), split.P2.data_ptr(), len(split),
+                           split.arena.data_ptr(), host.data_ptr(), draws_dev.data_ptr(), B, *[out[k].data_ptr() for k, _, _ in PLAN_TABLES],
+                           ops.stream())
+    return out
+
+
+class DeviceSplit:
+    """A KITTI split decoded once and held on the device: `DeviceSplit(root_or_split_file, mode)` resolves the split as build_batch does,
+    checks the bytes it needs against `max_bytes` (default: half of the device's free memory) from the PNG headers alone, then decodes
+    every frame with `min(workers, 16)` threads into one uint8 arena (`arena`: each frame (H, W, 3) RGB at a multiple of 16 bytes,
+    uploaded in large pinned chunks) and uploads the frame tables, indexed by dataset position: `img_off` (N) int64, `frame_hw` (N, 2)
+    int32 (H, W), `rec` (R, 16) float64 = label_records of every frame in order, `rec_span` (N, 2) int32 (first row, lines), `P2`
+    (N, 2, 12) float32 (as read; flip_calib of it), `mean_size`.  What sample_augment's frame_info needs stays on the host as well.
+
+    `build_batch` then returns what `build_batch(path, ...)` returns, bit for bit, without touching a file: the draws, one non-blocking
+    upload of the draw table from a ring of pinned buffers and three launches (plan_batch, the image augmentation, the label encoder).
+    `frame_info` knows every frame's true size, as the reference's dataset does; the path-based builder knows those of the batch's own
+    frames only, so the two draw the same mixup partners when frames that share a calibration share a size."""
+
+    RING = 4  # pinned draw tables in flight
+    CHUNK = 256 << 20  # bytes of decoded frames per upload
+
+    def __init__(self, root_or_split_file, mode="train", device="cuda", max_bytes=None, workers=8):
+        import os
+        import numpy as np
+        from concurrent.futures import ThreadPoolExecutor
+        from PIL import Image
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise Y3DError(f"DeviceSplit: the split is held on a HIP device, not {dev} (no host fallback)")
+        if mode == "test":
+            raise Y3DError("DeviceSplit: the test split has no labels")
+        if int(workers) < 1:
+            raise Y3DError(f"DeviceSplit: workers = {workers}")
+        if dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        self.device, self.mode = dev, mode
+        self.data, self.ids = _split(root_or_split_file, mode)
+        N = len(self.ids)
+        if N < 1:
+            raise Y3DError("DeviceSplit: the split lists no frame")
+        path = lambda sub, i, ext: os.path.join(self.data, sub, f"{i:06d}.{ext}")
+        # sizes from the PNG headers, the budget before anything is decoded or allocated
+        self.wh = []
+        for i in self.ids:
+            with Image.open(path("image_2", i, "png")) as im:
+                self.wh.append((int(im.size[0]), int(im.size[1])))
+        size = np.array([w * h * 3 for w, h in self.wh], np.int64)
+        padded = (size + _ALIGN - 1) // _ALIGN * _ALIGN
+        self.offsets = np.concatenate(([0], np.cumsum(padded)[:-1])).astype(np.int64)
+        self.nbytes = int(padded.sum())
+        allowed = int(max_bytes) if max_bytes is not None else torch.cuda.mem_get_info(dev)[0] // 2
+        if self.nbytes > allowed:
+            raise Y3DError(f"DeviceSplit: the {N} decoded frames need {self.nbytes} bytes, {allowed} bytes are allowed (max_bytes)")
+        pool = ThreadPoolExecutor(max_workers=min(int(workers), 16))
+        try:
+            # labels and calibrations, both projections of every frame
+            def tables(pos):
+                P = read_calib(path("calib", self.ids[pos], "txt"))
+                return label_records(read_label(path("label_2", self.ids[pos], "txt"))), P, flip_calib(P, self.wh[pos])
+
+            recs, self.P2_host, flipped = zip(*pool.map(tables, range(N)))
+            self.n_lines = [len(r) for r in recs]
+            self.cam = [(float(P[0, 2]), float(P[1, 2]), float(P[0, 0]), float(P[1, 1])) for P in self.P2_host]
+            span = np.zeros((N, 2), np.int32)
+            span[:, 1] = self.n_lines
+            span[1:, 0] = np.cumsum(self.n_lines)[:-1]
+            rec = np.concatenate(recs) if sum(self.n_lines) else np.zeros((1, _REC_W))
+            up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a)).to(device=dev, dtype=dt)
+            self.rec, self.rec_span = up(rec, torch.float64), up(span, torch.int32)
+            self.img_off = up(self.offsets, torch.int64)
+            self.frame_hw = up(np.array([(h, w) for w, h in self.wh], np.int32), torch.int32)
+            self.P2 = up(np.stack([np.stack((P.reshape(12), F.reshape(12))) for P, F in zip(self.P2_host, flipped)]).astype(np.float32), torch.float32)
+            self.mean_size = up(np.asarray(CLS_MEAN_SIZE, np.float64).reshape(-1, 3), torch.float64)
+            # the arena: runs of consecutive frames decoded into a pinned stage, one copy per run
+            self.arena = torch.empty(self.nbytes, dtype=torch.uint8, device=dev)
+            runs, first = [], 0
+            for pos in range(1, N + 1):
+                if pos == N or self.offsets[pos] + padded[pos] - self.offsets[first] > self.CHUNK:
+                    runs.append((first, pos))
+                    first = pos
+            stage = torch.zeros(max(int(self.offsets[b - 1] + padded[b - 1] - self.offsets[a]) for a, b in runs), dtype=torch.uint8).pin_memory()
+            stage_np = stage.numpy()
+
+            def decode(pos, base):
+                with Image.open(path("image_2", self.ids[pos], "png")) as im:
+                    px = np.array(im.convert("RGB"))
+                w, h = self.wh[pos]
+                if px.shape != (h, w, 3):
+                    raise Y3DError(f"DeviceSplit: frame {self.ids[pos]:06d} decodes to {px.shape}, its header said {(h, w, 3)}")
+                o = int(self.offsets[pos]) - base
+                stage_np[o:o + px.size] = px.reshape(-1)
+
+            for a, b in runs:
+                base, end = int(self.offsets[a]), int(self.offsets[b - 1] + padded[b - 1])
+                list(pool.map(lambda pos: decode(pos, base), range(a, b)))
+                self.arena[base:end].copy_(stage[:end - base])  # from pinned memory; returns when the stage may be refilled
+        finally:
+            pool.shutdown()
+        self._ring = None
+
+    def __len__(self):
+        return len(self.ids)
+
+    def check_device(self, device):
+        d = torch.device(device)
+        if d.type != "cuda" or (d.index is not None and d.index != self.device.index):
+            raise Y3DError(f"build_batch: the split lives on {self.device}, a batch on {d} was asked for")
+
+    def frame_info(self, pos):
+        """sample_augment's frame_info: ((cu, cv, fu, fv), label lines, (W, H)), the true size for every position"""
+        return self.cam[pos], self.n_lines[pos], self.wh[pos]
+
+    def frame(self, pos):
+        """the decoded frame at a dataset position: an (H, W, 3) uint8 view of the arena"""
+        w, h = self.wh[pos]
+        o = int(self.offsets[pos])
+        return self.arena[o:o + h * w * 3].view(h, w, 3)
+
+    def _upload(self, rows):
+        """the draw table through the next pinned buffer of the ring, non-blocking -> (host view, device tensor).  A buffer is rewritten
+        only after the copy that last read it has run (one event per buffer)."""
+        B = len(rows)
+        if self._ring is None or self._ring["host"][0].shape[0] < B:
+            cap = max(64, B)
+            self._ring = {"host": [torch.empty(cap, _DRAW_W, dtype=torch.float64).pin_memory() for _ in range(self.RING)],
+                          "event": [torch.cuda.Event() for _ in range(self.RING)], "next": 0}
+        r = self._ring
+        k = r["next"]
+        r["next"] = (k + 1) % self.RING
+        r["event"][k].synchronize()  # (returns at once for an event never recorded)
+        host = r["host"][k][:B]
+        host.numpy()[:] = rows
+        dev = torch.empty(B, _DRAW_W, dtype=torch.float64, device=self.device)
+        dev.copy_(host, non_blocking=True)
+        r["event"][k].record()
+        return host, dev
+
+    def build_batch(self, indices, args, mode="train", compact=False, img_mode="uint8", resolution=RESOLUTION):
+        """`build_batch(path, indices, args, device, ...)` from the resident split: the same dictionary, bit for bit.  With compact=False
+        nothing here waits for the device (but a ring buffer still in flight) and no file is opened."""
+        import numpy as np
+        if getattr(args, "load_depth_maps", False):
+            raise Y3DError("build_batch: depth maps (load_depth_maps) are not supported")
+        if mode == "test":
+            raise Y3DError("build_batch: the test split has no labels")
+        indices = [int(i) for i in indices]
+        N, B = len(self), len(indices)
+        if B < 1 or any(not 0 <= p < N for p in indices):
+            raise Y3DError(f"build_batch: {B} positions, all must lie in [0, {N})")
+        draws = sample_augment(N, indices, self.frame_info, args, mode, MAX_OBJS, resolution)
+        rows = []
+        for pos, d in zip(indices, draws):
+            if d["mixed"] and self.wh[d["partner"]] != self.wh[pos]:
+                raise Y3DError(f"build_batch: mixup partner {d['partner']} of position {pos} has another size")
+            rows.append(np.concatenate(([pos, d["partner"], d["flip"], d["scale"]], d["trans"].reshape(6), d["trans_inv"].reshape(6))))
+        with torch.cuda.device(self.device):
+            host, dev = self._upload(rows)
+            plan = plan_batch(self, host, dev)
+            W, H = int(resolution[0]), int(resolution[1])
+            if img_mode == "float":
+                img = torch.empty(B, 3, H, W, dtype=torch.float32, device=self.device)
+            else:
+                img = torch.empty(B, H, W, 3, dtype=torch.uint8, device=self.device)
+            lib().kitti_image_aug(plan["src"].data_ptr(), plan["src2"].data_ptr(), plan["hw"].data_ptr(), plan["flip"].data_ptr(),
+                                  plan["trans_inv"].data_ptr(), B, H, W, 0 if img_mode == "float" else 1, img.data_ptr(), ops.stream())
+            packed = {"rec": self.rec, "img_i": plan["img_i"], "img_f": plan["img_f"], "mean_size": self.mean_size}
+            lab = encode_labels(packed, resolution, args.min_depth_threshold, args.max_depth_threshold, bool(args.cam_dis), MAX_OBJS)
+        batch = {"img": img, "calib": lab["calib"],
+                 "info": [{"img_id": self.ids[p], "img_size": np.array(self.wh[p]), "trans_inv": d["trans_inv"]} for p, d in zip(indices, draws)],
+                 "im_file": [f"{self.ids[p]:06d}.txt" for p in indices], "ori_shape": [np.array(self.wh[p])[::-1] for p in indices],
+                 "ratio_pad": lab["ratio_pad"], "mean_sizes": self.mean_size, "mixed": plan["mixed"], "counts": lab["counts"]}
+        if compact:
+            batch.update(compact_labels(lab, lab["counts"].tolist(), [d["crop"] for d in draws], bool(args.cam_dis)))
+            del batch["counts"]
+        else:
+            batch.update({k: lab[k] for k in PER_BOX})
+        return batch
+
+    def epoch(self, batch, args, mode="train", shuffle=True, seed=0, drop_last=False, **kw):
+        """One epoch of batches: `build_batch` over `epoch_indices(len(self), batch, shuffle, seed, drop_last)`.  A build only enqueues
+        work on the current stream, so building the next batch already overlaps the step that consumes this one."""
+        for idx in epoch_indices(len(self), batch, shuffle, seed, drop_last):
+            yield self.build_batch(idx, args, mode=mode, **kw)
 
 
 def save_results(results, output_dir="./outputs", class_name=("Car", "Pedestrian", "Cyclist")):

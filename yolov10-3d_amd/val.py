@@ -90,7 +90,8 @@ class _Validator:
 
 
 class Validator3d(_Validator):
-    """`YOLOv10_3DDetectionValidator` for a KITTI root or split file (dataset="kitti") or a Waymo / Omni3D split JSON.
+    """`YOLOv10_3DDetectionValidator` for a KITTI root or split file (dataset="kitti") or a Waymo / Omni3D split JSON.  A KITTI split
+    may also be passed as a `kitti.DeviceSplit`: its frames are validated in its own order, batches are built without file access.
 
     Per batch of `batch` consecutive dataset positions: the val batch, the eval forward, `v10_3Dpostprocess`,
     `kitti.decode_preds_device` with the dataset's mean sizes and threshold = conf, `BoxStats.update_3d`, and
@@ -107,6 +108,8 @@ class Validator3d(_Validator):
             raise Y3DError(f"Validator3d: dataset {dataset!r} (kitti, waymo or omni3d)")
         if int(batch) < 1:
             raise Y3DError(f"Validator3d: batch = {batch}")
+        if isinstance(root_or_split, kitti.DeviceSplit) and dataset != "kitti":
+            raise Y3DError(f"Validator3d: a kitti.DeviceSplit holds a KITTI split, not dataset {dataset!r}")
         self.source, self.dataset, self.batch = root_or_split, dataset, int(batch)
         self.args = args if args is not None else kitti.data_args()
         self.resolution = (int(resolution[0]), int(resolution[1])) if dataset == "kitti" else json3d.RESOLUTION
@@ -119,6 +122,9 @@ class Validator3d(_Validator):
 
     def _dataset(self):
         """-> (number of images, position -> the original image's (cu, cv, fu, fv, tx, ty), as the reference's get_calib holds them)"""
+        if isinstance(self.source, kitti.DeviceSplit):  # resident on the device: ids, calibrations and the label directory from it
+            sp = self.source
+            return len(sp), lambda pos: kitti.calib_params(sp.P2_host[pos]), sp.data
         if self.dataset == "kitti":
             data, ids = kitti._split(self.source, "val")
             return len(ids), lambda pos: kitti.calib_params(kitti.read_calib(os.path.join(data, "calib", f"{ids[pos]:06d}.txt"))), data
