@@ -47,7 +47,9 @@ int y3d_pack_weight_fwd(int dtype, const float* w_oihw, void* out, int Cout, int
 int y3d_pack_weight_dgrad(int dtype, const float* w_oihw, void* out, int Cout, int Cin_g, int groups, int kh, int kw, void* stream);
 /* the two packings above for MANY weights in one launch (once per step, after the optimizer): desc is a DEVICE array of 8 int64 per
  * weight {src fp32 OIHW, dst, a, b, c, taps, Kpad, mode}; mode 0 = forward layout (a = Cout, b = Cin/g, c = padded Cin/g),
- * mode 1 = data-gradient layout (a = groups, b = Cout/g, c = Cin/g); chunk tables as in the optimizer kernels below */
+ * mode 1 = data-gradient layout (a = groups, b = Cout/g, c = Cin/g), mode 2 = the depth-wise layout of y3d_dw_pack_weight, always
+ * fp32 (a = 1, b = C, c = 1, Kpad = taps * C); chunk tables as in the optimizer kernels below: a chunk is `chunk` consecutive
+ * elements of a destination, and the workgroup it goes to packs the rows (of Kpad elements) that start in it */
 int y3d_mt_pack_weights(int dtype, const int64_t* desc, const int* chunk_tensor, const int* chunk_off, int nchunks, int chunk, void* stream);
 /* fp8 conv weights (fp8w.hip; BASELINE configs[4], no reference counterpart): OCP e4m3fn codes with one power-of-two scale per
  * output channel, scale = 2^ceil(log2(absmax / 448)).  MANY weights in one launch: desc is a DEVICE array of 6 int64 per weight
@@ -156,6 +158,10 @@ int y3d_set_bn_wide_slabs(int enable);
 int y3d_conv2d_bwd_weight(int dtype, const void* x, int64_t xsb, int64_t xsh, int64_t xsw, int B, int H, int W, int Cin,
                           int Cin_real, const void* dy, int64_t dsw, int Ho, int Wo, int Cout, int groups, int kh, int kw,
                           int stride, int pad, float* slab, int nsplit, float* grad_oihw, int accumulate, void* stream);
+/* the last pass of y3d_conv2d_bwd_weight on its own: grad_oihw[co][ci][tap] (+)= sum over the nsplit slabs [co][tap][ci] (Cin_g
+ * channels per tap, of which the first Cin_g_real are written), in the fixed order documented at wgrad_reduce_kernel */
+int y3d_wgrad_fold(const float* slab, int nsplit, int Cout, int taps, int Cin_g, int Cin_g_real, float* grad_oihw, int accumulate,
+                   void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Depth-wise convolution (dwconv.hip) — Conv(g=c): conv.py:172-177, block.py:705-706,747-751,783,824
@@ -179,6 +185,8 @@ int y3d_dwconv2d_bwd_data(int dtype, const void* dy, int64_t dsb, int64_t dsh, i
 int y3d_dwconv2d_bwd_weight(int dtype, const void* x, int64_t xsb, int64_t xsh, int64_t xsw, int B, int H, int W, int C,
                             const void* dy, int64_t dsw, int Ho, int Wo, int kh, int kw, int stride, int pad, float* slab,
                             float* grad_oihw, int accumulate, void* stream);
+/* its last pass on its own: grad_oihw[c][tap] (+)= sum over the nblk slabs [tap][c] */
+int y3d_dw_wgrad_fold(const float* slab, int nblk, int C, int taps, float* grad_oihw, int accumulate, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * BatchNorm (batch or running statistics) + SiLU + residual (bn_act.hip)

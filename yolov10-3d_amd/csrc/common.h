@@ -95,6 +95,25 @@ __device__ __forceinline__ float wave_xor_sum16(float v) {
   return v;
 }
 
+// `cnt` floats of an LDS image -> out[0, cnt) (accumulate: out + image), by the 256 threads of a workgroup, in whole 16-byte
+// pieces of the DESTINATION wherever it starts (an OIHW row of 27 floats starts anywhere); the ragged ends go float by float
+__device__ __forceinline__ void store_image_f32(const float* img, float* out, int cnt, int accumulate) {
+  const int mis = (int)(((uintptr_t)out >> 2) & 3);
+  for (int k = threadIdx.x; 4 * k < cnt + mis; k += 256) {
+    const int lo = 4 * k - mis;
+    if (lo >= 0 && lo + 4 <= cnt) {
+      float4 v = make_float4(img[lo], img[lo + 1], img[lo + 2], img[lo + 3]);
+      float4* o = (float4*)(out + lo);
+      if (accumulate) { const float4 a = *o; v.x = a.x + v.x; v.y = a.y + v.y; v.z = a.z + v.z; v.w = a.w + v.w; }
+      *o = v;
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (lo + j >= 0 && lo + j < cnt) out[lo + j] = accumulate ? out[lo + j] + img[lo + j] : img[lo + j];
+    }
+  }
+}
+
 // host-side error plumbing (y3d_api.cpp)
 void y3d_set_error(const char* fmt, ...);
 #define Y3D_CHECK(cond, ...)          \

@@ -514,10 +514,29 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(WgradP p) {
     }
 }
 
-// slab[split][co][tap][ci]  ->  grad OIHW [co][ci][tap]  (accumulate optional).  SL split-lanes per element group: a narrow layer has
-// few elements and many splits, so the split loop is shared by SL threads and folded through LDS.  A thread owns FOUR consecutive
-// elements (one float4 per slab: 512-byte runs per slab row and wave instead of 128 - the fold reads nsplit x n floats and was at
-// 2.7 TB/s with scalar loads); n is a multiple of 4 because Cg is a multiple of the 16-byte chunk.
+// ---- the weight-gradient fold:  slab[split][co][tap][ci]  ->  grad OIHW [co][ci][tap]  (accumulate optional) ----
+//
+// THE SUMMATION ORDER of the dense split-K folds (the depth-wise fold's stands at dw_wgrad_reduce_kernel in dwconv.hip;
+// tests/wgrad_fold_ref.py emulates both on the host).  An output element is summed by SL split lanes (SL is a function of the slab shape alone, see
+// launch_wgrad_reduce).  Lane sl takes the slabs k = sl, sl + SL, sl + 2 SL, ... in ascending order and deals them round-robin
+// onto four running sums s0..s3 while four whole rounds remain (k + 3 SL < nsplit): s0 += slab[k], s1 += slab[k + SL],
+// s2 += slab[k + 2 SL], s3 += slab[k + 3 SL]; the slabs left over all go to s0.  The lane's sum is (s0 + s1) + (s2 + s3).  The
+// lanes are then added in ascending lane order: ((lane0 + lane1) + lane2) + ...  With `accumulate` the result is grad + sum.
+// Which workgroup or thread sums an element does not enter the order, so the mapping is free to follow the memory layout.
+// Two mappings share that order:
+//  * many slabs of a small layer (SL = 16 / 8: nsplit >= 32, at most 1 M elements) - wgrad_reduce_kernel.  The slab stream is
+//    32..256 x the gradient, so the mapping follows the READS: a workgroup takes 256 / SL consecutive float4 groups of the slab
+//    row order (256..512-byte runs per slab and wave, one pass, up to 1152 workgroups) and every lane-0 thread ends in four
+//    4-byte stores `taps` floats apart.  Row-owning workgroups measured slower here (S-3D, per launch: SL = 16 6.3 -> 19.0 us,
+//    SL = 8 8.5 -> 12.5 us): a small layer has too few rows, and splitting a row by channel runs breaks the slab reads into
+//    16..112-byte pieces.
+//  * few slabs, or a large layer (SL = 2 / 1: the head layers' 2.4 M..9.4 M-element slabs) - wgrad_reduce_rows_kernel.  There the
+//    transposing 4-byte stores set the time, so the mapping follows the WRITES: a workgroup owns R whole output-channel rows, or -
+//    when a row is longer than the image - one run of CC >= 64 input channels of one row.  Either way its outputs are ONE
+//    contiguous run of OIHW floats.  A thread owns a float4 of four consecutive input channels per pass (one 16-byte load per
+//    slab), the lane-0 threads transpose [tap][ci] -> [ci][tap] into the LDS image (ds_write_b32 `taps` floats apart: taps is odd
+//    for every square kernel, so the 32 lanes of a write group fall on 8 or more banks), and the image leaves as 16-byte stores
+//    (S-3D, per launch: SL = 1 49.0 -> 23.3 us, SL = 2 10.7 -> 9.2 us).
 template <int SL>
 __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restrict__ slab, float* __restrict__ grad, int nsplit, int Ctot,
                                                            int taps, int Cg, int Cg_real, int accumulate) {
@@ -528,7 +547,6 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restri
   const long n = (long)Ctot * taps * Cg;
   float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
   if (idx < n) {
-    // four slabs in flight per lane (the partial sums keep a fixed order: bitwise reproducible)
     float4 s0 = s, s1 = s, s2 = s, s3 = s;
     auto add = [](float4& a, const float4 b) { a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w; };
     int k = sl;
@@ -561,54 +579,122 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restri
   }
 }
 
-// one element per thread: the form for few, large slabs (head layers: nsplit < 8, 2.4 M elements) - there the transposing
-// 4-byte writes dominate and four of them per thread were slower (49 -> 60 us)
+constexpr int FOLD_CAP = 6144;  // floats of OIHW image per workgroup (24 KB: a 512-channel 3x3 row is 4608)
+
 template <int SL>
-__global__ __launch_bounds__(256) void wgrad_reduce_scalar_kernel(const float* __restrict__ slab, float* __restrict__ grad, int nsplit, int Ctot,
-                                                           int taps, int Cg, int Cg_real, int accumulate) {
-  constexpr int EPB = 256 / SL;  // elements per block
-  __shared__ float sh[SL][EPB];
-  const int e = threadIdx.x % EPB, sl = threadIdx.x / EPB;
-  long idx = (long)blockIdx.x * EPB + e;
-  long n = (long)Ctot * taps * Cg;
-  float s = 0.f;
-  if (idx < n) {
-    // four slabs in flight per lane (the partial sums keep a fixed order: bitwise reproducible)
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-    int k = sl;
-    for (; k + 3 * SL < nsplit; k += 4 * SL) {
-      s0 += slab[(long)k * n + idx];
-      s1 += slab[(long)(k + SL) * n + idx];
-      s2 += slab[(long)(k + 2 * SL) * n + idx];
-      s3 += slab[(long)(k + 3 * SL) * n + idx];
+__global__ __launch_bounds__(256) void wgrad_reduce_rows_kernel(const float* __restrict__ slab, float* __restrict__ grad, int nsplit, int Ctot,
+                                                                int taps, int Cg, int Cg_real, int accumulate, int R, int CC) {
+  constexpr int GPB = 256 / SL;  // float4 groups per pass
+  __shared__ float4 sh[SL > 1 ? 2 * 256 : 1];  // [pass parity][SL][GPB]: one barrier per pass
+  __shared__ __attribute__((aligned(16))) float img[FOLD_CAP];
+  const int e = threadIdx.x % GPB, sl = threadIdx.x / GPB;
+  const int nch = (Cg + CC - 1) / CC;  // channel runs per row (1: whole rows)
+  int co0, c0, rows;
+  if (nch == 1) {
+    co0 = blockIdx.x * R; c0 = 0; rows = Ctot - co0 < R ? Ctot - co0 : R;
+  } else {
+    co0 = blockIdx.x / nch; c0 = (blockIdx.x - co0 * nch) * CC; rows = 1;
+  }
+  const int cc = Cg - c0 < CC ? Cg - c0 : CC;
+  const int q = cc >> 2, per = taps * q, ng = rows * per;  // float4 groups: per tap, per row, of this workgroup
+  const long n = (long)Ctot * taps * Cg;
+  int par = 0;
+  for (int g0 = 0; g0 < ng; g0 += GPB, par ^= 1) {
+    const int g = g0 + e;
+    int r = 0, tap = 0, c4 = 0;
+    float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (g < ng) {
+      r = g / per;
+      const int rem = g - r * per;
+      tap = rem / q;
+      c4 = rem - tap * q;
+      const float* src = slab + ((long)(co0 + r) * taps + tap) * Cg + c0 + 4 * c4;
+      float4 s0 = s, s1 = s, s2 = s, s3 = s;
+      auto add = [](float4& a, const float4 b) { a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w; };
+      int k = sl;
+      for (; k + 3 * SL < nsplit; k += 4 * SL) {
+        const float4 v0 = *(const float4*)(src + (long)k * n), v1 = *(const float4*)(src + (long)(k + SL) * n);
+        const float4 v2 = *(const float4*)(src + (long)(k + 2 * SL) * n), v3 = *(const float4*)(src + (long)(k + 3 * SL) * n);
+        add(s0, v0); add(s1, v1); add(s2, v2); add(s3, v3);
+      }
+      for (; k < nsplit; k += SL) add(s0, *(const float4*)(src + (long)k * n));
+      s.x = (s0.x + s1.x) + (s2.x + s3.x); s.y = (s0.y + s1.y) + (s2.y + s3.y);
+      s.z = (s0.z + s1.z) + (s2.z + s3.z); s.w = (s0.w + s1.w) + (s2.w + s3.w);
     }
-    for (; k < nsplit; k += SL) s0 += slab[(long)k * n + idx];
-    s = (s0 + s1) + (s2 + s3);
-  }
-  if (SL > 1) {
-    sh[sl][e] = s;
-    __syncthreads();
-    if (sl != 0) return;
+    if (SL > 1) {
+      // (the other parity's buffer is what lane 0 may still be reading from the pass before: it is next written after this barrier)
+      sh[(par * SL + sl) * GPB + e] = s;
+      __syncthreads();
+      if (sl == 0) {
 #pragma unroll
-    for (int j = 1; j < SL; ++j) s += sh[j][e];
+        for (int j = 1; j < SL; ++j) { const float4 v = sh[(par * SL + j) * GPB + e]; s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w; }
+      }
+    }
+    if (sl == 0 && g < ng) {
+      const float v[4] = {s.x, s.y, s.z, s.w};
+      float* d = img + ((long)r * Cg_real + 4 * c4) * taps + tap;
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (c0 + 4 * c4 + j < Cg_real) d[j * taps] = v[j];  // (channel padding is not part of the image)
+    }
   }
-  if (idx >= n) return;
-  int ci = idx % Cg;
-  int tap = (idx / Cg) % taps;
-  int co = idx / ((long)Cg * taps);
-  if (ci >= Cg_real) return;  // channel padding
-  long o = ((long)co * Cg_real + ci) * taps + tap;
-  grad[o] = accumulate ? grad[o] + s : s;
+  __syncthreads();
+  // the image is the run of OIHW floats that starts at (co0, c0)
+  int creal = Cg_real - c0 < cc ? Cg_real - c0 : cc;
+  if (creal < 0) creal = 0;
+  store_image_f32(img, grad + ((long)co0 * Cg_real + c0) * taps, rows * creal * taps, accumulate);
 }
 
-inline void launch_wgrad_reduce(const float* slab, float* grad, int nsplit, int Ctot, int taps, int Cg, int Cg_real, int accumulate, hipStream_t st) {
-  long n = (long)Ctot * taps * Cg;
-  long ng = (n + 3) / 4;  // float4 groups
-  // split lanes per element group: enough loads in flight for the slab stream (nsplit x n floats) whatever the layer's shape
-  if (n <= 65536 && nsplit >= 64) hipLaunchKernelGGL(wgrad_reduce_kernel<16>, dim3(cdiv(ng, 16)), dim3(256), 0, st, slab, grad, nsplit, Ctot, taps, Cg, Cg_real, accumulate);
-  else if (n <= 1048576 && nsplit >= 32) hipLaunchKernelGGL(wgrad_reduce_kernel<8>, dim3(cdiv(ng, 32)), dim3(256), 0, st, slab, grad, nsplit, Ctot, taps, Cg, Cg_real, accumulate);
-  else if (nsplit >= 8) hipLaunchKernelGGL(wgrad_reduce_kernel<2>, dim3(cdiv(ng, 128)), dim3(256), 0, st, slab, grad, nsplit, Ctot, taps, Cg, Cg_real, accumulate);
-  else hipLaunchKernelGGL(wgrad_reduce_scalar_kernel<1>, dim3(cdiv(n, 256)), dim3(256), 0, st, slab, grad, nsplit, Ctot, taps, Cg, Cg_real, accumulate);
+// (R, CC, workgroups) of a row-owning fold: a workgroup folds G float4 groups in cdiv(G, GPB) passes and about 1024 workgroups are
+// resident at once (4 per CU), so the time goes with (rounds of workgroups) x (passes of one).  The fewest wins; ties go to the
+// longer output run.  A row is only split into runs of 64 or more channels: 256-byte pieces of the slab rows.
+// (A model has a few dozen conv shapes and folds each of them every step: the last searches are remembered per host thread.)
+struct FoldShape { int Ctot, taps, Cg, GPB, R, CC, grid; };
+
+inline FoldShape wgrad_fold_shape(int Ctot, int taps, int Cg, int GPB) {
+  constexpr int NMEMO = 64;
+  thread_local FoldShape memo[NMEMO];
+  thread_local int nmemo = 0;
+  for (int i = 0; i < (nmemo < NMEMO ? nmemo : NMEMO); ++i)
+    if (memo[i].Ctot == Ctot && memo[i].taps == taps && memo[i].Cg == Cg && memo[i].GPB == GPB) return memo[i];
+  FoldShape f = {Ctot, taps, Cg, GPB, 0, 0, 0};
+  const int q = Cg / 4;
+  long best = -1;
+  int bestG = 0;
+  auto consider = [&](int r, int cc, long blocks, int G) {
+    const long cost = (long)cdiv(blocks, 1024) * cdiv(G, GPB);
+    if (best < 0 || cost < best || (cost == best && G > bestG)) { best = cost; bestG = G; f.R = r; f.CC = cc; f.grid = (int)blocks; }
+  };
+  for (int qq = 16; qq < q && 4L * qq * taps <= FOLD_CAP; ++qq) consider(1, 4 * qq, (long)Ctot * cdiv(q, qq), taps * qq);
+  for (int r = 1; r <= Ctot && (long)r * Cg * taps <= FOLD_CAP; ++r) consider(r, Cg, cdiv(Ctot, r), r * taps * q);
+  memo[nmemo++ % NMEMO] = f;
+  return f;
+}
+
+inline int launch_wgrad_reduce(const float* slab, float* grad, int nsplit, int Ctot, int taps, int Cg, int Cg_real, int accumulate, hipStream_t st) {
+  Y3D_CHECK(Cg % 4 == 0 && ((uintptr_t)slab & 15) == 0, "wgrad fold: the slabs are read as 16-byte chunks of four input channels");
+  const long n = (long)Ctot * taps * Cg;
+  const long ng = n / 4;  // float4 groups
+  // split lanes per element group: enough loads in flight for the slab stream (nsplit x n floats) whatever the layer's shape.
+  // SL is part of the summation order: these thresholds do not move.
+  if (n <= 65536 && nsplit >= 64) {
+    hipLaunchKernelGGL(wgrad_reduce_kernel<16>, dim3(cdiv(ng, 16)), dim3(256), 0, st, slab, grad, nsplit, Ctot, taps, Cg, Cg_real, accumulate);
+  } else if (n <= 1048576 && nsplit >= 32) {
+    hipLaunchKernelGGL(wgrad_reduce_kernel<8>, dim3(cdiv(ng, 32)), dim3(256), 0, st, slab, grad, nsplit, Ctot, taps, Cg, Cg_real, accumulate);
+  } else {
+    const int SL = nsplit >= 8 ? 2 : 1;  // 1: few, large slabs (head layers)
+    const FoldShape f = wgrad_fold_shape(Ctot, taps, Cg, 256 / SL);
+    if (f.grid == 0) {  // no row split fits the image (kernels of more than 96 taps): the flat mapping, same order
+      if (SL == 2) hipLaunchKernelGGL(wgrad_reduce_kernel<2>, dim3(cdiv(ng, 128)), dim3(256), 0, st, slab, grad, nsplit, Ctot, taps, Cg, Cg_real, accumulate);
+      else hipLaunchKernelGGL(wgrad_reduce_kernel<1>, dim3(cdiv(ng, 256)), dim3(256), 0, st, slab, grad, nsplit, Ctot, taps, Cg, Cg_real, accumulate);
+    } else if (SL == 2) {
+      hipLaunchKernelGGL(wgrad_reduce_rows_kernel<2>, dim3(f.grid), dim3(256), 0, st, slab, grad, nsplit, Ctot, taps, Cg, Cg_real, accumulate, f.R, f.CC);
+    } else {
+      hipLaunchKernelGGL(wgrad_reduce_rows_kernel<1>, dim3(f.grid), dim3(256), 0, st, slab, grad, nsplit, Ctot, taps, Cg, Cg_real, accumulate, f.R, f.CC);
+    }
+  }
+  Y3D_LAUNCH_CHECK();
+  return Y3D_OK;
 }
 
 // OIHW fp32 -> packed [Cout][taps][Cg_pad] (forward) in T, row pitch Kpad
@@ -644,73 +730,202 @@ __global__ void pack_w_dgrad_kernel(const float* __restrict__ w, T* __restrict__
   TT<T>::st(out + idx, v);
 }
 
-// Multi-tensor weight packing: every conv weight of the model, forward layout (mode 0: [Cout][taps][Cg_pad], as pack_w_fwd_kernel) or
-// data-gradient layout (mode 1: [G][Cg][taps][Cn], as pack_w_dgrad_kernel), in ONE launch per step instead of two tiny launches per
-// conv.  desc[t] = {src fp32 OIHW, dst, a, b, c, taps, Kpad, mode}: mode 0: a = Cout, b = Cg, c = Cg_pad; mode 1: a = G, b = Cn, c = Cg.
-// A workgroup owns `chunk` consecutive OUTPUT elements of one tensor.  Both layouts are transposes of the OIHW source (tap <-> channel,
-// output <-> input channel): gathering element by element read 4 bytes out of every 36..4608 (170 + 250 us per step on S-3D for
-// 110 MB of traffic).  The data-gradient layout is staged through LDS: the source is read in runs that are contiguous in OIHW (the
-// R * taps weights that R consecutive input channels own in one filter), the packed rows are written contiguously (250 -> 117 us).
+// Multi-tensor weight packing: every conv weight of the model in ONE launch per step and layout instead of two tiny launches per conv.
+// desc[t] = {src fp32 OIHW, dst, a, b, c, taps, Kpad, mode}:
+//   mode 0  forward layout       [Cout][taps][Cg_pad] in T, as pack_w_fwd_kernel:    a = Cout, b = Cg, c = Cg_pad
+//   mode 1  data-gradient layout [G][Cg][taps][Cn] in T, as pack_w_dgrad_kernel:     a = G, b = Cn, c = Cg
+//   mode 2  depth-wise layout    [taps][C] in fp32, as dw_pack_kernel (dwconv.hip):  a = 1, b = C, c = 1, Kpad = taps * C
+// (mode 2 is mode 1 with one group of one input channel and an fp32 destination.)  Every layout is a transpose of the OIHW source
+// (tap <-> channel, output <-> input channel); gathering element by element read 4 bytes out of every 36..4608.  So a workgroup takes
+// whole blocks whose source AND destination are contiguous, stages them in LDS and moves 16 bytes per lane on both sides:
+//   mode 0: output rows (one co each).  Source: the rows' b * taps floats each, back to back.  The LDS image IS the packed rows
+//           (as floats, padding zeroed): the transposing 4-byte LDS writes of a lane's four source floats go `c` floats apart per tap
+//           (ds_write_b32, banks mod 32: a write group's 32 lanes cover ~14 channels x the taps: 2-3 lanes per bank, and 2-way is free),
+//           the image leaves with ds_read_b128 + one 16-byte store per lane.  1x1 weights are copied through with ds_write_b128.
+//   mode 1: R rows (input channels of one group) x CB <= 128 output channels.  Source: per output channel a run of R * taps floats
+//           (R a multiple of 4: 16-byte loads).  Image [(ci, tap)][co], pitch CB | 1: a lane's four floats go 4-byte writes one pitch
+//           apart, lanes 4 pitches apart (ds_write_b32: 8 banks per group, 4-way); a lane reads 8 (bf16) or 4 (fp32) consecutive
+//           floats with ds_read_b32 (lane stride 8 floats: 8-way) and stores 16 bytes.  LDS cycles per 1 KB of bf16 output, both
+//           phases: ~190 of the ~380 the CU's share of HBM needs for the 3 KB moved; five workgroups per CU overlap the phases.
+// A workgroup is given `chunk` consecutive OUTPUT elements of one tensor (the chunk tables of the optimizer kernels) and packs the
+// rows that START in them.  Shapes the image cannot hold (a forward row of more than PACK_CAP elements) are gathered element by element.
+constexpr int PACK_CAP = 8192;  // floats of LDS image per workgroup (32 KB)
+
+// LDS image -> `count` consecutive output elements; 16-byte pieces when `vec` (out 16-byte aligned, count a multiple of the piece)
+template <typename OT>
+__device__ __forceinline__ void pack_store_linear(const float* img, OT* __restrict__ out, int count, bool vec, int tid) {
+  constexpr int E = TT<OT>::CE;
+  if (vec) {
+    for (int p = tid * E; p < count; p += 256 * E) {
+      float f[E];
+#pragma unroll
+      for (int j = 0; j < E; j += 4) {
+        const float4 v = *(const float4*)(img + p + j);
+        f[j] = v.x; f[j + 1] = v.y; f[j + 2] = v.z; f[j + 3] = v.w;
+      }
+      *(uint4*)(out + p) = Chunk<OT>::pack(f);
+    }
+  } else {
+    for (int i = tid; i < count; i += 256) TT<OT>::st(out + i, img[i]);
+  }
+}
+
+// one pass of modes 1 / 2: rows [r0, r0 + nr) (input channels ci0.. of group g) x output channels [co0, co0 + cb)
+template <typename OT>
+__device__ __forceinline__ void pack_cols_pass(const float* __restrict__ w, OT* __restrict__ out, float* img, int b, int c, int taps, int Kpad,
+                                               int g, int ci0, long r0, int nr, int co0, int cb, int P, bool vec, int tid) {
+  constexpr int E = TT<OT>::CE;
+  const int seg = nr * taps;
+  const long cs = (long)c * taps;  // source floats between two output channels
+  const float* __restrict__ base = w + ((long)(g * b + co0) * c + ci0) * taps;
+  if (((uintptr_t)w & 15) == 0 && seg % 4 == 0 && cs % 4 == 0 && ((long)ci0 * taps) % 4 == 0) {
+    const int sq = seg >> 2;
+    for (int i = tid; i < cb * sq; i += 256) {
+      const int col = i / sq, j = 4 * (i - col * sq);
+      const float4 v = *(const float4*)(base + col * cs + j);
+      float* d = img + j * P + col;
+      d[0] = v.x; d[P] = v.y; d[2 * P] = v.z; d[3 * P] = v.w;
+    }
+  } else {
+    for (int i = tid; i < cb * seg; i += 256) {
+      const int col = i / seg, j = i - col * seg;
+      img[j * P + col] = base[col * cs + j];
+    }
+  }
+  __syncthreads();
+  if (vec) {
+    const int pc = cb / E;
+    for (int p = tid; p < seg * pc; p += 256) {
+      const int j = p / pc, col = (p - j * pc) * E;
+      const int cil = j / taps, tap = j - cil * taps;
+      float f[E];
+#pragma unroll
+      for (int jj = 0; jj < E; ++jj) f[jj] = img[j * P + col + jj];
+      *(uint4*)(out + (r0 + cil) * Kpad + (long)tap * b + co0 + col) = Chunk<OT>::pack(f);
+    }
+  } else {
+    for (int o = tid; o < seg * cb; o += 256) {
+      const int j = o / cb, col = o - j * cb;
+      const int cil = j / taps, tap = j - cil * taps;
+      TT<OT>::st(out + (r0 + cil) * Kpad + (long)tap * b + co0 + col, img[j * P + col]);
+    }
+  }
+}
+
+// modes 1 / 2: the rows [rb, re) of one tensor
+template <typename OT>
+__device__ __forceinline__ void pack_cols(const float* __restrict__ w, OT* __restrict__ out, float* img, int b, int c, int taps, int Kpad, long rb,
+                                          long re, int tid) {
+  constexpr int E = TT<OT>::CE;
+  bool vec = ((uintptr_t)out & 15) == 0 && b % E == 0 && Kpad == taps * b;
+  int CB = b < 128 ? b : 128;
+  if ((long)taps * (CB | 1) > PACK_CAP) CB = PACK_CAP / taps - 1;  // (taps <= PACK_CAP / 2: the caller's test)
+  if (vec && CB >= E) CB -= CB % E;
+  else vec = false;
+  const int P = CB | 1;  // odd pitch
+  int R = PACK_CAP / (taps * P);
+  if (R >= 4) R &= ~3;
+  for (long r0 = rb; r0 < re;) {
+    const int g = (int)(r0 / c), ci0 = (int)(r0 - (long)g * c);
+    int nr = R;
+    if (nr > c - ci0) nr = c - ci0;
+    if (nr > re - r0) nr = (int)(re - r0);
+    const int over = (ci0 + nr) & 3;  // the next pass starts on a multiple of four input channels (16-byte source runs)
+    if (over && nr > over && ci0 + nr < c) nr -= over;
+    for (int co0 = 0; co0 < b; co0 += CB) {
+      __syncthreads();
+      pack_cols_pass<OT>(w, out, img, b, c, taps, Kpad, g, ci0, r0, nr, co0, b - co0 < CB ? b - co0 : CB, P, vec, tid);
+    }
+    if (Kpad != taps * b) {  // row padding (fewer than 8 elements per row)
+      const int np = Kpad - taps * b;
+      for (int o = tid; o < nr * np; o += 256) {
+        const int rl = o / np;
+        TT<OT>::st(out + (r0 + rl) * Kpad + taps * b + (o - rl * np), 0.f);
+      }
+    }
+    r0 += nr;
+  }
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void mt_pack_w_kernel(const long* __restrict__ desc, const int* __restrict__ ctensor, const int* __restrict__ coff,
                                                         int chunk) {
-  constexpr int CAP = 4096;
-  __shared__ float st[CAP + 64];
+  constexpr int E = TT<T>::CE;
+  __shared__ __attribute__((aligned(16))) float img[PACK_CAP];
   const long* d = desc + (long)ctensor[blockIdx.x] * 8;
   const float* __restrict__ w = (const float*)d[0];
-  T* __restrict__ out = (T*)d[1];
   const int a = (int)d[2], b = (int)d[3], c = (int)d[4], taps = (int)d[5], Kpad = (int)d[6], mode = (int)d[7];
   const long n = mode == 0 ? (long)a * Kpad : (long)a * c * Kpad;
   const long beg = (long)coff[blockIdx.x] * chunk;
   const long end = beg + chunk < n ? beg + chunk : n;
   const int tid = threadIdx.x;
-  const long rb = beg / Kpad, re = (end - 1) / Kpad;  // packed rows this chunk touches
-  if (mode == 0) {
-    // row = output channel co, columns (tap, ci): consecutive lanes read OIHW addresses `taps` floats apart, all inside one filter
-    // (b * taps contiguous floats) - the lines are reused from L1/L2.  (Staging whole filters through LDS measured slower: 118 vs 89 us.)
-    for (long idx = beg + tid; idx < end; idx += 256) {
-      const int k = (int)(idx % Kpad), co = (int)(idx / Kpad);
+  const long rb = (beg + Kpad - 1) / Kpad, re = (end + Kpad - 1) / Kpad;  // the packed rows that start in this chunk
+  if (rb >= re) return;
+  if ((mode == 0 && Kpad > PACK_CAP) || taps > PACK_CAP / 2) {
+    // element by element
+    for (long idx = rb * Kpad + tid; idx < re * Kpad; idx += 256) {
+      const int k = (int)(idx % Kpad);
+      const long row = idx / Kpad;
       float v = 0.f;
-      if (k < taps * c) {
-        const int tap = k / c, ci = k - tap * c;
-        if (ci < b) v = w[((long)co * b + ci) * taps + tap];
+      if (mode == 0) {
+        if (k < taps * c) {
+          const int tap = k / c, ci = k - tap * c;
+          if (ci < b) v = w[(row * b + ci) * taps + tap];
+        }
+      } else if (k < taps * b) {
+        const int tap = k / b, co = k - tap * b;
+        const long g = row / c, ci = row - g * c;
+        v = w[((g * b + co) * c + ci) * taps + tap];
       }
-      TT<T>::st(out + idx, v);
+      if (mode == 2) ((float*)d[1])[idx] = v;
+      else TT<T>::st((T*)d[1] + idx, v);
     }
+    return;
+  }
+  if (mode == 2) {
+    pack_cols<float>(w, (float*)d[1], img, b, c, taps, Kpad, rb, re, tid);
+  } else if (mode == 1) {
+    pack_cols<T>(w, (T*)d[1], img, b, c, taps, Kpad, rb, re, tid);
   } else {
-    // row = (g, ci); its columns are (tap, co).  Per pass: R consecutive input channels x CB output channels.
-    const int CB = b < 256 ? b : 256;
-    int R = CAP / (taps * (CB + 1));
-    if (R < 1) R = 1;
-    const int P = CB + 1;  // LDS pitch (odd: the transposing writes spread over the banks)
-    for (long r0 = rb; r0 <= re;) {
-      const int g = (int)(r0 / c), ci0 = (int)(r0 - (long)g * c);
-      int nr = R;
-      if (nr > c - ci0) nr = c - ci0;
-      if (nr > re - r0 + 1) nr = (int)(re - r0 + 1);
-      const int seg = nr * taps;
-      for (int co0 = 0; co0 < b; co0 += CB) {
-        const int cb = b - co0 < CB ? b - co0 : CB;
+    T* __restrict__ out = (T*)d[1];
+    const bool vec = ((uintptr_t)out & 15) == 0 && Kpad % E == 0;
+    const bool pad = c != b || Kpad != taps * c;
+    const int RP = PACK_CAP / Kpad, L = b * taps;  // rows per pass; source floats per row
+    const bool quad = ((uintptr_t)w & 15) == 0 && L % 4 == 0;
+    for (long r0 = rb; r0 < re; r0 += RP) {
+      const int nr = re - r0 < RP ? (int)(re - r0) : RP;
+      const int tot = nr * L;
+      const float* __restrict__ src = w + r0 * L;
+      __syncthreads();
+      if (pad) {
+        for (int i = tid; i < nr * Kpad; i += 256) img[i] = 0.f;
         __syncthreads();
-        for (int i = tid; i < cb * seg; i += 256) {
-          const int col = i / seg, j = i - col * seg;
-          st[j * P + col] = w[((long)(g * b + co0 + col) * c + ci0) * taps + j];
+      }
+      if (quad && taps == 1 && !pad) {  // a 1x1 weight without padding: the image is the source
+        for (int i = 4 * tid; i < tot; i += 1024) *(float4*)(img + i) = *(const float4*)(src + i);
+      } else if (quad) {
+        for (int i = 4 * tid; i < tot; i += 1024) {
+          const float4 v = *(const float4*)(src + i);
+          const float vv[4] = {v.x, v.y, v.z, v.w};
+          const int rc = i / taps;
+          int tap = i - rc * taps, rl = rc / b, ci = rc - rl * b;
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            img[rl * Kpad + tap * c + ci] = vv[j];
+            if (++tap == taps) {
+              tap = 0;
+              if (++ci == b) { ci = 0; ++rl; }
+            }
+          }
         }
-        __syncthreads();
-        for (int o = tid; o < seg * cb; o += 256) {
-          const int j = o / cb, col = o - j * cb;
-          const int cil = j / taps, tap = j - cil * taps;
-          const long idx = (r0 + cil) * Kpad + (long)tap * b + co0 + col;
-          if (idx >= beg && idx < end) TT<T>::st(out + idx, st[j * P + col]);
+      } else {
+        for (int i = tid; i < tot; i += 256) {
+          const int rc = i / taps, tap = i - rc * taps, rl = rc / b, ci = rc - rl * b;
+          img[rl * Kpad + tap * c + ci] = src[i];
         }
       }
-      // row padding (Kpad - taps * b < 8 elements)
-      for (int o = tid; o < nr * (Kpad - taps * b); o += 256) {
-        const int rl = o / (Kpad - taps * b), k = taps * b + o - rl * (Kpad - taps * b);
-        const long idx = (r0 + rl) * Kpad + k;
-        if (idx >= beg && idx < end) TT<T>::st(out + idx, 0.f);
-      }
-      r0 += nr;
+      __syncthreads();
+      pack_store_linear<T>(img, out + r0 * Kpad, nr * Kpad, vec, tid);
     }
   }
 }
@@ -1100,25 +1315,19 @@ int y3d_conv2d_bwd_weight(int dtype, const void* x, int64_t xsb, int64_t xsh, in
   if (route == Y3D_ROUTE_WGRAD_SMALL) {
     int rc = y3d_wgrad3x3_small_launch(x, xsb, xsh, xsw, dy, dsw, B, H, W, Cin, Cout, slab, nsplit, stream);
     if (rc) return rc;
-    launch_wgrad_reduce(slab, grad_oihw, nsplit, Cout, 9, Cin, Cin, accumulate, st);
-    Y3D_LAUNCH_CHECK();
-    return Y3D_OK;
+    return launch_wgrad_reduce(slab, grad_oihw, nsplit, Cout, 9, Cin, Cin, accumulate, st);
   }
   if (route == Y3D_ROUTE_WGRAD_TILE) {
     const int th = y3d_wgrad_tile_height(dtype, H, W, p.Cg, p.Cn, kh, kw, stride, pad);
     Y3D_CHECK(nsplit == y3d_wgrad_tile_splits(th, B, H, W, p.Cg, p.Cn, groups), "conv2d_bwd_weight: nsplit must come from y3d_conv2d_wgrad_plan");
     int rc = y3d_conv3x3_wgrad_tile_launch(th, x, xsb, xsh, xsw, dy, dsw, B, H, W, p.Cg, p.Cn, groups, slab, nsplit, stream);
     if (rc) return rc;
-    launch_wgrad_reduce(slab, grad_oihw, nsplit, Cout, kh * kw, p.Cg, p.Cg, accumulate, st);
-    Y3D_LAUNCH_CHECK();
-    return Y3D_OK;
+    return launch_wgrad_reduce(slab, grad_oihw, nsplit, Cout, kh * kw, p.Cg, p.Cg, accumulate, st);
   }
   if (route == Y3D_ROUTE_WGRAD_STREAM1X1) {
     int rc = y3d_wgrad1x1_stream_launch(x, xsw, dy, dsw, p.M, Cin, Cout, slab, nsplit, p.chunk_px, stream);
     if (rc) return rc;
-    launch_wgrad_reduce(slab, grad_oihw, nsplit, Cout, 1, Cin, Cin, accumulate, st);
-    Y3D_LAUNCH_CHECK();
-    return Y3D_OK;
+    return launch_wgrad_reduce(slab, grad_oihw, nsplit, Cout, 1, Cin, Cin, accumulate, st);
   }
   const int wd = wgrad_tile_w(p.Cn), wx = wgrad_tile_w(p.Ktot);
   dim3 grid(cdiv(p.Ktot, wx), cdiv(p.Cn, wd), groups * nsplit);
@@ -1136,9 +1345,12 @@ int y3d_conv2d_bwd_weight(int dtype, const void* x, int64_t xsb, int64_t xsh, in
 #undef Y3D_WGRAD
   Y3D_LAUNCH_CHECK();
   int cg_real = groups == 1 ? Cin_real : p.Cg;
-  launch_wgrad_reduce(slab, grad_oihw, nsplit, Cout, kh * kw, p.Cg, cg_real, accumulate, st);
-  Y3D_LAUNCH_CHECK();
-  return Y3D_OK;
+  return launch_wgrad_reduce(slab, grad_oihw, nsplit, Cout, kh * kw, p.Cg, cg_real, accumulate, st);
+}
+
+int y3d_wgrad_fold(const float* slab, int nsplit, int Cout, int taps, int Cin_g, int Cin_g_real, float* grad_oihw, int accumulate, void* stream) {
+  Y3D_CHECK(slab && grad_oihw && nsplit >= 1 && Cout >= 1 && Cin_g_real >= 1 && Cin_g_real <= Cin_g, "wgrad_fold: bad argument");
+  return launch_wgrad_reduce(slab, grad_oihw, nsplit, Cout, taps, Cin_g, Cin_g_real, accumulate, (hipStream_t)stream);
 }
 
 int y3d_mt_pack_weights(int dtype, const int64_t* desc, const int* chunk_tensor, const int* chunk_off, int nchunks, int chunk, void* stream) {

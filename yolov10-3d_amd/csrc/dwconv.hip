@@ -302,7 +302,12 @@ __global__ __launch_bounds__(256) void dwconv_wgrad_kernel(DwWP p) {
   }
 }
 
-// slab[nblk][taps][C] -> grad OIHW [C][1][kh][kw]; 8 lanes share the block loop of an element and fold through LDS
+// slab[nblk][taps][C] -> grad OIHW [C][1][kh][kw].  The summation order: 8 lanes share an element; lane sl adds the slabs
+// b = sl, sl + 8, ... in ascending order onto ONE running sum; lane 0 then adds the other lanes' sums in ascending lane order; with
+// `accumulate` the result is grad + sum.  A workgroup takes 32 consecutive elements of the slab order [tap][c] and ends in 4-byte
+// stores `taps` floats apart: the gradient is 1 / nblk (up to 1 / 1024) of the bytes.  Workgroups that own whole channels (float4
+// loads, the [c][tap] run transposed in LDS and stored in 16-byte pieces, as wgrad_reduce_rows_kernel in conv_gemm.hip) measured
+// slower on S-3D (6.4 -> 7.7 us per launch; 7x7 at 512 channels under 12.8 -> 16.9 us): 128 workgroups instead of 784 walk the slabs.
 __global__ __launch_bounds__(256) void dw_wgrad_reduce_kernel(const float* __restrict__ slab, float* __restrict__ grad, int nblk, int taps, int C,
                                                               int accumulate) {
   __shared__ float sh[8][32];
@@ -361,6 +366,12 @@ int y3d_dw_pack_weight(const float* w_oihw, float* out, int C, int kh, int kw, v
     else if (dgrad) { if (kk == 3) DW_LAUNCH_K(T, true, 3); else if (kk == 7) DW_LAUNCH_K(T, true, 7); else DW_LAUNCH_K(T, true, 0); }     \
     else { if (kk == 3) DW_LAUNCH_K(T, false, 3); else if (kk == 7) DW_LAUNCH_K(T, false, 7); else DW_LAUNCH_K(T, false, 0); }        \
   } while (0)
+
+static int dw_launch_fold(const float* slab, float* grad, int nblk, int taps, int C, int accumulate, hipStream_t st) {
+  hipLaunchKernelGGL(dw_wgrad_reduce_kernel, dim3(cdiv((long)C * taps, 32)), dim3(256), 0, st, slab, grad, nblk, taps, C, accumulate);
+  Y3D_LAUNCH_CHECK();
+  return Y3D_OK;
+}
 
 static int dw_launch(int dtype, bool dgrad, const DwP& p, hipStream_t st) {
   Y3D_CHECK(p.M < (1L << 31), "dwconv: more than 2^31 pixels");
@@ -462,9 +473,12 @@ int y3d_dwconv2d_bwd_weight(int dtype, const void* x, int64_t xsb, int64_t xsh, 
   if (dtype == Y3D_BF16) Y3D_DWW(bf16_t); else Y3D_DWW(float);
 #undef Y3D_DWW
   Y3D_LAUNCH_CHECK();
-  hipLaunchKernelGGL(dw_wgrad_reduce_kernel, dim3(cdiv((long)C * kh * kw, 32)), dim3(256), 0, st, slab, grad_oihw, nblk, kh * kw, C, accumulate);
-  Y3D_LAUNCH_CHECK();
-  return Y3D_OK;
+  return dw_launch_fold(slab, grad_oihw, nblk, kh * kw, C, accumulate, st);
+}
+
+int y3d_dw_wgrad_fold(const float* slab, int nblk, int C, int taps, float* grad_oihw, int accumulate, void* stream) {
+  Y3D_CHECK(slab && grad_oihw && nblk >= 1 && C >= 1 && taps >= 1, "dw_wgrad_fold: bad argument");
+  return dw_launch_fold(slab, grad_oihw, nblk, taps, C, accumulate, (hipStream_t)stream);
 }
 
 }  // extern "C"

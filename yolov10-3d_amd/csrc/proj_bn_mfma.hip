@@ -341,20 +341,27 @@ __global__ __launch_bounds__(256) void projg_bwd_weight_bn_mfma_kernel(PWP p) {
   if (tid < cout) p.bslab[(long)blockIdx.x * p.ctot + p.ooff[br] + tid] = bred[0][tid] + bred[1][tid] + bred[2][tid] + bred[3][tid];
 }
 
-// dw[br][o][ch] = sum_blk slab[blk][ooff + o][ch];  db[br][o] = sum_blk bslab[blk][ooff + o]
+// dw[br][o][ch] = sum_blk slab[blk][ooff + o][ch];  db[br][o] = sum_blk bslab[blk][ooff + o], both summed in ascending block order.
+// Eight slabs are loaded before they are added (in that same order): one load per add made the kernel a chain of nblk memory latencies.
+__device__ __forceinline__ float slab_sum_in_order(const float* __restrict__ src, long pitch, int nblk) {
+  float s = 0.f;
+  int b = 0;
+  for (; b + 8 <= nblk; b += 8) {
+    float v[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = src[(long)(b + j) * pitch];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) s += v[j];
+  }
+  for (; b < nblk; ++b) s += src[(long)b * pitch];
+  return s;
+}
+
 __global__ void projg_wslab_reduce_kernel(PWP p, int nblk, int cin) {
   const int br = blockIdx.y, cout = p.cout[br];
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx < cout * cin) {
-    float s = 0.f;
-    for (int b = 0; b < nblk; ++b) s += p.slab[((long)b * p.ctot + p.ooff[br]) * cin + idx];
-    p.dw[br][idx] = s;
-  }
-  if (idx < cout) {
-    float s = 0.f;
-    for (int b = 0; b < nblk; ++b) s += p.bslab[(long)b * p.ctot + p.ooff[br] + idx];
-    p.db[br][idx] = s;
-  }
+  if (idx < cout * cin) p.dw[br][idx] = slab_sum_in_order(p.slab + (long)p.ooff[br] * cin + idx, (long)p.ctot * cin, nblk);
+  if (idx < cout) p.db[br][idx] = slab_sum_in_order(p.bslab + p.ooff[br] + idx, p.ctot, nblk);
 }
 
 }  // namespace

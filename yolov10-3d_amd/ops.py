@@ -305,10 +305,16 @@ class _PackRegistry(_WeightRegistry):
     """Packed compute-dtype copies of the conv weights for the training step, refreshed by ONE multi-tensor launch per step
     (`y3d_mt_pack_weights`) instead of one tiny launch per conv and direction (S-3D: 113 launches of ~5 us + their gaps).
 
-    A weight is identified by (address, geometry); its packed buffer is persistent.  The first lookup after the weights changed
+    A weight is identified by (address, geometry, layout); its packed buffer is persistent.  The first lookup after the weights changed
     (WEIGHT_EPOCH moved: the fused optimizer wrote them) repacks every registered weight of that dtype from whatever its address holds
     now; a weight changed through torch (in-place op: its `_version` moved) is repacked on its own; an unknown weight is packed on its
-    own and registered."""
+    own and registered.
+
+    `mode` is the layout of the registry's weights (0: forward, 1: data gradient).  The depth-wise filters (layout 2: tap-major fp32,
+    what `y3d_dw_pack_weight` writes) are entries of the FORWARD registry with a layout of their own: they ride in its launch, and the
+    backward of a step finds the buffer its forward used."""
+
+    DW = 2
 
     CHUNK = 16384
 
@@ -320,7 +326,9 @@ class _PackRegistry(_WeightRegistry):
         L, st = lib(), stream()
         a, b, c, taps, kpad, dt = e["geo"]
         k = int(round(taps ** 0.5))
-        if self.mode == 0:
+        if e["mode"] == self.DW:
+            L.dw_pack_weight(e["src"], e["dst"].data_ptr(), b, k, k, st)
+        elif e["mode"] == 0:
             L.pack_weight_fwd(dt, e["src"], e["dst"].data_ptr(), a, b, c, k, k, st)
         else:
             L.pack_weight_dgrad(dt, e["src"], e["dst"].data_ptr(), a * b, c, a, k, k, st)
@@ -335,8 +343,8 @@ class _PackRegistry(_WeightRegistry):
             desc, ct, co = [], [], []
             for t, e in enumerate(ents):
                 a, b, c, taps, kpad, _ = e["geo"]
-                n = a * kpad if self.mode == 0 else a * c * kpad
-                desc += [e["src"], e["dst"].data_ptr(), a, b, c, taps, kpad, self.mode]
+                n = a * kpad if e["mode"] == 0 else a * c * kpad
+                desc += [e["src"], e["dst"].data_ptr(), a, b, c, taps, kpad, e["mode"]]
                 for j in range((n + self.CHUNK - 1) // self.CHUNK):
                     ct.append(t)
                     co.append(j)
@@ -347,20 +355,22 @@ class _PackRegistry(_WeightRegistry):
         lib().mt_pack_weights(dt, desc.data_ptr(), ct.data_ptr(), co.data_ptr(), n, self.CHUNK, stream())
         return ents
 
-    def lookup(self, w32, src_ptr, geo, dtype, ver=None):
+    def lookup(self, w32, src_ptr, geo, dtype, ver=None, mode=None):
         """geo = (a, b, c, taps, Kpad, dt) as y3d_mt_pack_weights; src_ptr: address of the (sub)tensor to pack -> packed tensor.
+        `mode`: the layout when it is not the registry's own (DW: dtype is torch.float32, dt the compute dtype whose launch it joins).
         `ver`: the torch-side version token of the weights (default: w32's own counter).  A stacked weight passes the counters of
         its per-branch Parameters: they are re-pointed at slices of the flat tensor with `.data =`, which shares storage but NOT the
         version counter, so torch-side writers (torch.optim, load_state_dict, init, broadcast) move only the Parameters' counters."""
-        key = (src_ptr, geo)
+        mode = self.mode if mode is None else mode
+        key = (src_ptr, geo, mode)
         ver = w32._version if ver is None else ver
         e = self.entries.get(key)
         if e is None:
             a, b, c, taps, kpad, dt = geo
-            n = a * kpad if self.mode == 0 else a * c * kpad
+            n = a * kpad if mode == 0 else a * c * kpad
             # "keep": the registry re-reads `src` at every epoch, so the storage behind it must outlive the entry
-            e = {"src": src_ptr, "geo": geo, "dst": torch.empty(n, dtype=dtype, device=w32.device), "ver": ver, "seen": WEIGHT_EPOCH,
-                 "keep": w32}
+            e = {"src": src_ptr, "geo": geo, "mode": mode, "dst": torch.empty(n, dtype=dtype, device=w32.device), "ver": ver,
+                 "seen": WEIGHT_EPOCH, "keep": w32}
             self.entries[key] = e
             self._pack_one(e)
         elif self._revisit(e, (WEIGHT_EPOCH, geo[5]), ver, lambda: self._pack_all(geo[5])):
@@ -418,6 +428,17 @@ class _QuantRegistry(_WeightRegistry):
 
 
 PACK_FWD, PACK_DGRAD, QUANT = _PackRegistry(0), _PackRegistry(1), _QuantRegistry()
+
+
+def _dw_packed(w32, C, k, dtype, ver):
+    """the tap-major fp32 copy of a depth-wise filter for a training step: from the forward pack registry, or packed on the spot"""
+    if PACK_CACHE:
+        return PACK_FWD.lookup(w32, w32.data_ptr(), (1, C, 1, k * k, k * k * C, code(dtype)), torch.float32, ver, _PackRegistry.DW)
+    wp = _f32(k * k * C, w32.device)
+    lib().dw_pack_weight(w32.data_ptr(), wp.data_ptr(), C, k, k, stream())
+    return wp
+
+
 WEIGHT_QUANT = None  # None | "fp8": conv (+BatchNorm) weights as e4m3fn codes with per-output-channel power-of-two scales
 
 
@@ -722,8 +743,7 @@ def _dw_forward(xin, w32, g32, b32, rm, rv, k, s, p, act, res, res_mode, trainin
     part = ss_eval = None
     if training:
         part = _f32(nblk * C * 2, dev)
-        wp = _f32(k * k * C, dev)
-        L.dw_pack_weight(w32.data_ptr(), wp.data_ptr(), C, k, k, st)
+        wp = _dw_packed(w32, C, k, dtype, ver[0] if ver is not None else None)
     else:
         wp, ss_eval = _eval_consts(cache, "dw", w32, g32, b32, rm, rv, ver, dtype, k, C, 1, 1, C, eps)
         if fused:
@@ -913,8 +933,7 @@ def _conv_backward(plan, saved, dy, dgb, dres, need_dx, dx_range, dx_out=None):
     dx = None
     dW = torch.empty_like(w32)
     if plan.dw:
-        wp = _f32(k * k * Cout, dev)
-        L.dw_pack_weight(w32.data_ptr(), wp.data_ptr(), Cout, k, k, st)
+        wp = _dw_packed(w32, Cout, k, dtype, plan.wver)  # (the buffer the forward of this step used)
         if need_dx:
             dx = nhwc_empty(B, Cin, H, W, dtype, dev)
             dsb, dsh, dsw = s3(dy)
