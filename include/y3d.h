@@ -513,6 +513,22 @@ int y3d_yolo2d_image_aug(const unsigned char* const* src, int n_src, const int* 
  * counts (B) int32 = the true number of survivors, which may exceed cap (the surplus is not stored). */
 int y3d_yolo2d_encode_labels(const float* rec, int n_rec, const int* lab_i, const float* lab_f, int B, int imgsz, int cap, float* cls,
                              float* bboxes, float* batch_idx, int* counts, void* stream);
+/* Width of a row of y3d_yolo2d_plan_batch's draw table (float64 values). */
+enum { Y3D_YOLO2D_DRAW_W = 56 };
+/* Batch plan over a 2D split held on the device (yolo2d_cache.hip, yolo2d.DeviceSplit), one workgroup per sample: the five record
+ * arrays of y3d_yolo2d_image_aug and y3d_yolo2d_encode_labels from the split's frame tables and one table of draws.  Frame tables, on
+ * the device, indexed by dataset position (N frames): frame_hw (N, 2) int32 (h0, w0); rec_span (N, 2) int32 = (first row, rows) in the
+ * split's label rows.  draws (B, Y3D_YOLO2D_DRAW_W) float64 on the device, draws_host the same table in host memory.  A row: two layers
+ * of 23 (the sample, its MixUp partner): [present, mosaic, warp, frame position of tiles 0..3 (-1: none; one tile without mosaic), yc,
+ * xc, canvas side, M 2x3 (float32 values), M_inv (6), scale]; then at 46: mix, r, hsv, the three HSV gains, flipud, fliplr, bgr, 0.
+ * Positions of used tiles outside [0, N), and a sample without its first layer, are refused from draws_host before the launch.  The
+ * kernel derives load_image's resized size, the mosaic rectangles or the letter-box placement and the pads from frame_hw and imgsz
+ * (yolo2d_cache.hip states the arithmetic), and the HSV tables from the gains.  Outputs, on the device, in the layouts stated above:
+ * rec_i (B, 112) int32 with source index = dataset position, rec_f (B, 16) float64, lut (B, 3, 256) uint8 (4-byte aligned; zeros
+ * without the hsv flag), lab_i (B, 20) int32 with rows counted in the split's label rows, lab_f (B, 48) float32.  Every element of the B
+ * rows is written.  Neither allocates nor synchronises. */
+int y3d_yolo2d_plan_batch(const int* frame_hw, const int* rec_span, int N, int imgsz, const double* draws_host, const double* draws, int B,
+                          int* rec_i, double* rec_f, unsigned char* lut, int* lab_i, float* lab_f, void* stream);
 /* Rectangular letter-box of decoded images into one (H, W) canvas, H != W allowed (letterbox.hip states the arithmetic): the image side
  * of a rect=True validation sample (data/base.py load_image :147-182 + data/augment.py LetterBox.__call__ :696-742, Format._format_img
  * :950-957) and of the predictor's preprocess (engine/predictor.py:115-156).  src_table: DEVICE table of n_src device pointers to

@@ -508,6 +508,56 @@ def plan_batch(split, draws, draws_dev=None, out=None):
     return out
 
 
+def fill_arena(arena, offsets, padded, decode, pool, chunk):
+    """Fills a uint8 device arena with decoded frames.  `decode(pos)` -> frame pos as an (H, W, 3) uint8 array (it raises for a frame it
+    does not accept); the frame lands at byte offsets[pos], where padded[pos] bytes are its own.  Runs of consecutive frames of at most
+    `chunk` bytes are decoded by the threads of `pool` into a pinned stage and reach the arena in one copy per run."""
+    N = len(offsets)
+    runs, first = [], 0
+    for pos in range(1, N + 1):
+        if pos == N or offsets[pos] + padded[pos] - offsets[first] > chunk:
+            runs.append((first, pos))
+            first = pos
+    stage = torch.zeros(max(int(offsets[b - 1] + padded[b - 1] - offsets[a]) for a, b in runs), dtype=torch.uint8).pin_memory()
+    stage_np = stage.numpy()
+
+    def put(pos, base):
+        px = decode(pos)
+        o = int(offsets[pos]) - base
+        stage_np[o:o + px.size] = px.reshape(-1)
+
+    for a, b in runs:
+        base, end = int(offsets[a]), int(offsets[b - 1] + padded[b - 1])
+        list(pool.map(lambda pos: put(pos, base), range(a, b)))
+        arena[base:end].copy_(stage[:end - base])  # from pinned memory; returns when the stage may be refilled
+
+
+class DrawRing:
+    """`n` pinned (rows, width) float64 draw tables in flight to `device`: `upload(rows)` writes a table into the next buffer and starts
+    a non-blocking copy -> (host view, device tensor).  A buffer is rewritten only after the copy that last read it has run (one event
+    per buffer)."""
+
+    def __init__(self, width, device, n):
+        self.width, self.device, self.n, self._r = int(width), device, int(n), None
+
+    def upload(self, rows):
+        B = len(rows)
+        if self._r is None or self._r["host"][0].shape[0] < B:
+            cap = max(64, B)
+            self._r = {"host": [torch.empty(cap, self.width, dtype=torch.float64).pin_memory() for _ in range(self.n)],
+                       "event": [torch.cuda.Event() for _ in range(self.n)], "next": 0}
+        r = self._r
+        k = r["next"]
+        r["next"] = (k + 1) % self.n
+        r["event"][k].synchronize()  # (returns at once for an event never recorded)
+        host = r["host"][k][:B]
+        host.numpy()[:] = rows
+        dev = torch.empty(B, self.width, dtype=torch.float64, device=self.device)
+        dev.copy_(host, non_blocking=True)
+        r["event"][k].record()
+        return host, dev
+
+
 class DeviceSplit:
     """A KITTI split decoded once and held on the device: `DeviceSplit(root_or_split_file, mode)` resolves the split as build_batch does,
     checks the bytes it needs against `max_bytes` (default: half of the device's free memory) from the PNG headers alone, then decodes
@@ -578,30 +628,19 @@ class DeviceSplit:
             self.mean_size = up(np.asarray(CLS_MEAN_SIZE, np.float64).reshape(-1, 3), torch.float64)
             # the arena: runs of consecutive frames decoded into a pinned stage, one copy per run
             self.arena = torch.empty(self.nbytes, dtype=torch.uint8, device=dev)
-            runs, first = [], 0
-            for pos in range(1, N + 1):
-                if pos == N or self.offsets[pos] + padded[pos] - self.offsets[first] > self.CHUNK:
-                    runs.append((first, pos))
-                    first = pos
-            stage = torch.zeros(max(int(self.offsets[b - 1] + padded[b - 1] - self.offsets[a]) for a, b in runs), dtype=torch.uint8).pin_memory()
-            stage_np = stage.numpy()
 
-            def decode(pos, base):
+            def decode(pos):
                 with Image.open(path("image_2", self.ids[pos], "png")) as im:
                     px = np.array(im.convert("RGB"))
                 w, h = self.wh[pos]
                 if px.shape != (h, w, 3):
                     raise Y3DError(f"DeviceSplit: frame {self.ids[pos]:06d} decodes to {px.shape}, its header said {(h, w, 3)}")
-                o = int(self.offsets[pos]) - base
-                stage_np[o:o + px.size] = px.reshape(-1)
+                return px
 
-            for a, b in runs:
-                base, end = int(self.offsets[a]), int(self.offsets[b - 1] + padded[b - 1])
-                list(pool.map(lambda pos: decode(pos, base), range(a, b)))
-                self.arena[base:end].copy_(stage[:end - base])  # from pinned memory; returns when the stage may be refilled
+            fill_arena(self.arena, self.offsets, padded, decode, pool, self.CHUNK)
         finally:
             pool.shutdown()
-        self._ring = None
+        self._ring = DrawRing(_DRAW_W, dev, self.RING)
 
     def __len__(self):
         return len(self.ids)
@@ -620,25 +659,6 @@ class DeviceSplit:
         w, h = self.wh[pos]
         o = int(self.offsets[pos])
         return self.arena[o:o + h * w * 3].view(h, w, 3)
-
-    def _upload(self, rows):
-        """the draw table through the next pinned buffer of the ring, non-blocking -> (host view, device tensor).  A buffer is rewritten
-        only after the copy that last read it has run (one event per buffer)."""
-        B = len(rows)
-        if self._ring is None or self._ring["host"][0].shape[0] < B:
-            cap = max(64, B)
-            self._ring = {"host": [torch.empty(cap, _DRAW_W, dtype=torch.float64).pin_memory() for _ in range(self.RING)],
-                          "event": [torch.cuda.Event() for _ in range(self.RING)], "next": 0}
-        r = self._ring
-        k = r["next"]
-        r["next"] = (k + 1) % self.RING
-        r["event"][k].synchronize()  # (returns at once for an event never recorded)
-        host = r["host"][k][:B]
-        host.numpy()[:] = rows
-        dev = torch.empty(B, _DRAW_W, dtype=torch.float64, device=self.device)
-        dev.copy_(host, non_blocking=True)
-        r["event"][k].record()
-        return host, dev
 
     def build_batch(self, indices, args, mode="train", compact=False, img_mode="uint8", resolution=RESOLUTION):
         """`build_batch(path, indices, args, device, ...)` from the resident split: the same dictionary, bit for bit.  With compact=False
@@ -659,7 +679,7 @@ class DeviceSplit:
                 raise Y3DError(f"build_batch: mixup partner {d['partner']} of position {pos} has another size")
             rows.append(np.concatenate(([pos, d["partner"], d["flip"], d["scale"]], d["trans"].reshape(6), d["trans_inv"].reshape(6))))
         with torch.cuda.device(self.device):
-            host, dev = self._upload(rows)
+            host, dev = self._ring.upload(rows)
             plan = plan_batch(self, host, dev)
             W, H = int(resolution[0]), int(resolution[1])
             if img_mode == "float":

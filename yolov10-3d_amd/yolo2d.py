@@ -16,6 +16,11 @@ Rectangular validation batches (the validator's `rect=True` dataset: `set_rectan
 its own stride-multiple (H, W) canvas (`y3d_letterbox_image`, `y3d_letterbox_labels`, csrc/letterbox.hip) and returns the `ratio_pad`
 that `metrics.BoxStats.update_2d` reads.  `Split(rect=True)` itself keeps raising.
 
+`DeviceSplit` and `DeviceRectSplit` are the same two splits decoded once and held on the device (the reference's `cache="ram"`, one step
+further): a batch from them is the draws, one small pinned upload and three launches (`y3d_yolo2d_plan_batch`, csrc/yolo2d_cache.hip,
+writes the records of the two kernels from the draws and the split's frame tables), or for a rect batch two launches over records
+computed at load — the same batch bit for bit, without opening a file.
+
 Not covered (each raises Y3DError where it can be asked for): rect training batches, segments / keypoints / obb, copy_paste > 0,
 perspective != 0, Albumentations, the RNG streams of multi-worker loaders, the mosaic 3 / 9 grids.
 """
@@ -458,15 +463,25 @@ def build_batch(split, indices, args, device, mode="train", max_boxes=None, comp
     work on the device.  -> {"img", "cls", "bboxes", "batch_idx", "counts", "im_file", "ori_shape", "resized_shape"}; the per-box keys in
     encode_labels' static layout, or with compact=True (one read-back of the counts) in collate_fn's ragged shapes.  img_mode
     "uint8": (B, S, S, 3) uint8 in Format's channel order for the stem; "float": (B, 3, S, S) float32 in [0, 1].
-    A `RectSplit` (mode "val" only) gives the validator's rectangular batch instead: see `_build_rect_batch`."""
-    import numpy as np
+    A `RectSplit` (mode "val" only) gives the validator's rectangular batch instead: see `_build_rect_batch`.  A `DeviceSplit` or a
+    `DeviceRectSplit` builds the same batch from its resident frames (their `build_batch`), on the device it lives on."""
     if torch.device(device).type != "cuda":
         raise Y3DError("build_batch: the batch is built on a HIP device (no host fallback)")
     if img_mode not in ("uint8", "float"):
         raise ValueError("img_mode must be 'uint8' or 'float'")
     _loss.check_max_boxes(max_boxes)
+    if isinstance(split, (DeviceSplit, DeviceRectSplit)):
+        split.check_device(device)
+        return split.build_batch(indices, args, mode=mode, max_boxes=max_boxes, compact=compact, img_mode=img_mode)
     if isinstance(split, RectSplit):
         return _build_rect_batch(split, indices, args, device, mode, max_boxes, compact, img_mode)
+    return _build_square_batch(split, indices, args, device, mode, max_boxes, compact, img_mode)
+
+
+def _build_square_batch(split, indices, args, device, mode, max_boxes, compact, img_mode):
+    """build_batch over a `Split`, through `split.decode`: the host builds the five record arrays, the pointer table and the label table
+    of the batch's own frames and uploads them.  (Over a `DeviceSplit` it opens no file either: `decode` is a view of the arena.)"""
+    import numpy as np
     samples = [sample_augment(split, i, args, mode) for i in indices]
     frames = sorted({t["frame"] for x in samples for pre in (x["pre"], x["pre2"]) if pre is not None for t in pre["tiles"]})
     slot = {f: n for n, f in enumerate(frames)}
@@ -698,3 +713,264 @@ def _build_rect_batch(split, indices, args, device, mode, max_boxes, compact, im
     else:
         batch.update({k: lab[k] for k in ("cls", "bboxes", "batch_idx")})
     return batch
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# the split resident on the device: decoded once, then a batch is the draws, one small upload and three launches
+# ------------------------------------------------------------------------------------------------------------------------------
+_DRAW_W, _DRAW_LAYER, _DRAW_TAIL = 56, 23, 46  # Y3D_YOLO2D_DRAW_W (include/y3d.h): two layers of 23, then the sample's own nine values
+_ALIGN = 16  # every frame starts on a multiple of 16 bytes of the arena (both image kernels read their sources byte by byte)
+PLAN_TABLES = (("rec_i", torch.int32, (_REC_I,)), ("rec_f", torch.float64, (_REC_F,)), ("lut", torch.uint8, (3, 256)),
+               ("lab_i", torch.int32, (_LAB_I,)), ("lab_f", torch.float32, (_LAB_F,)))
+
+
+def draw_table(samples):
+    """sample_augment's records -> the (B, 56) float64 draw table of `y3d_yolo2d_plan_batch`.  Per layer (the sample at 0, its MixUp
+    partner at 23): [present, mosaic, warp, the frame positions of tiles 0..3 (-1: no such tile), yc, xc, canvas, M[:2] (6), M_inv (6),
+    scale]; then at 46: mix, r, hsv, the three gains, flipud, fliplr, bgr, 0.  Every value is carried exactly (M is float32)."""
+    import numpy as np
+    d = np.zeros((len(samples), _DRAW_W), np.float64)
+    for b, s in enumerate(samples):
+        for l, pre in enumerate((s["pre"], s["pre2"])):
+            if pre is None:
+                continue
+            o = l * _DRAW_LAYER
+            frames = [t["frame"] for t in pre["tiles"]]
+            d[b, o:o + 3] = (1, pre["mosaic"], pre["warp"])
+            d[b, o + 3:o + 7] = frames + [-1] * (4 - len(frames))
+            d[b, o + 7:o + 10] = (pre["yc"], pre["xc"], pre["canvas"])
+            d[b, o + 10:o + 16] = np.asarray(pre["M"], np.float32)[:2].reshape(6)
+            d[b, o + 16:o + 22] = pre["M_inv"]
+            d[b, o + 22] = pre["scale"]
+        hsv = s["hsv_gain"] is not None
+        d[b, _DRAW_TAIL:_DRAW_TAIL + 3] = (s["pre2"] is not None, s["r"], hsv)
+        if hsv:
+            d[b, _DRAW_TAIL + 3:_DRAW_TAIL + 6] = s["hsv_gain"]
+        d[b, _DRAW_TAIL + 6:_DRAW_TAIL + 9] = (s["flipud"], s["fliplr"], not s["rgb"])
+    return d
+
+
+def plan_batch(split, draws, draws_dev=None, out=None):
+    """The five record arrays of `y3d_yolo2d_image_aug` and `y3d_yolo2d_encode_labels` for a draw table over a DeviceSplit, one HIP launch
+    (`y3d_yolo2d_plan_batch`), no allocation when `out` is given and no synchronisation (capturable).  draws: (B, 56) float64 on the host
+    (numpy or tensor), rows as `draw_table` writes them; draws_dev: the same table on the device (uploaded here when None).  Frame
+    positions outside the split are refused from the host table.  out: optionally the five output tensors (at least B rows each; the
+    first B are written).  -> dict rec_i (B, 112) int32 with source index = dataset position, rec_f (B, 16) float64, lut (B, 3, 256)
+    uint8, lab_i (B, 20) int32 with rows counted in `split.rec`, lab_f (B, 48) float32."""
+    host = torch.as_tensor(draws)
+    if host.dim() != 2 or host.shape[1] != _DRAW_W or host.dtype != torch.float64 or host.is_cuda or not host.is_contiguous():
+        raise Y3DError(f"plan_batch: the draws are a contiguous (B, {_DRAW_W}) float64 table on the host, got {tuple(host.shape)} {host.dtype}")
+    B, dev = host.shape[0], split.device
+    if draws_dev is None:
+        draws_dev = host.to(dev)
+    if draws_dev.shape != host.shape or draws_dev.dtype != torch.float64 or draws_dev.device != dev or not draws_dev.is_contiguous():
+        raise Y3DError("plan_batch: the device copy of the draws must match the host table and live on the split's device")
+    if out is None:
+        out = {k: torch.empty(B, *s, dtype=dt, device=dev) for k, dt, s in PLAN_TABLES}
+    for k, dt, s in PLAN_TABLES:
+        t = out[k]
+        if t.dtype != dt or t.device != dev or t.dim() != 1 + len(s) or t.shape[0] < B or tuple(t.shape[1:]) != s or not t.is_contiguous():
+            raise Y3DError(f"plan_batch: output {k} must be a contiguous ({B}+, {', '.join(map(str, s))}) {dt} tensor on {dev}")
+    lib().yolo2d_plan_batch(split.frame_hw.data_ptr(), split.rec_span.data_ptr(), len(split), split.imgsz, host.data_ptr(), draws_dev.data_ptr(),
+                            B, *[out[k].data_ptr() for k, _, _ in PLAN_TABLES], ops.stream())
+    return out
+
+
+def _hip_device(device, what):
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise Y3DError(f"{what}: the split is held on a HIP device, not {dev} (no host fallback)")
+    return dev
+
+
+def _decode_rgb(path):
+    """`Split.decode`'s arithmetic on the host: (h0, w0, 3) uint8 RGB, the EXIF orientation applied"""
+    import numpy as np
+    from PIL import Image, ImageOps
+    with Image.open(path) as im:
+        return np.array(ImageOps.exif_transpose(im).convert("RGB"))
+
+
+class _Resident:
+    """What DeviceSplit and DeviceRectSplit share: the frames of a `Split` decoded once into one uint8 device arena, and the frame tables
+    indexed by dataset position (the position in `im_files`): `arena`; `img_off` (N) int64; `frame_hw` (N, 2) int32 (h0, w0); `src` (N)
+    int64 device pointers arena + offset, the pointer table both image kernels take with n_src = N; `rec` (R, 5) float32, all label rows
+    in file order (one dummy row when there is none; `n_rec` = R); `rec_span` (N, 2) int32 (first row, rows)."""
+
+    RING = 4  # pinned draw tables in flight
+    CHUNK = 256 << 20  # bytes of decoded frames per upload
+
+    def _load(self, dev, max_bytes, workers):
+        import numpy as np
+        from concurrent.futures import ThreadPoolExecutor
+        from .kitti import DrawRing, fill_arena
+        N = self.ni
+        # sizes from the file headers (Split.size's EXIF rule), the budget before anything is decoded or allocated
+        hw = np.array([self.size(i) for i in range(N)], np.int64).reshape(N, 2)
+        size = hw[:, 0] * hw[:, 1] * 3
+        padded = (size + _ALIGN - 1) // _ALIGN * _ALIGN
+        self.offsets = np.concatenate(([0], np.cumsum(padded)[:-1])).astype(np.int64)
+        self.nbytes = int(padded.sum())
+        allowed = int(max_bytes) if max_bytes is not None else torch.cuda.mem_get_info(dev)[0] // 2
+        if self.nbytes > allowed:
+            raise Y3DError(f"{type(self).__name__}: the {N} decoded frames need {self.nbytes} bytes, {allowed} bytes are allowed (max_bytes)")
+        if dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        self.device = dev
+        up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a)).to(device=dev, dtype=dt)
+        n_rows = [len(r) for r in self.labels]
+        span = np.zeros((N, 2), np.int32)
+        span[:, 1] = n_rows
+        span[1:, 0] = np.cumsum(n_rows)[:-1]
+        self.n_rec = int(sum(n_rows))
+        self.span_host = span
+        rec = np.concatenate(self.labels).astype(np.float32).reshape(-1, 5) if self.n_rec else np.zeros((1, 5), np.float32)
+        self.rec, self.rec_span = up(rec, torch.float32), up(span, torch.int32)
+        self.img_off, self.frame_hw = up(self.offsets, torch.int64), up(hw, torch.int32)
+        # the arena: runs of consecutive frames decoded into a pinned stage, one copy per run
+        self.arena = torch.empty(self.nbytes, dtype=torch.uint8, device=dev)
+        self.src = up(self.arena.data_ptr() + self.offsets, torch.int64)
+
+        def decode(pos):
+            px = _decode_rgb(self.im_files[pos])
+            h, w = self._hw0[pos]
+            if px.shape != (h, w, 3):
+                raise Y3DError(f"{type(self).__name__}: {self.im_files[pos]} decodes to {px.shape}, its header said {(h, w, 3)}")
+            return px
+
+        pool = ThreadPoolExecutor(max_workers=min(int(workers), 16))
+        try:
+            fill_arena(self.arena, self.offsets, padded, decode, pool, self.CHUNK)
+        finally:
+            pool.shutdown()
+        self._ring = DrawRing(_DRAW_W, dev, self.RING)
+
+    def check_device(self, device):
+        d = torch.device(device)
+        if d.type != "cuda" or (d.index is not None and d.index != self.device.index):
+            raise Y3DError(f"build_batch: the split lives on {self.device}, a batch on {d} was asked for")
+
+    def frame(self, pos):
+        """the decoded frame at a dataset position: an (h0, w0, 3) uint8 view of the arena"""
+        h, w = self._hw0[pos]
+        o = int(self.offsets[pos])
+        return self.arena[o:o + h * w * 3].view(h, w, 3)
+
+    def decode(self, i, device):
+        """`Split.decode` without the file: the arena view of frame i"""
+        self.check_device(device)
+        return self.frame(int(i))
+
+
+class DeviceSplit(_Resident, Split):
+    """A `Split` decoded once and held on the device (the reference's `YOLODataset(cache="ram")`, one step further): the files are listed
+    and the labels read as `Split` does, the sizes come from the file headers, the bytes needed are checked against `max_bytes` (default:
+    half of the device's free memory) before anything is decoded, then every frame is decoded with `min(workers, 16)` threads into one
+    uint8 arena (each frame (h0, w0, 3) RGB at a multiple of 16 bytes, uploaded in large pinned chunks) next to the frame tables of
+    `_Resident`.  Originals only: the image kernel samples the original frame.
+
+    `build_batch` then returns what `build_batch(Split(...), ...)` returns, bit for bit, without touching a file: `sample_augment` per
+    index (the same draws, the same buffer), one non-blocking upload of the draw table from a ring of pinned buffers and three launches
+    (`plan_batch`, the image augmentation over the split's pointer table, the label encoder over the split's label rows).  `decode` is a
+    view of the arena, so the host-built path (`_build_square_batch`) runs on a DeviceSplit as well, and opens no file either."""
+
+    def __init__(self, img_dir_or_list, imgsz=640, batch=16, augment=True, device="cuda", max_bytes=None, workers=8):
+        dev = _hip_device(device, "DeviceSplit")
+        if int(workers) < 1:
+            raise Y3DError(f"DeviceSplit: workers = {workers}")
+        Split.__init__(self, img_dir_or_list, imgsz, batch, augment)
+        self._load(dev, max_bytes, workers)
+
+    def build_batch(self, indices, args, mode="train", max_boxes=None, compact=False, img_mode="uint8"):
+        """`build_batch(split, indices, args, device, ...)` from the resident split: the same dictionary, bit for bit.  With compact=False
+        nothing here waits for the device (but a ring buffer still in flight) and no file is opened."""
+        if img_mode not in ("uint8", "float"):
+            raise ValueError("img_mode must be 'uint8' or 'float'")
+        _loss.check_max_boxes(max_boxes)
+        samples = [sample_augment(self, i, args, mode) for i in indices]
+        if not samples:
+            raise Y3DError("build_batch: an empty batch")
+        s = self.imgsz
+        with torch.cuda.device(self.device):
+            host, dev = self._ring.upload(draw_table(samples))
+            plan = plan_batch(self, host, dev)
+            img = augment_images({"src": self.src, "rec_i": plan["rec_i"], "rec_f": plan["rec_f"], "lut": plan["lut"], "imgsz": s}, img_mode)
+            lab = encode_labels({"rec": self.rec, "n_rec": self.n_rec, "lab_i": plan["lab_i"], "lab_f": plan["lab_f"]}, s, max_boxes)
+        batch = {"img": img, "im_file": [self.im_files[x["index"]] for x in samples], "ori_shape": [self.size(x["index"]) for x in samples],
+                 "resized_shape": [(s, s) for _ in samples], "counts": lab["counts"]}
+        if compact:
+            batch.update(compact_labels(lab, lab["counts"].tolist(), max_boxes))
+        else:
+            batch.update({k: lab[k] for k in ("cls", "bboxes", "batch_idx")})
+        return batch
+
+    def epoch(self, batch, args, mode="train", shuffle=True, seed=0, drop_last=False, **kw):
+        """One epoch of batches: `build_batch` over `kitti.epoch_indices(len(self), batch, shuffle, seed, drop_last)`.  A build only
+        enqueues work on the current stream, so building the next batch already overlaps the step that consumes this one."""
+        from .kitti import epoch_indices
+        for idx in epoch_indices(len(self), batch, shuffle, seed, drop_last):
+            yield self.build_batch(idx, args, mode=mode, **kw)
+
+
+class DeviceRectSplit(_Resident, RectSplit):
+    """A `RectSplit` held on the device: the arena and frame tables of `_Resident`, indexed by the split's (aspect-ratio sorted) positions.
+    A rect split has no randomness but Format's bgr draw, so the records of every batch are computed once at load with the host
+    functions of the path-based builder (`rect_sample`, `rect_records`), with source index = position and label rows counted in `rec`,
+    and uploaded once: `lb_rec` (N, 8) int32, `lb_lab_i` (N, 2) int32, `lb_lab_f` (N, 4) float32.  `build_batch` over a run of
+    consecutive positions of one rect batch (what `batches()` lists) is then two launches over slices of those tables: no upload, no
+    file.  Any other index list of one rect batch goes through the host-built path over the arena (`_build_rect_batch`)."""
+
+    def __init__(self, img_dir_or_list, imgsz=640, batch=16, stride=32, pad=0.5, device="cuda", max_bytes=None, workers=8):
+        import numpy as np
+        dev = _hip_device(device, "DeviceRectSplit")
+        if int(workers) < 1:
+            raise Y3DError(f"DeviceRectSplit: workers = {workers}")
+        RectSplit.__init__(self, img_dir_or_list, imgsz, batch, stride, pad)
+        self._load(dev, max_bytes, workers)
+        state = random.getstate()  # rect_sample draws Format's bgr number; the load leaves the generator as it found it
+        try:
+            self._samples = [rect_sample(self, i) for i in range(self.ni)]
+        finally:
+            random.setstate(state)
+        same = {i: i for i in range(self.ni)}
+        rec, li, lf = rect_records(self, self._samples, same, {i: int(self.span_host[i, 0]) for i in range(self.ni)})
+        rec[:, 7] = 0  # a draw that asks for BGR (p_bgr == 0.0) is served by the host-built path
+        for r, s in zip(rec, self._samples):
+            H, W = s["canvas"]
+            if min(r[1:5]) < 1 or r[5] < 0 or r[6] < 0 or r[5] + r[3] > H or r[6] + r[4] > W or W % 4:
+                raise Y3DError(f"DeviceRectSplit: {self.im_files[s['index']]} does not fit its {H} x {W} canvas")
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.device)
+        self.lb_rec, self.lb_lab_i, self.lb_lab_f = up(rec), up(li), up(lf)
+
+    def build_batch(self, indices, args, mode="val", max_boxes=None, compact=False, img_mode="uint8"):
+        """`build_batch(rect_split, indices, args, device, mode="val", ...)` from the resident split: the same dictionary, bit for bit"""
+        if img_mode not in ("uint8", "float"):
+            raise ValueError("img_mode must be 'uint8' or 'float'")
+        _loss.check_max_boxes(max_boxes)
+        _check_args(args)
+        if mode != "val":
+            raise Y3DError(f"yolo2d: a RectSplit builds validation batches only (mode {mode!r}); rect training batches are not supported")
+        indices = [int(i) for i in indices]
+        if not indices:
+            raise Y3DError("yolo2d: an empty rect batch")
+        ks = {self.batch_of(i) for i in indices}
+        if len(ks) != 1:
+            raise Y3DError(f"yolo2d: indices of rect batches {sorted(ks)}: a rect batch has one shape, build them one at a time")
+        a, b = indices[0], indices[0] + len(indices)
+        state = random.getstate()
+        rgb = [random.uniform(0, 1) > 0.0 for _ in indices]  # Format's bgr draw of every sample, as rect_sample draws it
+        if indices != list(range(a, b)) or not all(rgb):
+            random.setstate(state)
+            return _build_rect_batch(self, indices, args, self.device, mode, max_boxes, compact, img_mode)
+        samples = self._samples[a:b]
+        H, W = samples[0]["canvas"]
+        with torch.cuda.device(self.device):
+            img = letterbox_images({"src": self.src, "rec": self.lb_rec[a:b], "H": H, "W": W}, img_mode)
+            lab = letterbox_labels({"rec": self.rec, "n_rec": self.n_rec, "lab_i": self.lb_lab_i[a:b], "lab_f": self.lb_lab_f[a:b]}, H, W, max_boxes)
+        batch = {"img": img, "im_file": [self.im_files[i] for i in indices], "ori_shape": [(s["h0"], s["w0"]) for s in samples],
+                 "resized_shape": [(H, W) for _ in samples], "ratio_pad": [s["ratio_pad"] for s in samples], "counts": lab["counts"]}
+        if compact:
+            batch.update(compact_labels(lab, lab["counts"].tolist(), max_boxes))
+        else:
+            batch.update({k: lab[k] for k in ("cls", "bboxes", "batch_idx")})
+        return batch
