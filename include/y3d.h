@@ -440,7 +440,8 @@ int y3d_kitti_image_aug(const unsigned char* const* src, const unsigned char* co
  * predsO (B, K, C), predsM (B, KM, C) post-processed rows [xyxy | ... | depth (C-4) | depth log-variance (C-3) | score | label (C-1)];
  * the one-to-many rows with IoU > iou_thres, the same label and exp(-log-variance) > thres vote on the depth through a weighted
  * gaussian kernel density (silverman bandwidth as scikit-learn defines it), evaluated at nprop float32 proposals between the
- * extreme votes; out (B, K, C) = predsO with the most likely proposal as depth. */
+ * extreme votes; out (B, K, C) = predsO with the most likely proposal as depth.  KM <= 3902: the votes of one detection are kept in
+ * 64 KiB of LDS; more is an error and nothing is written. */
 int y3d_kde_depth_fusion(const float* predsO, int B, int K, const float* predsM, int KM, int C, float thres, float iou_thres, int nprop,
                          float* out, void* stream);
 /* KITTI decode of the post-processed detections (data/datasets/kitti.py:519-576 `decode_preds`, called by the validator's

@@ -1,6 +1,6 @@
 // One row of the KITTI decode (data/datasets/kitti.py:519-576), shared by kitti_decode_kernel (post.hip) and predict3d_rows_kernel
 // (predict3d.hip) so that both compute the same bits.  The reference promotes the float32 predictions to float64 through the
-// calibration constants; the float32 steps (heading angle, sigmoid, exp, size residual) are kept in float32 here as there.  The
+// calibration constants; the float32 steps (heading angle, sigmoid, exp) are kept in float32 here as there; the size is a float64 sum stored as float32.  The
 // library is built with contraction off: the order of the operations below is the result.
 #pragma once
 #include "common.h"
@@ -23,7 +23,10 @@ __device__ __forceinline__ void kitti_decode_row(const float* __restrict__ r, co
   const double alpha = (double)ang;
   const double x1 = (double)r[0] / rw, y1 = (double)r[1] / rh, x2 = (double)r[2] / rw, y2 = (double)r[3] / rh;
   const double xc = (x1 + x2) / 2;
-  const float h = r[6] + (float)mean_size[cm * 3 + 0], w = r[7] + (float)mean_size[cm * 3 + 1], l = r[8] + (float)mean_size[cm * 3 + 2];
+  // `dimensions += cls_mean_size[cls]` on a float32 array with a float64 table: numpy adds in float64 and rounds the SUM to float32
+  // (adding the table rounded to float32 is one ulp off in about a tenth of the rows)
+  const float h = (float)((double)r[6] + mean_size[cm * 3 + 0]), w = (float)((double)r[7] + mean_size[cm * 3 + 1]),
+              l = (float)((double)r[8] + mean_size[cm * 3 + 2]);
   const double depth = (double)r[33];
   const double sigma = (double)expf(-r[34]);
   double u, v;

@@ -317,7 +317,8 @@ __global__ __launch_bounds__(256) void kitti_aug_kernel(AugP p, void* __restrict
 
 // ---- f2: one-to-many depth fusion of the validator (models/yolov10_3D/val.py:78-102) -------------------------------------------------
 // one block per one-to-one detection: collect the votes (itself + matching one-to-many rows, in index order), then the weighted
-// gaussian kernel density at NPROP proposals (double precision, as scikit-learn), first maximum of the log-density
+// gaussian kernel density at NPROP proposals (double precision, as scikit-learn), first maximum of the log-density.
+// LDS: 16 * KM + 3088 bytes dynamic and 12 bytes static; the wrapper admits KM <= 3902 (64 KiB in all, no opt-in to more)
 __global__ __launch_bounds__(256) void kde_fusion_kernel(const float* __restrict__ O, const float* __restrict__ M, float* __restrict__ out, int K, int KM,
                                                          int C, float thres, float iou_thres, int nprop) {
   extern __shared__ float sm[];       // (one dynamic-LDS symbol per translation unit: float[], viewed as doubles here; 16-byte aligned)
@@ -625,8 +626,11 @@ int y3d_kitti_image_aug(const unsigned char* const* src, const unsigned char* co
 int y3d_kde_depth_fusion(const float* predsO, int B, int K, const float* predsM, int KM, int C, float thres, float iou_thres, int nprop,
                          float* out, void* stream) {
   Y3D_CHECK(predsO && predsM && out && B >= 1 && K >= 1 && KM >= 1 && C >= 8 && nprop >= 2, "kde_depth_fusion: bad arguments");
+  // dynamic LDS (votes, weights, the block's arg-max) plus the kernel's three static words (nv, s_lo, s_hi: 12 bytes, counted as 16,
+  // which covers any alignment of the dynamic segment behind them) must fit the 64 KiB a launch gets without an opt-in:
+  // 16 * KM + 3088 + 16 <= 65536, so the largest KM is 3902 (3903 would need 65 552 bytes)
   size_t sm = (size_t)(2 * (KM + 1) + 256) * sizeof(double) + 256 * sizeof(int);
-  Y3D_CHECK(sm <= 64 * 1024, "kde_depth_fusion: %d one-to-many rows do not fit LDS", KM);
+  Y3D_CHECK(sm + 16 <= 64 * 1024, "kde_depth_fusion: %d one-to-many rows do not fit LDS (at most 3902)", KM);
   hipLaunchKernelGGL(kde_fusion_kernel, dim3(K, B), dim3(256), sm, (hipStream_t)stream, predsO, predsM, out, K, KM, C, thres, iou_thres, nprop);
   Y3D_LAUNCH_CHECK();
   return Y3D_OK;
