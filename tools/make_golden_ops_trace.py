@@ -1,0 +1,399 @@
+"""Mints tests/golden/ops_call_trace.json.gz: every call the Python glue makes into the library (name + arguments) over a set of small
+cases, so that a change to `ops.py` that is meant to keep the launch sequence and every launch argument can be checked call for call.
+
+    python tools/make_golden_ops_trace.py             # needs the built library and a HIP device; writes the fixture
+    python tools/make_golden_ops_trace.py --check     # replays the cases and compares them with the fixture instead
+
+The `yolov10_3d_amd._lib._lib` singleton (what every `lib()` of the package returns) is replaced by a proxy that records a call and forwards
+it to the real library.  Recorded per argument: ints and floats as they are; a pointer (`c_void_p` in the parsed header) as 0 / 1 for
+null / non-null; a ctypes int or float array as its values; a ctypes pointer array as its length.  The pack and quantiser registries are
+replaced by empty ones for the duration of a case (their multi-tensor launches cover every weight the process has registered), and a case
+runs once unrecorded first, so that nothing in the trace depends on what the process did before.  Regenerate the fixture ONLY with a
+change that is meant to move a launch, and say so there.
+
+Cases (`CASES`): the tiny 3D model of `__graft_entry__.smoke()` (training forward + backward at 64x64, eval forward at 256x256: the
+smallest image whose stride-32 map holds the head's 50 candidates) in bf16 and f32, bf16 with each of PACK_CACHE / STEM_FUSED /
+PROJ_BN_MFMA / DW_EVAL_FUSED / PLACEMENT off, two steps around a `bump_weight_epoch()`, the eval forward of the model folded the
+reference's way; the stem on uint8 images; the 128-wide head of tests/test_hip_fp8.py under the three fp8 switches and with
+PROJ_BN_MFMA off; the 2D `v10Detect` head with a wide and a narrow projection; eval Bottlenecks with a shortcut on both residual arms.
+"""
+from __future__ import annotations
+
+import contextlib
+import copy
+import ctypes
+import gzip
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for _p in (ROOT, os.path.join(ROOT, "tests")):
+    if _p not in sys.path:
+        sys.path.insert(0, _p)
+OUT = os.path.join(ROOT, "tests", "golden", "ops_call_trace.json.gz")
+DEV = "cuda"
+
+
+# ---- the recording proxy -----------------------------------------------------------------------------------------------------------
+def _encode(v, t):
+    if t is ctypes.c_void_p:
+        if isinstance(v, ctypes.Array):
+            return ["ptrs", len(v)] if v._type_ is ctypes.c_void_p else ["vals", list(v)]
+        return 1 if v else 0
+    return float(v) if t in (ctypes.c_float, ctypes.c_double) else int(v)
+
+
+class Recorder:
+    """stands in for the `_Lib` singleton: `sink` receives [name, [encoded arguments]] per call of a function declared in y3d.h"""
+
+    def __init__(self, real, sink):
+        self.__dict__.update(_real=real, _sink=sink)
+
+    def __getattr__(self, name):
+        real, sink = self.__dict__["_real"], self.__dict__["_sink"]
+        fn = getattr(real, name)
+        proto = real.protos.get("y3d_" + name)
+        if proto is None:
+            return fn
+
+        def call(*a):
+            sink.append([name, [_encode(v, t) for v, t in zip(a, proto[1])]])
+            return fn(*a)
+
+        return call
+
+
+@contextlib.contextmanager
+def recording(sink):
+    from yolov10_3d_amd import _lib
+    _lib.lib()
+    prev = _lib._lib
+    _lib._lib = Recorder(prev, sink)
+    try:
+        yield
+    finally:
+        _lib._lib = prev
+
+
+@contextlib.contextmanager
+def fresh_registries():
+    from yolov10_3d_amd import ops
+    prev = ops.PACK_FWD, ops.PACK_DGRAD, ops.QUANT
+    ops.PACK_FWD, ops.PACK_DGRAD, ops.QUANT = ops._PackRegistry(0), ops._PackRegistry(1), ops._QuantRegistry()
+    try:
+        yield
+    finally:
+        ops.PACK_FWD, ops.PACK_DGRAD, ops.QUANT = prev
+
+
+@contextlib.contextmanager
+def flag_off(name):
+    from yolov10_3d_amd import ops
+    prev = getattr(ops, name) if name else None
+    if name:
+        setattr(ops, name, False)
+    try:
+        yield
+    finally:
+        if name:
+            setattr(ops, name, prev)
+
+
+@contextlib.contextmanager
+def compute_dtype(dt):
+    import torch
+    import yolov10_3d_amd as y3d
+    y3d.set_compute_dtype(dt)
+    try:
+        yield
+    finally:
+        y3d.set_compute_dtype(torch.bfloat16)
+
+
+# ---- the cases ---------------------------------------------------------------------------------------------------------------------
+def _tiny_model():
+    import torch
+    import yolov10_3d_amd as y3d
+    cfg = y3d.yaml_model_load("yolov10s_3D.yaml")
+    cfg.update(scales={"n": [0.33, 0.125, 1024]}, scale="n",
+               channels={k + "_c": 16 for k in ("cls", "o2d", "s2d", "o3d", "s3d", "hd", "dep", "dep_un")})
+    torch.manual_seed(0)
+    return y3d.YOLOv10_3DDetectionModel(cfg).to(DEV)
+
+
+def _tiny_batch():
+    import torch
+    g = torch.Generator().manual_seed(1)
+    b = {
+        "img": torch.rand(2, 3, 64, 64, generator=g),
+        "batch_idx": torch.tensor([0.0, 0.0, 1.0]), "cls": torch.tensor([[0.0], [2.0], [1.0]]),
+        "bboxes": torch.tensor([[0.4, 0.5, 0.3, 0.25], [0.6, 0.4, 0.2, 0.3], [0.5, 0.5, 0.35, 0.3]]),
+        "size_3d": torch.zeros(3, 3), "depth": torch.tensor([12.0, 30.0, 20.0]), "heading_bin": torch.tensor([1.0, 5.0, 9.0]),
+        "heading_res": torch.tensor([0.1, -0.1, 0.0]), "calib": torch.tensor([[32.0, 32.0, 700.0, 700.0, 0.06, -0.002]]).repeat(2, 1),
+        "mean_sizes": torch.tensor([[1.76, 0.66, 0.84], [1.53, 1.63, 3.88], [1.74, 0.60, 1.76]]),
+    }
+    b["center_2d"] = b["bboxes"][:, :2] * 64
+    b["size_2d"] = b["bboxes"][:, 2:] * 64
+    b["center_3d"] = b["center_2d"] + 1.0
+    return {k: v.to(DEV) for k, v in b.items()}
+
+
+def _eval_image():
+    import torch
+    return torch.rand(2, 3, 256, 256, generator=torch.Generator().manual_seed(2)).to(DEV)
+
+
+def _reference_fuse(model):
+    """what the reference's BaseModel.fuse() does to every Conv: a new nn.Conv2d with folded weight + bias, no `.bn`, `forward_fuse`"""
+    import torch
+    import yolov10_3d_amd as y3d
+    from yolov10_3d_amd import modules as M
+    for m in model.modules():
+        if isinstance(m, M.Conv) and hasattr(m, "bn"):
+            w, b = y3d.tasks.fuse_conv_and_bn(m.conv.weight.detach(), m.bn.weight.detach(), m.bn.bias.detach(), m.bn.running_mean, m.bn.running_var, m.bn.eps)
+            c = m.conv
+            f = torch.nn.Conv2d(c.in_channels, c.out_channels, c.kernel_size, c.stride, c.padding, groups=c.groups, bias=True).requires_grad_(False).to(w.device)
+            f.weight.copy_(w)
+            f.bias.copy_(b)
+            m.conv = f
+            delattr(m, "bn")
+            m.forward = m.forward_fuse
+    return model
+
+
+def tiny(dtype="bf16", off=None, steps=1, fuse=False):
+    import torch
+    from yolov10_3d_amd import ops
+    with compute_dtype(torch.bfloat16 if dtype == "bf16" else torch.float32), flag_off(off):
+        model, batch = _tiny_model().train(), _tiny_batch()
+        for i in range(steps):
+            if i:
+                ops.bump_weight_epoch()  # what the fused optimizer does after writing the weights: the registries refresh every pack
+                model.zero_grad(set_to_none=True)
+            loss, _ = model(batch)
+            loss.backward()
+        model.eval()
+        with torch.no_grad():
+            if fuse:
+                model = _reference_fuse(copy.deepcopy(model))
+            model(_eval_image())
+    torch.cuda.synchronize()
+
+
+def stem_u8(off=None):
+    """the stem Conv on the dataset's bytes (NCHW and channels-last), training forward + backward and eval"""
+    import torch
+    from yolov10_3d_amd import modules as M
+    torch.manual_seed(1)
+    with flag_off(off):
+        m = M.Conv(3, 16, 3, 2).to(DEV)
+        img = torch.randint(0, 256, (2, 3, 32, 48), dtype=torch.uint8, device=DEV)
+        for x in (img, img.contiguous(memory_format=torch.channels_last)):
+            m.train()(x).float().sum().backward()
+            with torch.no_grad():
+                m.eval()(x)
+    torch.cuda.synchronize()
+
+
+def head3d(quant=None, conv=False, dgrad=False, off=None, eval_too=False):
+    """the 128-wide two-level head of tests/test_hip_fp8.py: training forward + backward (and the eval forward) under the fp8 switches"""
+    import torch
+    import yolov10_3d_amd as y3d
+    from test_hip_fp8 import _head_case
+    hd, xs = _head_case(DEV)
+    y3d.set_weight_quant(quant)
+    try:
+        with flag_off(off):
+            y3d.set_fp8_conv(conv)
+            y3d.set_fp8_dgrad(dgrad)
+            m = hd.to(DEV).train()
+            xin = [x.to(DEV).requires_grad_(True) for x in xs]
+            out = m(xin)
+            sum(t.float().sum() for t in out["one2many"] + out["one2one"]).backward()
+            if eval_too:
+                with torch.no_grad():
+                    m.eval()([x.detach() for x in xin])
+    finally:
+        y3d.set_fp8_conv(False)
+        y3d.set_weight_quant(None)
+    torch.cuda.synchronize()
+
+
+def head2d():
+    """one level at 8x8, nc = 8: the 64 box-distribution outputs take HeadProjFn's wide (MFMA) arm, the 8 class outputs its narrow one"""
+    import torch
+    from yolov10_3d_amd import modules as M
+    torch.manual_seed(2)
+    hd = M.v10Detect(8, (64,))
+    hd.stride = torch.tensor([8.0])
+    hd.bias_init()
+    hd = hd.to(DEV).train()
+    x = torch.randn(2, 64, 8, 8, device=DEV).requires_grad_(True)
+    out = hd([x])
+    sum(t.float().sum() for t in out["one2many"] + out["one2one"]).backward()
+    torch.cuda.synchronize()
+
+
+def bottleneck_eval():
+    """eval Bottleneck with shortcut: 32 channels (`y3d_conv2d_fwd_affine_res_ok` says yes) and 128 (no: conv + bn_act_fwd with the residual)"""
+    import torch
+    from yolov10_3d_amd import modules as M
+    torch.manual_seed(3)
+    for c in (32, 128):
+        mod = M.Bottleneck(c, c, True, 1, (3, 3), 1.0).to(DEV).eval()
+        with torch.no_grad():
+            mod(torch.randn(2, c, 20, 20, device=DEV))
+    torch.cuda.synchronize()
+
+
+CASES = {
+    "tiny/bf16": lambda: tiny("bf16"),
+    "tiny/f32": lambda: tiny("f32"),
+    "tiny/bf16/PACK_CACHE_off": lambda: tiny(off="PACK_CACHE"),
+    "tiny/bf16/STEM_FUSED_off": lambda: tiny(off="STEM_FUSED"),
+    "tiny/bf16/PROJ_BN_MFMA_off": lambda: tiny(off="PROJ_BN_MFMA"),
+    "tiny/bf16/DW_EVAL_FUSED_off": lambda: tiny(off="DW_EVAL_FUSED"),
+    "tiny/bf16/PLACEMENT_off": lambda: tiny(off="PLACEMENT"),
+    "tiny/bf16/two_steps": lambda: tiny(steps=2),
+    "tiny/bf16/fused_eval": lambda: tiny(steps=0, fuse=True),
+    "stem/u8": stem_u8,
+    "stem/u8/STEM_FUSED_off": lambda: stem_u8("STEM_FUSED"),
+    "fp8/weights": lambda: head3d("fp8"),
+    "fp8/conv": lambda: head3d("fp8", conv=True, eval_too=True),  # eval: the fp8 kernel's affine epilogue, the matrix-core proj_slices_eval
+    "fp8/dgrad": lambda: head3d("fp8", conv=True, dgrad=True),
+    "head3d/PROJ_BN_MFMA_off": lambda: head3d(off="PROJ_BN_MFMA", eval_too=True),  # (the tiny model's 16-wide head never takes the matrix-core forms)
+    "head2d": head2d,
+    "bottleneck_eval": bottleneck_eval,
+}
+
+
+def run_case(name):
+    """-> the calls of one case, [[name, [arguments]], ...]"""
+    import torch
+    from yolov10_3d_amd import ops
+    torch.cuda.synchronize()
+    try:
+        with fresh_registries():
+            CASES[name]()  # unrecorded: whatever the process does once (module loads, tables, caches) happens here
+        calls = []
+        with fresh_registries(), recording(calls):
+            CASES[name]()
+    finally:
+        ops.reset_placement()
+    return json.loads(json.dumps(calls))
+
+
+# ---- which arms of the conv + BatchNorm + activation glue a trace reaches --------------------------------------------------------
+def _has(name, cond=lambda a: True):
+    return lambda calls: any(c[0] == name and cond(c[1]) for c in calls)
+
+
+ARMS = {
+    "_stem_forward: fused eval (stem_conv_eval)": _has("stem_conv_eval"),
+    "_stem_forward: fused training (stem_conv_train)": _has("stem_conv_train"),
+    "_stem_forward: im2col of a float image + dense conv": _has("stem_im2col"),
+    "_stem_forward: im2col of a uint8 image + dense conv": _has("stem_im2col_u8"),
+    "_dw_forward: eval, BatchNorm + SiLU in the epilogue": _has("dwconv2d_fwd_affine", lambda a: a[13] == 0),
+    "_dw_forward: eval, epilogue with a residual": _has("dwconv2d_fwd_affine", lambda a: a[13] != 0),
+    "_dw_forward: eval, conv + tail (DW_EVAL_FUSED off)": _has("dwconv2d_fwd", lambda a: a[-2] == 0),
+    "_dw_forward: training": _has("dwconv2d_fwd", lambda a: a[-2] == 1),
+    "_dw_packed: packed on the spot": _has("dw_pack_weight"),
+    "_dense_forward: fp8 eval (affine epilogue)": _has("conv3x3_fp8_fwd", lambda a: a[12] == 0 and a[13] == 1),
+    "_dense_forward: fp8 training": _has("conv3x3_fp8_fwd", lambda a: a[12] == 1),
+    "_dense_forward: eval, affine epilogue": _has("conv2d_fwd_affine"),
+    "_dense_forward: eval, affine epilogue with the residual": _has("conv2d_fwd_affine_res"),
+    "_dense_forward: eval, conv + tail with the residual": _has("conv2d_fwd", lambda a: a[-2] == 0 and a[10] == 0),
+    "_dense_forward: training": _has("conv2d_fwd", lambda a: a[-2] == 1),
+    "forward pack on the spot": _has("pack_weight_fwd"),
+    "registry refresh-all": _has("mt_pack_weights"),
+    "_bn_act_tail: training statistics": _has("bn_finalize"),
+    "_bn_act_tail: apply + fp8 copy": _has("bn_act_fwd_q"),
+    "_bn_act_tail: apply": _has("bn_act_fwd", lambda a: a[6] == 0),
+    "_bn_act_tail: apply, res_mode 1": _has("bn_act_fwd", lambda a: a[6] == 1),
+    "_bn_act_tail: apply, res_mode 2": _has("bn_act_fwd", lambda a: a[6] == 2),
+    "_conv_backward: depth-wise data gradient": _has("dwconv2d_bwd_data"),
+    "_conv_backward: depth-wise weight gradient": _has("dwconv2d_bwd_weight"),
+    "_conv_backward: fp8 data gradient": _has("conv3x3_fp8_dgrad"),
+    "_conv_backward: data-gradient pack on the spot": _has("pack_weight_dgrad"),
+    "_conv_backward: data gradient": _has("conv2d_bwd_data"),
+    "_conv_backward: weight gradient": _has("conv2d_bwd_weight"),
+    "HeadProjFn: narrow arm": _has("proj_fwd"),
+    "HeadProjFn: narrow arm, backward": _has("proj_bwd_weight"),
+    "HeadProjFn: wide arm, backward (bias column sums)": _has("colsum_partials"),
+    "HeadProjSlicesFn / FusedConvBNProjFn: VALU forms": _has("proj_group_fwd_bn"),
+    "FusedConvBNProjFn: matrix-core forms": _has("proj_group_bn_bwd"),
+    "proj_slices_eval: matrix-core form": _has("proj_group_fwd_bn_mfma", lambda a: a[10] == 0),
+    "conv_bias_act_eval (folded model)": _has("bn_eval_scale", lambda a: a[5] == 0.0),
+}
+
+
+def unreached(traces):
+    calls = [c for t in traces.values() for c in t]
+    return [arm for arm, hit in ARMS.items() if not hit(calls)]
+
+
+# ---- the fixture -------------------------------------------------------------------------------------------------------------------
+def pack(traces):
+    """{case: calls} -> the stored form: every distinct call once, the cases as index lists"""
+    table, index = [], {}
+    cases = []
+    for name, calls in traces.items():
+        seq = []
+        for c in calls:
+            k = json.dumps(c)
+            if k not in index:
+                index[k] = len(table)
+                table.append(c)
+            seq.append(index[k])
+        cases.append([name, seq])
+    return {"calls": table, "cases": cases}
+
+
+def unpack(stored):
+    return {name: [stored["calls"][i] for i in seq] for name, seq in stored["cases"]}
+
+
+def load(path=OUT):
+    with gzip.open(path, "rt") as f:
+        return unpack(json.load(f))
+
+
+def first_difference(got, want, context=10):
+    """None when the two call lists are equal, else a report: the first differing call with `context` calls around it"""
+    if got == want:
+        return None
+    i = next((j for j, (a, b) in enumerate(zip(got, want)) if a != b), min(len(got), len(want)))
+    lines = [f"{len(got)} calls, {len(want)} recorded; first difference at call {i}"]
+    for j in range(max(0, i - context), min(max(len(got), len(want)), i + context + 1)):
+        a = got[j] if j < len(got) else None
+        b = want[j] if j < len(want) else None
+        lines.append(f"{'>>' if j == i else '  '} {j}: {a}" + ("" if a == b else f"\n      recorded: {b}"))
+    return "\n".join(lines)
+
+
+def main():
+    traces = {name: run_case(name) for name in CASES}
+    miss = unreached(traces)
+    if "--check" in sys.argv:
+        want = load()
+        bad = [name for name in CASES if traces[name] != want.get(name)]
+        for name in bad:
+            print(f"{name}:\n{first_difference(traces[name], want.get(name, []))}")
+        print(f"{len(CASES) - len(bad)} of {len(CASES)} cases equal the fixture")
+        sys.exit(1 if bad else 0)
+    if miss and "--allow-unreached" not in sys.argv:
+        sys.exit(f"arms not reached by any case: {miss}")
+    print(f"arms not reached: {miss}")
+    out = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else OUT
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    with open(out, "wb") as raw, gzip.GzipFile(filename="", fileobj=raw, mode="wb", mtime=0) as f:
+        f.write(json.dumps(pack(traces), separators=(",", ":")).encode())
+    names = sorted({c[0] for t in traces.values() for c in t})
+    print(f"{out}: {len(CASES)} cases, {sum(len(t) for t in traces.values())} calls of {len(names)} functions, {os.path.getsize(out)} bytes")
+    for name, t in traces.items():
+        print(f"  {name}: {len(t)} calls")
+
+
+if __name__ == "__main__":
+    main()

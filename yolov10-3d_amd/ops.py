@@ -7,6 +7,7 @@ dtype (bf16 by default, fp32 for the parity mode).
 """
 from __future__ import annotations
 
+import ctypes
 import os
 from collections import namedtuple
 
@@ -439,6 +440,29 @@ def _dw_packed(w32, C, k, dtype, ver):
     return wp
 
 
+def _fwd_packed(w32, Cout, Cin_g, Cg_pad, k, dtype, ver=None, registry=False):
+    """the K-contiguous compute-dtype rows of a dense / grouped conv weight (Cin_g channels per group, rows padded to Cg_pad): from the
+    forward pack registry when the caller asks for it (`registry`: the weights of a training step), or packed on the spot"""
+    dt = code(dtype)
+    if registry and PACK_CACHE:
+        return PACK_FWD.lookup(w32, w32.data_ptr(), (Cout, Cin_g, Cg_pad, k * k, k * k * Cg_pad, dt), dtype, ver)
+    wp = torch.empty(Cout * k * k * Cg_pad, dtype=dtype, device=w32.device)
+    lib().pack_weight_fwd(dt, w32.data_ptr(), wp.data_ptr(), Cout, Cin_g, Cg_pad, k, k, stream())
+    return wp
+
+
+def _dgrad_packed(w32, src, co, Cin_g, g, k, dtype, ver=None, registry=False):
+    """the data-gradient layout of the `co` output channels of w32 that start at address `src`: from the data-gradient pack registry
+    when the caller asks for it, or packed on the spot"""
+    dt = code(dtype)
+    kp = lib().conv_kpad(dt, k * k * (co // g))
+    if registry and PACK_CACHE:
+        return PACK_DGRAD.lookup(w32, src, (g, co // g, Cin_g, k * k, kp, dt), dtype, ver)
+    wpd = torch.empty(Cin_g * g * kp, dtype=dtype, device=w32.device)
+    lib().pack_weight_dgrad(dt, src, wpd.data_ptr(), co, Cin_g, g, k, k, stream())
+    return wpd
+
+
 WEIGHT_QUANT = None  # None | "fp8": conv (+BatchNorm) weights as e4m3fn codes with per-output-channel power-of-two scales
 
 
@@ -570,7 +594,7 @@ def conv_bn_act_eval(x, w, gamma, beta, rm, rv, k, s, p, g, act, eps, cache=None
     """eval-mode act(bn(conv(x))) on explicit (possibly stacked / sliced) tensors; no autograd.  `cache`: a dict owned by the
     caller that keeps the packed weights + folded BatchNorm scale/shift until a parameter changes; `ver`: version token of the
     tensors behind a stacked view (StackedConvs.ver)"""
-    z, _, _ = _cba_forward(x, w, gamma, beta, rm, rv, k, s, p, g, act, None, 0, False, eps, 0.0, cache, ver=ver)
+    z, _, _ = _cba_forward(x, ConvCall(w32=w, g32=gamma, b32=beta, rm=rm, rv=rv, k=k, s=s, p=p, g=g, act=act, eps=eps, cache=cache, ver=ver))
     return z
 
 
@@ -591,7 +615,8 @@ def conv_bias_act_eval(x, w, bias, k, s, p, g, act, res, res_mode, cache):
     _require_gpu(x)
     ones, zeros = _identity_bn(w.shape[0], w.device)
     with torch.no_grad():
-        z, _, _ = _cba_forward(x, _w32(w), ones, bias.detach().float(), zeros, ones, k, s, p, g, act, res, res_mode, False, 0.0, 0.0, cache)
+        z, _, _ = _cba_forward(x, ConvCall(w32=_w32(w), g32=ones, b32=bias.detach().float(), rm=zeros, rv=ones, k=k, s=s, p=p, g=g, act=act,
+                                           res=res, res_mode=res_mode, cache=cache))
     return z
 
 
@@ -602,10 +627,11 @@ def _cache_put(cache, key, value):
     cache[key] = value
 
 
-def _eval_consts(cache, kind, w32, g32, b32, rm, rv, ver, dtype, k, g, Cin_g, Cg_pad, Cout, eps):
-    """eval-mode constants of one conv, cached in `cache` (a dict owned by the module / stack) until a parameter or buffer changes:
+def _eval_consts(call, kind, dtype, Cin_g, Cg_pad, Cout):
+    """eval-mode constants of one conv, cached in `call.cache` (a dict owned by the module / stack) until a parameter or buffer changes:
     the packed weights (kind "dense": K-contiguous compute-dtype rows; "dw": tap-major fp32 rows) and the folded BatchNorm
     (scale, shift) pair.  A steady-state eval forward launches neither packing nor bn_eval_scale kernels."""
+    cache, w32, g32, b32, rm, rv, ver, k, g, eps = call.cache, call.w32, call.g32, call.b32, call.rm, call.rv, call.ver, call.k, call.g, call.eps
     L, st, dev = lib(), stream(), w32.device
     vkey = ver[1] if ver is not None else (w32._version, g32._version, b32._version, rm._version, rv._version)
     key = (kind, PARAM_EPOCH, w32.data_ptr(), g32.data_ptr(), rm.data_ptr(), vkey, dtype, k, g, Cg_pad, Cout, float(eps))
@@ -615,8 +641,7 @@ def _eval_consts(cache, kind, w32, g32, b32, rm, rv, ver, dtype, k, g, Cin_g, Cg
             wp = _f32(k * k * Cout, dev)
             L.dw_pack_weight(w32.data_ptr(), wp.data_ptr(), Cout, k, k, st)
         else:
-            wp = torch.empty(Cout * k * k * Cg_pad, dtype=dtype, device=dev)
-            L.pack_weight_fwd(code(dtype), w32.data_ptr(), wp.data_ptr(), Cout, Cin_g, Cg_pad, k, k, st)
+            wp = _fwd_packed(w32, Cout, Cin_g, Cg_pad, k, dtype)
         ss = _f32(2 * Cout, dev).view(2, Cout)
         L.bn_eval_scale(Cout, g32.data_ptr(), b32.data_ptr(), rm.data_ptr(), rv.data_ptr(), eps, ss[0].data_ptr(), ss[1].data_ptr(), st)
         hit = (wp, ss, w32)  # w32 kept alive: its address is part of the key
@@ -639,23 +664,42 @@ def _timed(key, launch):
 ConvPlan = namedtuple("ConvPlan", "B Cin Cin_k H W Cout Ho Wo k s p g dw res_mode training dtype act wver fp8_entry stem", defaults=(False,))
 
 
-def _cba_forward(x, w32, g32, b32, rm, rv, k, s, p, g, act, res, res_mode, training, eps, momentum, cache=None, bn_apply=True, ver=None):
-    """conv -> BN statistics -> BN apply + SiLU (+res).  Returns (z, plan, saved) with everything the backward needs.
-    ver = (weights token, all-tensors token) of a stacked view (StackedConvs), None for tensors that carry their own counters."""
+# What one conv + BatchNorm + activation forward is asked to do: fp32 weight and BatchNorm tensors, geometry, activation, residual
+# (res_mode 1: act(bn(conv)) + res, 2: act(bn(conv) + res)) and BatchNorm mode.  cache: the dict of eval constants owned by the module /
+# stack (None: nothing is kept); bn_apply False: the consumer applies BatchNorm + activation itself and gets the pre-BatchNorm tensor;
+# ver = (weights token, all-tensors token) of a stacked view (StackedConvs) or an fp8 shadow, None for tensors with counters of their own.
+ConvCall = namedtuple("ConvCall", "w32 g32 b32 rm rv k s p g act res res_mode training eps momentum cache bn_apply ver",
+                      defaults=(None, 0, False, 0.0, 0.0, None, True, None))
+
+
+def _module_call(m, **fields):
+    """the ConvCall of Conv module `m` (kernel, stride, padding, activation, BatchNorm mode and constants); `fields`: the tensors, the
+    groups and whatever else the caller sets"""
+    return ConvCall(k=m.k, s=m.s, p=m.p, act=m.has_act, training=m.training, eps=m.eps, momentum=m.momentum, **fields)
+
+
+def _wver(call):
+    return call.ver[0] if call.ver is not None else None
+
+
+def _cba_forward(x, call):
+    """conv -> BN statistics -> BN apply + SiLU (+res).  Returns (z, plan, saved) with everything the backward needs."""
     _require_gpu(x)
     dtype = _COMPUTE_DTYPE
     B, Cin, H, W = x.shape
+    w32, k, s, p, g = call.w32, call.k, call.s, call.p, call.g
     dw = g > 1 and g == Cin and g == w32.shape[0]
     qent = None
     if WEIGHT_QUANT and not dw:
         # fp8w mode: the kernels pack and multiply the fp8-valued shadow of the weight; the master keeps receiving the gradient
-        w32, qtok = QUANT.lookup(w32, ver[0] if ver is not None else None)
+        w32, qtok = QUANT.lookup(w32, _wver(call))
         qent = QUANT.last
-        ver = ((qtok,), (qtok,) + (ver[1] if ver is not None else (g32._version, b32._version, rm._version, rv._version)))
+        rest = call.ver[1] if call.ver is not None else (call.g32._version, call.b32._version, call.rm._version, call.rv._version)
+        call = call._replace(w32=w32, ver=((qtok,), (qtok,) + rest))
     Cout, Cg_w, kh, kw = w32.shape
     assert kh == k and kw == k and Cin // g == Cg_w, "Conv: weight shape does not match input"
     if Cin == 3 and k == 3 and s == 2 and p == 1 and g == 1 and not x.requires_grad:
-        return _stem_forward(x, w32, g32, b32, rm, rv, act, res, res_mode, training, eps, momentum, cache, ver)
+        return _stem_forward(x, call)
     # ---- input: NHWC compute dtype; a channel count that is no whole number of 16-byte chunks is padded while converting from NCHW fp32
     c = ce(dtype)
     if Cin % c != 0:
@@ -667,8 +711,8 @@ def _cba_forward(x, w32, g32, b32, rm, rv, k, s, p, g, act, res, res_mode, train
     else:
         xin = to_nhwc(x, dtype)
     if dw:
-        return _dw_forward(xin, w32, g32, b32, rm, rv, k, s, p, act, res, res_mode, training, eps, momentum, cache, bn_apply, ver)
-    return _dense_forward(xin, w32, g32, b32, rm, rv, Cin, k, s, p, g, act, res, res_mode, training, eps, momentum, cache, bn_apply, ver, qent, True)
+        return _dw_forward(xin, call)
+    return _dense_forward(xin, call, Cin, qent, True)
 
 
 def _stem_image(x):
@@ -679,26 +723,27 @@ def _stem_image(x):
     return x.float().contiguous(), 0
 
 
-def _stem_forward(x, w32, g32, b32, rm, rv, act, res, res_mode, training, eps, momentum, cache, ver):
+def _stem_forward(x, call):
     """the stem (3 -> Cout, 3x3, stride 2) as a dense 1x1 conv with K = 32 over the im2col rows of the image (27 window values + 5 zeros
     per output pixel); as a 9-tap conv over an 8-channel-padded image the MFMA tiles were 86 % padding.  dW is mapped back in _conv_backward."""
     L, st, dtype, dev = lib(), stream(), _COMPUTE_DTYPE, x.device
     dt = code(dtype)
+    w32, act, res_mode, training, cache = call.w32, call.act, call.res_mode, call.training, call.cache
     B, _, H, W = x.shape
     Cout = w32.shape[0]
     Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
-    wkey = ("stemcol", PARAM_EPOCH, w32.data_ptr(), ver[0] if ver is not None else w32._version)
+    wkey = ("stemcol", PARAM_EPOCH, w32.data_ptr(), call.ver[0] if call.ver is not None else w32._version)
     wcol = cache.get(wkey) if (cache is not None and not training) else None
     if wcol is None:
         wcol = torch.zeros(Cout, 32, dtype=torch.float32, device=dev)
         wcol[:, :27] = w32.detach().permute(0, 2, 3, 1).reshape(Cout, 27)  # column (r*3+q)*3+ci
         if cache is not None and not training:  # eval: the im2col form of the stem weight is a constant of the forward
             _cache_put(cache, wkey, wcol)
-    w1x1 = wcol.view(Cout, 32, 1, 1)
+    call = call._replace(w32=wcol.view(Cout, 32, 1, 1), k=1, s=1, p=0, g=1, bn_apply=True)  # the 1x1 form over 32 im2col channels
     fused = dtype == torch.bfloat16 and Cout % 16 == 0 and 16 <= Cout <= 80 and STEM_FUSED and x.dtype in (torch.uint8, torch.float32)
     if fused and not training and not res_mode:
         # eval: gather + MFMA + folded BatchNorm + SiLU in one pass over the image (csrc/stem_fused.hip); no column tensor
-        _, ss = _eval_consts(cache, "dense", w1x1, g32, b32, rm, rv, ver, dtype, 1, 1, 32, 32, Cout, eps)
+        _, ss = _eval_consts(call, "dense", dtype, 32, 32, Cout)
         xs, hwc = _stem_image(x)
         mode = 1 + hwc if xs.dtype == torch.uint8 else 0
         ye = out_tensor(B, Cout, Ho, Wo, dtype, dev)
@@ -708,6 +753,8 @@ def _stem_forward(x, w32, g32, b32, rm, rv, act, res, res_mode, training, eps, m
         return ye, None, None
     xcol = nhwc_empty(B, 32, Ho, Wo, dtype, dev)
     xs, hwc = _stem_image(x)
+    # wcol is built from the already quantised stem weight and repacked per call: no quantiser entry, no version token, no pack registry
+    call = call._replace(ver=None)
     if fused and training:
         # training: the same one-pass kernel writes the raw conv output, the BatchNorm partials and - its own B operand - the column
         # tensor the weight gradient reads; the two-step form wrote the column tensor and read it back (im2col 167 us + conv 146 us)
@@ -717,35 +764,33 @@ def _stem_forward(x, w32, g32, b32, rm, rv, act, res, res_mode, training, eps, m
         part = _f32(rows * Cout * 2, dev)
         _timed(("conv_fwd", dt, B, H, W, 3, Cout, 3, 2, 1),
                lambda: L.stem_conv_train(xs.data_ptr(), mode, wcol.data_ptr(), ypre.data_ptr(), ypre.stride(3), xcol.data_ptr(), part.data_ptr(), B, H, W, Cout, st))
-        z, plan, saved = _bn_act_tail(xcol, w1x1, ypre, part, rows, None, g32, b32, rm, rv, 32, 1, 1, 0, 1, act, res, res_mode, training, eps, momentum,
-                                      True, None, None)
+        z, plan, saved = _bn_act_tail(xcol, ypre, part, rows, None, call, 32, None, None)
     else:
         if xs.dtype == torch.uint8:
             L.stem_im2col_u8(dt, xs.data_ptr(), hwc, xcol.data_ptr(), B, H, W, Ho, Wo, st)
         else:
             L.stem_im2col(dt, xs.data_ptr(), xcol.data_ptr(), B, H, W, Ho, Wo, st)
-        # wcol is built from the already quantised stem weight and repacked per call: no quantiser entry, no version token, no pack registry
-        z, plan, saved = _dense_forward(xcol, w1x1, g32, b32, rm, rv, 32, 1, 1, 0, 1, act, res, res_mode, training, eps, momentum, cache, True, None,
-                                        None, False)
+        z, plan, saved = _dense_forward(xcol, call, 32, None, False)
     return z, (plan._replace(stem=True) if plan is not None else None), saved
 
 
-def _dw_forward(xin, w32, g32, b32, rm, rv, k, s, p, act, res, res_mode, training, eps, momentum, cache, bn_apply, ver):
+def _dw_forward(xin, call):
     """depth-wise conv (one filter per channel): the eval form with folded BatchNorm + SiLU (+res) in its epilogue, or dwconv2d_fwd + the tail"""
     L, st, dtype, dev = lib(), stream(), xin.dtype, xin.device
+    k, s, p, act, res, res_mode, training = call.k, call.s, call.p, call.act, call.res, call.res_mode, call.training
     dt = code(dtype)
     B, C, H, W = xin.shape
     Ho, Wo = (H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1
     sb, sh, sw = s3(xin)
-    fused = not training and bn_apply and DW_EVAL_FUSED
+    fused = not training and call.bn_apply and DW_EVAL_FUSED
     y = None if fused else nhwc_empty(B, C, Ho, Wo, dtype, dev)  # pre-BatchNorm tensor
     nblk = L.dw_blocks(B * Ho * Wo)
     part = ss_eval = None
     if training:
         part = _f32(nblk * C * 2, dev)
-        wp = _dw_packed(w32, C, k, dtype, ver[0] if ver is not None else None)
+        wp = _dw_packed(call.w32, C, k, dtype, _wver(call))
     else:
-        wp, ss_eval = _eval_consts(cache, "dw", w32, g32, b32, rm, rv, ver, dtype, k, C, 1, 1, C, eps)
+        wp, ss_eval = _eval_consts(call, "dw", dtype, 1, 1, C)
         if fused:
             # eval: folded BatchNorm + SiLU (+ the RepVGGDW / shortcut residual) in the depth-wise kernel's epilogue - one launch, no
             # pre-BN tensor (12 depth-wise layers of S-3D: 12 bn_act_fwd launches and their read + write less per forward)
@@ -759,20 +804,20 @@ def _dw_forward(xin, w32, g32, b32, rm, rv, k, s, p, act, res, res_mode, trainin
             return ze, None, None
     L.dwconv2d_fwd(dt, xin.data_ptr(), sb, sh, sw, B, H, W, C, wp.data_ptr(), y.data_ptr(), C, Ho, Wo, k, k, s, p,
                    part.data_ptr() if training else None, st)
-    return _bn_act_tail(xin, w32, y, part, nblk, ss_eval, g32, b32, rm, rv, C, k, s, p, C, act, res, res_mode, training, eps, momentum, bn_apply,
-                        ver[0] if ver is not None else None, None)
+    return _bn_act_tail(xin, y, part, nblk, ss_eval, call, C, _wver(call), None)
 
 
-def _dense_forward(xin, w32, g32, b32, rm, rv, Cin, k, s, p, g, act, res, res_mode, training, eps, momentum, cache, bn_apply, ver, qent, pack_cache):
-    """dense / grouped conv over the NHWC input `xin` (Cin: its channels before padding); qent: the quantiser entry of w32 (fp8w mode) or
-    None; pack_cache: training weight packs go through the registry"""
+def _dense_forward(xin, call, Cin, qent, pack_cache):
+    """dense / grouped conv over the NHWC input `xin` (Cin: its channels before padding); qent: the quantiser entry of call.w32 (fp8w
+    mode) or None; pack_cache: training weight packs go through the registry"""
     L, st, dtype, dev = lib(), stream(), xin.dtype, xin.device
+    w32, k, s, p, g, act, res, res_mode, training = call.w32, call.k, call.s, call.p, call.g, call.act, call.res, call.res_mode, call.training
     dt = code(dtype)
     B, Cin_k, H, W = xin.shape
     Cout = w32.shape[0]
     Ho, Wo = (H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1
     sb, sh, sw = s3(xin)
-    wver = ver[0] if ver is not None else None
+    wver = _wver(call)
     y = nhwc_empty(B, Cout, Ho, Wo, dtype, dev) if (training or res_mode) else None  # pre-BatchNorm tensor (the eval fast paths have none)
     # fp8 MFMA forward (set_fp8_conv): e4m3 codes of the weight x the MX-quantised activation; everything after the conv - BatchNorm
     # statistics from the partial rows, the apply pass, the bf16 backward over (xin, w_eff) - is the bf16 path's
@@ -783,7 +828,7 @@ def _dense_forward(xin, w32, g32, b32, rm, rv, Cin, k, s, p, g, act, res, res_mo
     Cg_pad = Cin_k // g
     wp = ss_eval = None
     if not training:
-        wp, ss_eval = _eval_consts(cache, "dense", w32, g32, b32, rm, rv, ver, dtype, k, g, Cin // g, Cg_pad, Cout, eps)
+        wp, ss_eval = _eval_consts(call, "dense", dtype, Cin // g, Cg_pad, Cout)
     if f8:
         xq, xs = fp8_input(xin)
         wq, ws = fp8_weight(qent, Cin // g)
@@ -814,34 +859,30 @@ def _dense_forward(xin, w32, g32, b32, rm, rv, Cin, k, s, p, g, act, res, res_mo
         return ye, None, None
     else:
         # training, or eval with a residual the epilogue kernel does not serve: conv (eval: the cached packed weights) + the tail's pass
-        if training and pack_cache and PACK_CACHE:
-            wp = PACK_FWD.lookup(w32, w32.data_ptr(), (Cout, Cin // g, Cg_pad, k * k, k * k * Cg_pad, dt), dtype, wver)
-        elif training:
-            wp = torch.empty(Cout * k * k * Cg_pad, dtype=dtype, device=dev)
-            L.pack_weight_fwd(dt, w32.data_ptr(), wp.data_ptr(), Cout, Cin // g, Cg_pad, k, k, st)
+        if training:
+            wp = _fwd_packed(w32, Cout, Cin // g, Cg_pad, k, dtype, wver, registry=pack_cache)
         _timed(("conv_fwd", dt, B, H, W, Cin_k, Cout, k, s, g),
                lambda: L.conv2d_fwd(dt, xin.data_ptr(), sb, sh, sw, B, H, W, Cin_k, wp.data_ptr(), None, y.data_ptr(), Cout, Ho, Wo, Cout, g,
                                     k, k, s, p, part.data_ptr() if training else None, st))
-    return _bn_act_tail(xin, w32, y, part, nblk, ss_eval, g32, b32, rm, rv, Cin, k, s, p, g, act, res, res_mode, training, eps, momentum, bn_apply,
-                        wver, qent if f8 else None)
+    return _bn_act_tail(xin, y, part, nblk, ss_eval, call, Cin, wver, qent if f8 else None)
 
 
-def _bn_act_tail(xin, w32, y, part, nblk, ss_eval, g32, b32, rm, rv, Cin, k, s, p, g, act, res, res_mode, training, eps, momentum, bn_apply, wver,
-                 fp8_entry):
+def _bn_act_tail(xin, y, part, nblk, ss_eval, call, Cin, wver, fp8_entry):
     """BatchNorm + activation (+res) over the pre-BatchNorm tensor y of a conv that has run.  Training: statistics from the conv's `nblk`
     partial rows `part`; eval: the folded (scale, shift) pair `ss_eval`.  -> (z, plan, saved)"""
     L, st, dtype, dev = lib(), stream(), y.dtype, y.device
     dt = code(dtype)
+    w32, g, act, res_mode, training, bn_apply = call.w32, call.g, call.act, call.res_mode, call.training, call.bn_apply
     B, Cin_k, H, W = xin.shape
     _, Cout, Ho, Wo = y.shape
     M = B * Ho * Wo
-    plan = ConvPlan(B, Cin, Cin_k, H, W, Cout, Ho, Wo, k, s, p, g, g > 1 and g == Cin and g == Cout, res_mode, training, dtype, int(act), wver,
-                    fp8_entry)
+    plan = ConvPlan(B, Cin, Cin_k, H, W, Cout, Ho, Wo, call.k, call.s, call.p, g, g > 1 and g == Cin and g == Cout, res_mode, training, dtype,
+                    int(act), wver, fp8_entry)
     if training:
         stats = _f32(6 * Cout, dev).view(6, Cout)  # mean, invstd, scale, shift, mean_g, mean_gx
         bump_param_epoch()  # bn_finalize updates the running statistics in place
-        L.bn_finalize(part.data_ptr(), nblk, Cout, M, g32.data_ptr(), b32.data_ptr(), eps, momentum, rm.data_ptr(), rv.data_ptr(),
-                      stats[0].data_ptr(), stats[1].data_ptr(), stats[2].data_ptr(), stats[3].data_ptr(), st)
+        L.bn_finalize(part.data_ptr(), nblk, Cout, M, call.g32.data_ptr(), call.b32.data_ptr(), call.eps, call.momentum, call.rm.data_ptr(),
+                      call.rv.data_ptr(), stats[0].data_ptr(), stats[1].data_ptr(), stats[2].data_ptr(), stats[3].data_ptr(), st)
     elif not bn_apply:  # eval: the fused consumer reads the cached (scale, shift) pair as rows 2 / 3 of a statistics tensor
         stats = torch.zeros(6, Cout, dtype=torch.float32, device=dev)
         stats[2:4].copy_(ss_eval)
@@ -852,7 +893,7 @@ def _bn_act_tail(xin, w32, y, part, nblk, ss_eval, g32, b32, rm, rv, Cin, k, s, 
     z = out_tensor(B, Cout, Ho, Wo, dtype, dev)
     rr = None
     if res_mode:
-        rr = to_nhwc(res, dtype, dense=True)
+        rr = to_nhwc(call.res, dtype, dense=True)
         assert rr.shape == z.shape, "residual shape mismatch"
     sc_t, sh_t = (stats[2], stats[3]) if training else (ss_eval[0], ss_eval[1])
     if _FP8_WANT and dtype == torch.bfloat16 and not res_mode and Cout % 64 == 0 and not plan.dw:
@@ -965,13 +1006,7 @@ def _conv_backward(plan, saved, dy, dgb, dres, need_dx, dx_range, dx_out=None):
             lo, hi = dx_range if dx_range is not None else (0, Cout)
             assert g == 1 or (lo, hi) == (0, Cout)
             co = hi - lo
-            kp = L.conv_kpad(dt, k * k * (co // g))
-            src = w32.data_ptr() + lo * (Cin // g) * k * k * 4
-            if plan.stem or not PACK_CACHE:
-                wpd = torch.empty(Cin * kp, dtype=dtype, device=dev)
-                L.pack_weight_dgrad(dt, src, wpd.data_ptr(), co, Cin // g, g, k, k, st)
-            else:
-                wpd = PACK_DGRAD.lookup(w32, src, (g, co // g, Cin // g, k * k, kp, dt), dtype, plan.wver)
+            wpd = _dgrad_packed(w32, w32.data_ptr() + lo * (Cin // g) * k * k * 4, co, Cin // g, g, k, dtype, plan.wver, registry=not plan.stem)
             dx = dx_out if dx_out is not None else nhwc_empty(B, Cin, H, W, dtype, dev)  # dx_out: a slice of a shared gradient buffer (grad_slot)
             dsb, dsh, dsw = s3(dy)
             _timed(("conv_dgrad", dt, B, H, W, Cin, co, k, s, g),
@@ -1003,9 +1038,9 @@ class ConvBNActFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, gamma, beta, res, res_mode, m):
-        z, cfg, saved = _cba_forward(x, _w32(weight), gamma.detach().float(), beta.detach().float(), m.bn.running_mean, m.bn.running_var,
-                                     m.k, m.s, m.p, m.g, m.has_act, res, res_mode, m.training, m.eps, m.momentum,
-                                     m.__dict__.setdefault("_eval_cache", {}))
+        z, cfg, saved = _cba_forward(x, _module_call(m, w32=_w32(weight), g32=gamma.detach().float(), b32=beta.detach().float(), rm=m.bn.running_mean,
+                                                     rv=m.bn.running_var, g=m.g, res=res, res_mode=res_mode,
+                                                     cache=m.__dict__.setdefault("_eval_cache", {})))
         if m.training:
             m._nbt_pending += 1
         ctx.cfg = cfg
@@ -1079,7 +1114,7 @@ class FusedConvBNActFn(torch.autograd.Function):
     def forward(ctx, x, stack, groups, dx_range, *params):
         w, gm, bt, rm, rv = stack.tensors()
         m = stack.convs[0]
-        z, cfg, saved = _cba_forward(x, w, gm, bt, rm, rv, m.k, m.s, m.p, groups, m.has_act, None, 0, m.training, m.eps, m.momentum, ver=stack.ver)
+        z, cfg, saved = _cba_forward(x, _module_call(m, w32=w, g32=gm, b32=bt, rm=rm, rv=rv, g=groups, ver=stack.ver))
         if m.training:
             for c in stack.convs:
                 c._nbt_pending += 1
@@ -1093,13 +1128,7 @@ class FusedConvBNActFn(torch.autograd.Function):
     def backward(ctx, dz):
         dx_out = grad_slot_tensor(ctx.gslot) if (ctx.gslot is not None and ctx.needs_input_grad[0]) else None
         dx, dW, dg, db, _ = _cba_backward(ctx.cfg, ctx.saved_tensors, dz, ctx.needs_input_grad[0], False, ctx.dx_range, dx_out=dx_out)
-        dWs, dgs, dbs, off = [], [], [], 0
-        for co in ctx.couts:
-            dWs.append(dW[off:off + co])
-            dgs.append(dg[off:off + co])
-            dbs.append(db[off:off + co])
-            off += co
-        return (dx, None, None, None, *dWs, *dgs, *dbs)
+        return (dx, None, None, None, *dW.split(ctx.couts), *dg.split(ctx.couts), *db.split(ctx.couts))  # per-branch row slices of the stack
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -1242,8 +1271,7 @@ class HeadProjFn(torch.autograd.Function):
         L = lib()
         xs, ws, bs = args[:n], args[n:2 * n], args[2 * n:3 * n]
         dtype = _COMPUTE_DTYPE
-        dt = code(dtype)
-        st = stream()
+        dt, st = code(dtype), stream()
         B, _, H, W = xs[0].shape
         P = B * H * W
         couts = [w.shape[0] for w in ws]
@@ -1253,8 +1281,7 @@ class HeadProjFn(torch.autograd.Function):
         xs = [to_nhwc(x, dtype, dense=True) for x in xs]
         w32 = [w.detach().float().contiguous() for w in ws]
         b32 = [b.detach().float().contiguous() for b in bs]
-        off = 0
-        wide = []
+        off, wide = 0, []
         for x, w, b, co in zip(xs, w32, b32, couts):
             Cin = x.shape[1]
             # wide projections (the 2D head's 64 box-distribution and nc class outputs): a 1x1 conv with bias on the MFMA kernels,
@@ -1262,8 +1289,7 @@ class HeadProjFn(torch.autograd.Function):
             mf = co >= 32 and co % 8 == 0 and off % 8 == 0 and tot % 8 == 0 and Cin % 8 == 0
             wide.append(mf)
             if mf:
-                wp = torch.empty(co * Cin, dtype=dtype, device=x.device)
-                L.pack_weight_fwd(dt, w.data_ptr(), wp.data_ptr(), co, Cin, Cin, 1, 1, st)
+                wp = _fwd_packed(w, co, Cin, Cin, 1, dtype)  # (on the spot: these weights are no entries of the pack registry)
                 sb, sh, sw = s3(x)
                 L.conv2d_fwd(dt, x.data_ptr(), sb, sh, sw, B, H, W, Cin, wp.data_ptr(), b.data_ptr(), out.data_ptr() + off * esz, tot, H, W, co,
                              1, 1, 1, 1, 0, None, st)
@@ -1282,8 +1308,7 @@ class HeadProjFn(torch.autograd.Function):
         L = lib()
         n, couts, dtype = ctx.n, ctx.couts, ctx.dtype
         xs, ws = ctx.saved_tensors[:n], ctx.saved_tensors[n:]
-        dt = code(dtype)
-        st = stream()
+        dt, st = code(dtype), stream()
         if not (dout.dtype == dtype and px_dense(dout)):
             dout = to_nhwc(dout, dtype, dense=True) if dout.shape[1] % ce(dtype) == 0 else _dense_any(dout, dtype)
         B, tot, H, W = dout.shape
@@ -1292,8 +1317,7 @@ class HeadProjFn(torch.autograd.Function):
         esz = dout.element_size()
         dsw = dout.stride(3)
         nb = L.proj_blocks(P)
-        dxs, dws, dbs = [], [], []
-        off = 0
+        dxs, dws, dbs, off = [], [], [], 0
         for j, (x, w, co) in enumerate(zip(xs, ws, couts)):
             Cin = x.shape[1]
             dx = None
@@ -1301,9 +1325,7 @@ class HeadProjFn(torch.autograd.Function):
                 dptr = dout.data_ptr() + off * esz
                 dsb, dsh, _ = s3(dout)
                 if ctx.needs_input_grad[1 + j]:
-                    kp = L.conv_kpad(dt, co)
-                    wpd = torch.empty(Cin * kp, dtype=dtype, device=dev)
-                    L.pack_weight_dgrad(dt, w.data_ptr(), wpd.data_ptr(), co, Cin, 1, 1, 1, st)
+                    wpd = _dgrad_packed(w, w.data_ptr(), co, Cin, 1, 1, dtype)
                     dx = nhwc_empty(B, Cin, H, W, dtype, dev)
                     L.conv2d_bwd_data(dt, dptr, dsb, dsh, dsw, B, H, W, co, wpd.data_ptr(), dx.data_ptr(), Cin, H, W, Cin, 1, 1, 1, 1, 0, st)
                 sb, sh, sw = s3(x)
@@ -1317,29 +1339,19 @@ class HeadProjFn(torch.autograd.Function):
                 L.colsum_partials(dt, dptr, dsw, part.data_ptr(), P, co, st)
                 db, scratch = _f32(co, dev), _f32(2 * co, dev)
                 L.bn_bwd_finalize(part.data_ptr(), nbb, co, P, None, db.data_ptr(), 0, scratch.data_ptr(), scratch.data_ptr() + 4 * co, st)
-                dxs.append(dx)
-                dws.append(dW)
-                dbs.append(db)
-                off += co
-                continue
-            if ctx.needs_input_grad[1 + j]:
-                dx = nhwc_empty(B, Cin, H, W, dtype, dev)
-                first = True
-                for o0 in range(0, co, 24):
-                    oc = min(24, co - o0)
-                    if first:
-                        L.proj_bwd_data(dt, dout.data_ptr() + (off + o0) * esz, dsw, w.data_ptr() + o0 * Cin * 4, dx.data_ptr(), Cin, P, Cin, oc, st)
-                        first = False
-                    else:
-                        tmp = nhwc_empty(B, Cin, H, W, dtype, dev)
-                        L.proj_bwd_data(dt, dout.data_ptr() + (off + o0) * esz, dsw, w.data_ptr() + o0 * Cin * 4, tmp.data_ptr(), Cin, P, Cin, oc, st)
-                        L.add2d(dt, dx.data_ptr(), Cin, tmp.data_ptr(), Cin, dx.data_ptr(), Cin, P, Cin, st)
-            dW = torch.empty_like(w)
-            db = _f32(co, dev)
-            slab = _f32(nb * co * Cin, dev)
-            bslab = _f32(nb * co, dev)
-            L.proj_bwd_weight(dt, x.data_ptr(), x.stride(3), dout.data_ptr() + off * esz, dsw, slab.data_ptr(), bslab.data_ptr(),
-                              dW.data_ptr(), db.data_ptr(), 0, P, Cin, co, st)
+            else:
+                if ctx.needs_input_grad[1 + j]:
+                    dx = nhwc_empty(B, Cin, H, W, dtype, dev)
+                    for o0 in range(0, co, 24):  # 24 outputs per launch; the later chunks go through a temporary and are added
+                        tgt = dx if o0 == 0 else nhwc_empty(B, Cin, H, W, dtype, dev)
+                        L.proj_bwd_data(dt, dout.data_ptr() + (off + o0) * esz, dsw, w.data_ptr() + o0 * Cin * 4, tgt.data_ptr(), Cin, P, Cin,
+                                        min(24, co - o0), st)
+                        if o0:
+                            L.add2d(dt, dx.data_ptr(), Cin, tgt.data_ptr(), Cin, dx.data_ptr(), Cin, P, Cin, st)
+                dW, db = torch.empty_like(w), _f32(co, dev)
+                slab, bslab = _f32(nb * co * Cin, dev), _f32(nb * co, dev)
+                L.proj_bwd_weight(dt, x.data_ptr(), x.stride(3), dout.data_ptr() + off * esz, dsw, slab.data_ptr(), bslab.data_ptr(),
+                                  dW.data_ptr(), db.data_ptr(), 0, P, Cin, co, st)
             dxs.append(dx)
             dws.append(dW)
             dbs.append(db)
@@ -1347,28 +1359,54 @@ class HeadProjFn(torch.autograd.Function):
         return (None, *dxs, *dws, *dbs)
 
 
+# What the grouped head projections (proj_group.hip, proj_bn_mfma.hip) take per launch: branch j projects channels [offsets[j],
+# offsets[j] + cin) of one stacked tensor to couts[j] outputs (tot in all).  w32 / b32: the fp32 weights and biases; c_w / c_b / c_off /
+# c_co: the ctypes arrays of their addresses, of the offsets and of the output counts.
+ProjGroup = namedtuple("ProjGroup", "n cin couts tot w32 b32 c_w c_b c_off c_co")
+
+
+def _proj_group(ws, bs, offsets, cin):
+    """the ProjGroup of weights `ws` and biases `bs` (none: a backward, which launches nothing that reads them)"""
+    n = len(ws)
+    assert n <= 16, "grouped projections: at most 16 branches"
+    couts = [w.shape[0] for w in ws]
+    w32 = [w.detach().float().contiguous() for w in ws]
+    b32 = [b.detach().float().contiguous() for b in bs]
+    PV, IA = ctypes.c_void_p * n, ctypes.c_int * n
+    return ProjGroup(n, cin, couts, sum(couts), w32, b32, PV(*[t.data_ptr() for t in w32]), PV(*[t.data_ptr() for t in b32]) if b32 else None,
+                     IA(*offsets), IA(*couts))
+
+
+def _proj_wgrad_buffers(pg, nb, dev):
+    """the weight-gradient side of a ProjGroup for a launch of `nb` blocks: per-branch dW / db, the split slabs, and the ctypes arrays of
+    the dW / db addresses -> (dws, dbs, slab, bslab, c_dw, c_db)"""
+    dws = [torch.empty_like(w) for w in pg.w32]
+    dbs = [_f32(co, dev) for co in pg.couts]
+    PV = ctypes.c_void_p * pg.n
+    return (dws, dbs, _f32(nb * pg.tot * pg.cin, dev), _f32(nb * pg.tot, dev), PV(*[t.data_ptr() for t in dws]), PV(*[t.data_ptr() for t in dbs]))
+
+
+def _proj_mfma(dtype, cin):
+    """the projections (and the BatchNorm backward through them) run on the matrix-core kernels of proj_bn_mfma.hip"""
+    return dtype == torch.bfloat16 and cin in (64, 128) and PROJ_BN_MFMA
+
+
 def proj_slices_eval(x, offsets, cin, ws, bs):
     """eval form of HeadProjSlicesFn (no graph): branch j projects channels [offsets[j], offsets[j] + cin) of the ACTIVATED features x with
     its 1x1 conv + bias (head.py:637), all branches in one launch.  bf16 with 64 / 128 channels per branch: the matrix-core kernel of
     the training head (proj_bn_mfma.hip) with an identity BatchNorm (scale 1, shift 0, no activation) - the VALU form
     (y3d_proj_group_fwd) took 42 us per level for the 1 600 candidate pixels of a batch of 32 (128-long serial dot products)."""
-    import ctypes
     n = len(ws)
     dtype = _COMPUTE_DTYPE
-    if not (dtype == torch.bfloat16 and cin in (64, 128) and PROJ_BN_MFMA and n <= 16):
+    if not (_proj_mfma(dtype, cin) and n <= 16):
         return HeadProjSlicesFn.apply(x, offsets, [cin] * n, n, *ws, *bs)
-    L, st = lib(), stream()
     x = to_nhwc(x, dtype, dense=True)
     B, Ct, H, W = x.shape
-    couts = [w.shape[0] for w in ws]
-    tot = sum(couts)
-    out = nhwc_empty(B, tot, H, W, dtype, x.device)
-    w32 = [w.detach().float().contiguous() for w in ws]
-    b32 = [b.detach().float().contiguous() for b in bs]
+    pg = _proj_group(ws, bs, offsets, cin)
+    out = nhwc_empty(B, pg.tot, H, W, dtype, x.device)
     ident = _identity_bn(Ct, x.device)
-    PV, IA = ctypes.c_void_p * n, ctypes.c_int * n
-    L.proj_group_fwd_bn_mfma(n, cin, x.data_ptr(), x.stride(3), IA(*offsets), PV(*[t.data_ptr() for t in w32]), PV(*[t.data_ptr() for t in b32]), IA(*couts),
-                             ident[0].data_ptr(), ident[1].data_ptr(), 0, out.data_ptr(), tot, B * H * W, st)
+    lib().proj_group_fwd_bn_mfma(n, cin, x.data_ptr(), x.stride(3), pg.c_off, pg.c_w, pg.c_b, pg.c_co, ident[0].data_ptr(), ident[1].data_ptr(), 0,
+                                 out.data_ptr(), pg.tot, B * H * W, stream())
     return out
 
 
@@ -1379,61 +1417,41 @@ class HeadProjSlicesFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, offsets, cins, n, *args):
-        import ctypes
         L = lib()
         ws, bs = args[:n], args[n:2 * n]
         dtype = _COMPUTE_DTYPE
-        dt = code(dtype)
-        st = stream()
         x = to_nhwc(x, dtype, dense=True)
         B, Ct, H, W = x.shape
-        P = B * H * W
-        couts = [w.shape[0] for w in ws]
         cin = cins[0]
-        assert all(c == cin for c in cins) and n <= 16, "HeadProjSlicesFn: uniform branch width, at most 16 branches"
-        tot = sum(couts)
-        out = nhwc_empty(B, tot, H, W, dtype, x.device)
-        w32 = [w.detach().float().contiguous() for w in ws]
-        b32 = [b.detach().float().contiguous() for b in bs]
-        PV = ctypes.c_void_p * n
-        IA = ctypes.c_int * n
-        c_w, c_b = PV(*[w.data_ptr() for w in w32]), PV(*[b.data_ptr() for b in b32])
-        c_off, c_co = IA(*offsets), IA(*couts)
-        L.proj_group_fwd(dt, n, cin, x.data_ptr(), x.stride(3), c_off, c_w, c_b, c_co, out.data_ptr(), tot, P, st)
-        ctx.meta = (list(offsets), cin, n, couts, dtype)
-        ctx.save_for_backward(x, *w32)
+        assert all(c == cin for c in cins), "HeadProjSlicesFn: uniform branch width"
+        pg = _proj_group(ws, bs, offsets, cin)
+        out = nhwc_empty(B, pg.tot, H, W, dtype, x.device)
+        L.proj_group_fwd(code(dtype), n, cin, x.data_ptr(), x.stride(3), pg.c_off, pg.c_w, pg.c_b, pg.c_co, out.data_ptr(), pg.tot, B * H * W, stream())
+        ctx.meta = (list(offsets), cin, dtype)
+        ctx.save_for_backward(x, *pg.w32)
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        import ctypes
         L = lib()
-        offsets, cin, n, couts, dtype = ctx.meta
+        offsets, cin, dtype = ctx.meta
         x, ws = ctx.saved_tensors[0], ctx.saved_tensors[1:]
-        dt = code(dtype)
-        st = stream()
+        dt, st = code(dtype), stream()
         if not (dout.dtype == dtype and px_dense(dout)):
             dout = _dense_any(dout, dtype)
         B, Ct, H, W = x.shape
         P = B * H * W
         dev = x.device
-        tot = sum(couts)
-        PV = ctypes.c_void_p * n
-        IA = ctypes.c_int * n
-        c_w, c_off, c_co = PV(*[w.data_ptr() for w in ws]), IA(*offsets), IA(*couts)
+        pg = _proj_group(ws, (), offsets, cin)
         dx = None
         if ctx.needs_input_grad[0]:
             dx = nhwc_empty(B, Ct, H, W, dtype, dev)
-            if n * cin != Ct:
+            if pg.n * cin != Ct:
                 dx.zero_()
-            L.proj_group_bwd_data(dt, n, cin, dout.data_ptr(), dout.stride(3), c_off, c_w, c_co, dx.data_ptr(), Ct, P, st)
-        dws = [torch.empty_like(w) for w in ws]
-        dbs = [_f32(co, dev) for co in couts]
-        nb = L.proj_group_blocks(P)
-        slab = _f32(nb * tot * cin, dev)
-        bslab = _f32(nb * tot, dev)
-        L.proj_group_bwd_weight(dt, n, cin, x.data_ptr(), x.stride(3), c_off, dout.data_ptr(), dout.stride(3), c_co, slab.data_ptr(),
-                                bslab.data_ptr(), PV(*[t.data_ptr() for t in dws]), PV(*[t.data_ptr() for t in dbs]), P, st)
+            L.proj_group_bwd_data(dt, pg.n, cin, dout.data_ptr(), dout.stride(3), pg.c_off, pg.c_w, pg.c_co, dx.data_ptr(), Ct, P, st)
+        dws, dbs, slab, bslab, c_dw, c_db = _proj_wgrad_buffers(pg, L.proj_group_blocks(P), dev)
+        L.proj_group_bwd_weight(dt, pg.n, cin, x.data_ptr(), x.stride(3), pg.c_off, dout.data_ptr(), dout.stride(3), pg.c_co, slab.data_ptr(),
+                                bslab.data_ptr(), c_dw, c_db, P, st)
         return (dx, None, None, None, *dws, *dbs)
 
 
@@ -1446,15 +1464,13 @@ class FusedConvBNProjFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, stack, groups, offsets, cins, n, *params):
-        import ctypes
         L = lib()
         w, gm, bt, rm, rv = stack.tensors()
         m = stack.convs[0]
         npar = len(params) - 2 * n
         ws, bs = params[npar:npar + n], params[npar + n:]
         ctx.gslot = grad_slot(x) if (m.training and x.is_cuda) else None
-        y, cfg, saved = _cba_forward(x, w, gm, bt, rm, rv, m.k, m.s, m.p, groups, m.has_act, None, 0, m.training, m.eps, m.momentum, bn_apply=False,
-                                     ver=stack.ver)
+        y, cfg, saved = _cba_forward(x, _module_call(m, w32=w, g32=gm, b32=bt, rm=rm, rv=rv, g=groups, bn_apply=False, ver=stack.ver))
         if m.training:
             for c in stack.convs:
                 c._nbt_pending += 1
@@ -1462,59 +1478,47 @@ class FusedConvBNProjFn(torch.autograd.Function):
         dt, st = code(dtype), stream()
         B, Ct, H, W = y.shape
         P = B * H * W
-        couts = [t.shape[0] for t in ws]
         cin = cins[0]
-        assert all(c == cin for c in cins) and n <= 16 and n * cin == Ct and cin % 64 == 0
-        tot = sum(couts)
-        out = nhwc_empty(B, tot, H, W, dtype, y.device)
-        w32 = [t.detach().float().contiguous() for t in ws]
-        b32 = [t.detach().float().contiguous() for t in bs]
-        PV, IA = ctypes.c_void_p * n, ctypes.c_int * n
+        assert all(c == cin for c in cins) and n * cin == Ct and cin % 64 == 0
+        pg = _proj_group(ws, bs, offsets, cin)
+        out = nhwc_empty(B, pg.tot, H, W, dtype, y.device)
         stats = saved[3]
-        if dtype == torch.bfloat16 and cin in (64, 128) and PROJ_BN_MFMA:
-            L.proj_group_fwd_bn_mfma(n, cin, y.data_ptr(), y.stride(3), IA(*offsets), PV(*[t.data_ptr() for t in w32]), PV(*[t.data_ptr() for t in b32]),
-                                     IA(*couts), stats[2].data_ptr(), stats[3].data_ptr(), int(m.has_act), out.data_ptr(), tot, P, st)
+        tail = (y.data_ptr(), y.stride(3), pg.c_off, pg.c_w, pg.c_b, pg.c_co, stats[2].data_ptr(), stats[3].data_ptr(), int(m.has_act), out.data_ptr(),
+                pg.tot, P, st)
+        if _proj_mfma(dtype, cin):
+            L.proj_group_fwd_bn_mfma(n, cin, *tail)
         else:
-            L.proj_group_fwd_bn(dt, n, cin, y.data_ptr(), y.stride(3), IA(*offsets), PV(*[t.data_ptr() for t in w32]), PV(*[t.data_ptr() for t in b32]),
-                                IA(*couts), stats[2].data_ptr(), stats[3].data_ptr(), int(m.has_act), out.data_ptr(), tot, P, st)
-        ctx.cfg, ctx.couts_stack, ctx.meta = cfg, stack.couts, (list(offsets), cin, n, couts, dtype, int(m.has_act))
-        ctx.nsaved = len(saved)
-        ctx.save_for_backward(*[t for t in saved if t is not None], *w32)
+            L.proj_group_fwd_bn(dt, n, cin, *tail)
+        ctx.cfg, ctx.couts_stack, ctx.meta = cfg, stack.couts, (list(offsets), cin, dtype, int(m.has_act))
+        ctx.save_for_backward(*[t for t in saved if t is not None], *pg.w32)
         ctx.none_mask = [t is None for t in saved]
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        import ctypes
         L = lib()
-        offsets, cin, n, couts, dtype, act = ctx.meta
+        offsets, cin, dtype, act = ctx.meta
         it = iter(ctx.saved_tensors)
         saved = tuple(None if isnone else next(it) for isnone in ctx.none_mask)
-        ws = list(it)
-        xin, w32c, y, stats, _ = saved
+        pg = _proj_group(list(it), (), offsets, cin)
+        y, stats = saved[2], saved[3]
         dt, st = code(dtype), stream()
         if not (dout.dtype == dtype and px_dense(dout)):
             dout = _dense_any(dout, dtype)
         B, Ct, H, W = y.shape
         P = B * H * W
         dev = y.device
-        tot = sum(couts)
-        PV, IA = ctypes.c_void_p * n, ctypes.c_int * n
-        c_w, c_off, c_co = PV(*[t.data_ptr() for t in ws]), IA(*offsets), IA(*couts)
-        dws = [torch.empty_like(t) for t in ws]
-        dbs = [_f32(co, dev) for co in couts]
-        mfma = dtype == torch.bfloat16 and cin in (64, 128) and PROJ_BN_MFMA
+        n, c_w, c_off, c_co = pg.n, pg.c_w, pg.c_off, pg.c_co
+        mfma = _proj_mfma(dtype, cin)
         dx_out = grad_slot_tensor(ctx.gslot) if (ctx.gslot is not None and ctx.needs_input_grad[0]) else None
         nb = L.proj_group_bwd_weight_bn_mfma_blocks(P) if mfma else L.proj_group_blocks(P)
-        slab, bslab = _f32(nb * tot * cin, dev), _f32(nb * tot, dev)
+        dws, dbs, slab, bslab, c_dw, c_db = _proj_wgrad_buffers(pg, nb, dev)
+        tail = (y.data_ptr(), y.stride(3), c_off, dout.data_ptr(), dout.stride(3), c_co, stats[2].data_ptr(), stats[3].data_ptr(), act, slab.data_ptr(),
+                bslab.data_ptr(), c_dw, c_db, P, st)
         if mfma:
-            L.proj_group_bwd_weight_bn_mfma(n, cin, y.data_ptr(), y.stride(3), c_off, dout.data_ptr(), dout.stride(3), c_co, stats[2].data_ptr(),
-                                            stats[3].data_ptr(), act, slab.data_ptr(), bslab.data_ptr(), PV(*[t.data_ptr() for t in dws]),
-                                            PV(*[t.data_ptr() for t in dbs]), P, st)
+            L.proj_group_bwd_weight_bn_mfma(n, cin, *tail)
         else:
-            L.proj_group_bwd_weight_bn(dt, n, cin, y.data_ptr(), y.stride(3), c_off, dout.data_ptr(), dout.stride(3), c_co, stats[2].data_ptr(),
-                                       stats[3].data_ptr(), act, slab.data_ptr(), bslab.data_ptr(), PV(*[t.data_ptr() for t in dws]),
-                                       PV(*[t.data_ptr() for t in dbs]), P, st)
+            L.proj_group_bwd_weight_bn(dt, n, cin, *tail)
         if mfma and ctx.cfg.training:
             # BatchNorm backward straight from `dout`: dz = dout . W is recomputed on the matrix cores by the reduce and the apply pass
             # (proj_bn_mfma.hip) instead of being written once and read twice (839 MB at the stride-8 level)
@@ -1532,13 +1536,8 @@ class FusedConvBNProjFn(torch.autograd.Function):
             dz = nhwc_empty(B, Ct, H, W, dtype, dev)
             L.proj_group_bwd_data(dt, n, cin, dout.data_ptr(), dout.stride(3), c_off, c_w, c_co, dz.data_ptr(), Ct, P, st)
             dx, dW, dg, db, _ = _cba_backward(ctx.cfg, saved, dz, ctx.needs_input_grad[0], False, None, dx_out=dx_out)
-        dWs, dgs, dbs_s, off = [], [], [], 0
-        for co in ctx.couts_stack:
-            dWs.append(dW[off:off + co])
-            dgs.append(dg[off:off + co])
-            dbs_s.append(db[off:off + co])
-            off += co
-        return (dx, None, None, None, None, None, *dWs, *dgs, *dbs_s, *dws, *dbs)
+        cs = ctx.couts_stack
+        return (dx, None, None, None, None, None, *dW.split(cs), *dg.split(cs), *db.split(cs), *dws, *dbs)
 
 
 def _dense_any(x, dtype):
