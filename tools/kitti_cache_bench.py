@@ -68,8 +68,7 @@ def main():
         # the three launches, each between two events, on the draws of one seed
         np.random.seed(0)
         draws = kitti.sample_augment(n, items, split.frame_info, args)
-        table = torch.from_numpy(np.stack([np.concatenate(([p, d["partner"], d["flip"], d["scale"]], d["trans"].reshape(6), d["trans_inv"].reshape(6)))
-                                           for p, d in zip(items, draws)]))
+        table = torch.from_numpy(kitti.draw_table(items, draws))
         table_dev = table.to(dev)
         plan = kitti.plan_batch(split, table, table_dev)
         W, H = kitti.RESOLUTION

@@ -136,44 +136,17 @@ def flip_calib(P2, img_size):
     the float64 intrinsics (KITTI's text reader makes them float32 first, which `kitti.flip_calib` reproduces).  -> P2 (3, 4) float32"""
     import numpy as np
     P = np.asarray(P2, np.float64)
-    W, H = float(img_size[0]), float(img_size[1])
-    cu, cv, fu, fv, tx, ty = P[0, 2], P[1, 2], P[0, 0], P[1, 1], P[0, 3] / -P[0, 0], P[1, 3] / -P[1, 1]
-    u = np.tile(np.linspace(0.0, W, 4), 2)
-    v = np.repeat(np.linspace(0.0, H, 2), 4)
-    z = np.linspace(2.0, 78.0, 8)
-    x, y = ((u - cu) * z) / fu + tx, ((v - cv) * z) / fv + ty
-    x, u = -x, W - u
-    one, nil = np.ones(8), np.zeros(8)
-    A = np.concatenate([np.stack([x, z, nil, one, nil, -u], 1), np.stack([y, nil, z, nil, one, -v], 1)])
-    f, c_u, c_v, t_u, t_v, _ = np.linalg.lstsq(A, np.concatenate([u * z, v * z]), rcond=None)[0]
-    out = np.zeros((3, 4), np.float32)
-    out[0] = (f, 0.0, c_u, t_u)
-    out[1] = (0.0, f, c_v, t_v)
-    out[2, 3] = P[2, 3]
-    return out
+    cam = (P[0, 2], P[1, 2], P[0, 0], P[1, 1], P[0, 3] / -P[0, 0], P[1, 3] / -P[1, 1])
+    return kitti._flip_fit(cam, float(img_size[0]), float(img_size[1]), P[2, 3])
 
 
 def pack_labels(records, partners, P2s, trans, flips, scales, img_sizes, device, dataset):
     """Host side of encode_labels: B images' object records (partners[b]: the mixup partner's, or None), their P2 (float64 as read,
     or the float32 `flip_calib` result when flips[b]), crop matrices, crop scales and original (W, H) -> dict of device tensors"""
     import numpy as np
-    if torch.device(device).type != "cuda":
-        raise Y3DError("pack_labels: the label encoder runs on a HIP device (no host fallback)")
-    B = len(records)
-    recs, img_i, img_f, row = [], np.zeros((B, 7), np.int32), np.zeros((B, 19), np.float64), 0
-    for b in range(B):
-        r0 = np.asarray(records[b], np.float64).reshape(-1, REC_W)
-        r1 = np.asarray(partners[b], np.float64).reshape(-1, REC_W) if partners[b] is not None else np.zeros((0, REC_W))
-        img_i[b] = (row, len(r0), row + len(r0), len(r1), int(bool(flips[b])), int(img_sizes[b][0]), int(img_sizes[b][1]))
-        img_f[b, :12] = np.asarray(P2s[b], np.float64).reshape(12)
-        img_f[b, 12:18] = np.asarray(trans[b], np.float64).reshape(6)
-        img_f[b, 18] = float(scales[b])
-        recs += [r0, r1]
-        row += len(r0) + len(r1)
-    rec = np.concatenate(recs) if row else np.zeros((1, REC_W))
-    up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a)).to(device=device, dtype=dt)
-    return {"rec": up(rec, torch.float64), "img_i": up(img_i, torch.int32), "img_f": up(img_f, torch.float64),
-            "mean_size": up(np.asarray(CLS_MEAN_SIZE[dataset], np.float64).reshape(-1, 3), torch.float64), "dataset": dataset}
+    records_of = lambda r: np.asarray(r, np.float64).reshape(-1, REC_W)
+    packed = kitti._pack(records, partners, P2s, trans, flips, scales, img_sizes, device, (records_of, REC_W, "float64", CLS_MEAN_SIZE[dataset]))
+    return dict(packed, dataset=dataset)
 
 
 def encode_labels(packed, out_wh=RESOLUTION, min_depth=1.0, max_depth=120.0, use_camera_dis=False, max_objs=MAX_OBJS):
@@ -185,14 +158,8 @@ def encode_labels(packed, out_wh=RESOLUTION, min_depth=1.0, max_depth=120.0, use
     if packed["rec"].shape[-1] != REC_W:
         raise Y3DError(f"encode_labels: records of width {packed['rec'].shape[-1]}, expected {REC_W}")
     mode = _dataset_mode(packed["dataset"])
-    dev, B = img_i.device, img_i.shape[0]
-    n = B * max_objs
-    e = lambda *s, dt: torch.empty(*s, dtype=dt, device=dev)
-    o = {"cls": e(n, 1, dt=torch.int64), "bboxes": e(n, 4, dt=torch.float64), "center_2d": e(n, 2, dt=torch.float32),
-         "size_2d": e(n, 2, dt=torch.float32), "center_3d": e(n, 2, dt=torch.float64), "size_3d": e(n, 3, dt=torch.float64),
-         "depth": e(n, dt=torch.float64), "heading_bin": e(n, dt=torch.int64), "heading_res": e(n, dt=torch.float64),
-         "batch_idx": e(n, dt=torch.float32), "counts": e(B, dt=torch.int32), "calib": e(B, 6, dt=torch.float64),
-         "ratio_pad": e(B, 2, 2, dt=torch.float64)}
+    B = img_i.shape[0]
+    o = kitti._label_outputs(B, max_objs, img_i.device)
     ms = packed["mean_size"]
     lib().json3d_encode_labels(packed["rec"].data_ptr(), img_i.data_ptr(), packed["img_f"].data_ptr(), B, mode, int(out_wh[0]),
                                int(out_wh[1]), float(min_depth), float(max_depth), int(bool(use_camera_dis)), ms.data_ptr(), ms.shape[0],
@@ -264,14 +231,6 @@ def build_batch(json_file, indices, args, device, dataset="waymo", mode="train",
                          [im.size for im in frames], device, dataset)
     cam_dis = bool(getattr(args, "cam_dis", False))
     lab = encode_labels(packed, RESOLUTION, args.min_depth_threshold, args.max_depth_threshold, cam_dis, MAX_OBJS)
-    batch = {"img": img, "calib": lab["calib"],
-             "info": [{"img_id": ids[p], "img_size": np.array(im.size), "trans_inv": d["trans_inv"]} for p, im, d in zip(indices, frames, draws)],
-             "im_file": ["%06d.txt" % ids[p] for p in indices], "ori_shape": [np.array(im.size)[::-1] for im in frames],
-             "ratio_pad": lab["ratio_pad"], "mean_sizes": packed["mean_size"],
-             "mixed": torch.tensor([int(d["mixed"]) for d in draws], dtype=torch.uint8).to(device), "counts": lab["counts"]}
-    if compact:
-        batch.update(compact_labels(lab, lab["counts"].tolist(), cam_dis, MAX_OBJS, dataset))
-        del batch["counts"]
-    else:
-        batch.update({k: lab[k] for k in PER_BOX})
-    return batch
+    mixed = torch.tensor([int(d["mixed"]) for d in draws], dtype=torch.uint8).to(device)
+    return kitti._batch(img, lab, [ids[p] for p in indices], [im.size for im in frames], draws, packed["mean_size"], mixed,
+                        compact and (lambda counts: compact_labels(lab, counts, cam_dis, MAX_OBJS, dataset)))

@@ -16,6 +16,7 @@ import torch
 
 from . import ops
 from ._lib import Y3DError, lib
+from .resident import DrawRing, ResidentSplit, check_plan, epoch_indices, fill_arena, span_table, upload  # noqa: F401  (re-exported)
 
 # (h, w, l) per class, kitti.py:38-41
 CLS_MEAN_SIZE = ((1.52563191462, 1.62856739989, 3.88311640418), (1.76255119, 0.66068622, 0.84422524), (1.73698127, 0.59706367, 1.76282397))
@@ -214,13 +215,10 @@ def calib_params(P2):
     return (float(P[0, 2]), float(P[1, 2]), float(P[0, 0]), float(P[1, 1]), float(P[0, 3] / -P[0, 0]), float(P[1, 3] / -P[1, 1]))
 
 
-def flip_calib(P2, img_size):
-    """The projection of the mirrored image (kitti_utils.py Calibration.flip): eight pixels of a 4 x 2 grid over the image, at depths
-    2 .. 78, are lifted to 3D with the float32 calibration, mirrored (x -> -x, u -> W - u), and a pinhole camera with fu = fv is fitted to
-    them by least squares in float64.  -> P2 (3, 4) float32; as in the reference, its third row is (0, 0, 0, P2[2, 3])."""
+def _flip_fit(cam, W, H, p23):
+    """flip_calib's fit for the intrinsics cam = (cu, cv, fu, fv, tx, ty) of a W x H image; p23 = P2[2, 3] -> P2 (3, 4) float32"""
     import numpy as np
-    W, H = float(img_size[0]), float(img_size[1])
-    cu, cv, fu, fv, tx, ty = calib_params(P2)
+    cu, cv, fu, fv, tx, ty = cam
     u = np.tile(np.linspace(0.0, W, 4), 2)
     v = np.repeat(np.linspace(0.0, H, 2), 4)
     z = np.linspace(2.0, 78.0, 8)
@@ -234,8 +232,16 @@ def flip_calib(P2, img_size):
     out = np.zeros((3, 4), np.float32)
     out[0] = (f, 0.0, c_u, t_u)
     out[1] = (0.0, f, c_v, t_v)
-    out[2, 3] = np.asarray(P2, np.float32)[2, 3]
+    out[2, 3] = p23
     return out
+
+
+def flip_calib(P2, img_size):
+    """The projection of the mirrored image (kitti_utils.py Calibration.flip): eight pixels of a 4 x 2 grid over the image, at depths
+    2 .. 78, are lifted to 3D with the float32 calibration, mirrored (x -> -x, u -> W - u), and a pinhole camera with fu = fv is fitted to
+    them by least squares in float64.  -> P2 (3, 4) float32; as in the reference, its third row is (0, 0, 0, P2[2, 3])."""
+    import numpy as np
+    return _flip_fit(calib_params(P2), float(img_size[0]), float(img_size[1]), np.asarray(P2, np.float32)[2, 3])
 
 
 def sample_augment(n, items, frame_info, args, mode="train", max_objs=MAX_OBJS, resolution=RESOLUTION):
@@ -292,27 +298,44 @@ def label_records(lab):
     return r
 
 
-def pack_labels(labels, partners, P2s, trans, flips, scales, img_sizes, device, cls_mean_size=CLS_MEAN_SIZE):
-    """Host side of encode_labels: B images' read_label dicts (partners[b]: the mixup partner's, or None), their P2 (flipped when
-    flips[b]: flip_calib), crop matrices `trans` (2, 3), crop scales and original (W, H) -> dict of device tensors (one upload each)"""
+def _pack(items, partners, P2s, trans, flips, scales, img_sizes, device, source):
+    """pack_labels of this module and of json3d.  source = (records, rec_w, p2_dtype, mean_size): `records(item)` -> the (n, rec_w)
+    float64 records of one image, the dtype the projections are rounded to on their way into `img_f`, the class mean sizes."""
     import numpy as np
+    records, rec_w, p2_dtype, mean_size = source
     if torch.device(device).type != "cuda":
         raise Y3DError("pack_labels: the label encoder runs on a HIP device (no host fallback)")
-    B = len(labels)
+    B = len(items)
     recs, img_i, img_f, row = [], np.zeros((B, 7), np.int32), np.zeros((B, 19), np.float64), 0
     for b in range(B):
-        r0 = label_records(labels[b])
-        r1 = label_records(partners[b]) if partners[b] is not None else np.zeros((0, _REC_W))
+        r0 = records(items[b])
+        r1 = records(partners[b]) if partners[b] is not None else np.zeros((0, rec_w))
         img_i[b] = (row, len(r0), row + len(r0), len(r1), int(bool(flips[b])), int(img_sizes[b][0]), int(img_sizes[b][1]))
-        img_f[b, :12] = np.asarray(P2s[b], np.float32).reshape(12)
+        img_f[b, :12] = np.asarray(P2s[b], p2_dtype).reshape(12)
         img_f[b, 12:18] = np.asarray(trans[b], np.float64).reshape(6)
         img_f[b, 18] = float(scales[b])
         recs += [r0, r1]
         row += len(r0) + len(r1)
-    rec = np.concatenate(recs) if row else np.zeros((1, _REC_W))
-    up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a)).to(device=device, dtype=dt)
-    return {"rec": up(rec, torch.float64), "img_i": up(img_i, torch.int32), "img_f": up(img_f, torch.float64),
-            "mean_size": up(np.asarray(cls_mean_size, np.float64).reshape(-1, 3), torch.float64)}
+    rec = np.concatenate(recs) if row else np.zeros((1, rec_w))
+    return {"rec": upload(rec, device, torch.float64), "img_i": upload(img_i, device, torch.int32), "img_f": upload(img_f, device, torch.float64),
+            "mean_size": upload(np.asarray(mean_size, np.float64).reshape(-1, 3), device, torch.float64)}
+
+
+def pack_labels(labels, partners, P2s, trans, flips, scales, img_sizes, device, cls_mean_size=CLS_MEAN_SIZE):
+    """Host side of encode_labels: B images' read_label dicts (partners[b]: the mixup partner's, or None), their P2 (flipped when
+    flips[b]: flip_calib), crop matrices `trans` (2, 3), crop scales and original (W, H) -> dict of device tensors (one upload each)"""
+    return _pack(labels, partners, P2s, trans, flips, scales, img_sizes, device, (label_records, _REC_W, "float32", cls_mean_size))
+
+
+def _label_outputs(B, max_objs, dev):
+    """the thirteen tensors of encode_labels' static layout, unwritten"""
+    n = B * max_objs
+    e = lambda *s, dt: torch.empty(*s, dtype=dt, device=dev)
+    return {"cls": e(n, 1, dt=torch.int64), "bboxes": e(n, 4, dt=torch.float64), "center_2d": e(n, 2, dt=torch.float32),
+            "size_2d": e(n, 2, dt=torch.float32), "center_3d": e(n, 2, dt=torch.float64), "size_3d": e(n, 3, dt=torch.float64),
+            "depth": e(n, dt=torch.float64), "heading_bin": e(n, dt=torch.int64), "heading_res": e(n, dt=torch.float64),
+            "batch_idx": e(n, dt=torch.float32), "counts": e(B, dt=torch.int32), "calib": e(B, 6, dt=torch.float64),
+            "ratio_pad": e(B, 2, 2, dt=torch.float64)}
 
 
 def encode_labels(packed, out_wh=RESOLUTION, min_depth=1.0, max_depth=120.0, use_camera_dis=False, max_objs=MAX_OBJS):
@@ -323,14 +346,8 @@ def encode_labels(packed, out_wh=RESOLUTION, min_depth=1.0, max_depth=120.0, use
     img_i = packed["img_i"]
     if not img_i.is_cuda or any(not packed[k].is_cuda for k in ("rec", "img_f", "mean_size")):
         raise Y3DError("encode_labels: the packed labels must live on a HIP device (no host fallback)")
-    dev, B = img_i.device, img_i.shape[0]
-    n = B * max_objs
-    e = lambda *s, dt: torch.empty(*s, dtype=dt, device=dev)
-    o = {"cls": e(n, 1, dt=torch.int64), "bboxes": e(n, 4, dt=torch.float64), "center_2d": e(n, 2, dt=torch.float32),
-         "size_2d": e(n, 2, dt=torch.float32), "center_3d": e(n, 2, dt=torch.float64), "size_3d": e(n, 3, dt=torch.float64),
-         "depth": e(n, dt=torch.float64), "heading_bin": e(n, dt=torch.int64), "heading_res": e(n, dt=torch.float64),
-         "batch_idx": e(n, dt=torch.float32), "counts": e(B, dt=torch.int32), "calib": e(B, 6, dt=torch.float64),
-         "ratio_pad": e(B, 2, 2, dt=torch.float64)}
+    B = img_i.shape[0]
+    o = _label_outputs(B, max_objs, img_i.device)
     ms = packed["mean_size"]
     lib().kitti_encode_labels(packed["rec"].data_ptr(), img_i.data_ptr(), packed["img_f"].data_ptr(), B, int(out_wh[0]), int(out_wh[1]),
                               float(min_depth), float(max_depth), int(bool(use_camera_dis)), ms.data_ptr(), ms.shape[0], int(max_objs),
@@ -381,6 +398,22 @@ def _split(root_or_split_file, mode):
     data = os.path.join(root, "testing" if mode == "test" else "training")
     ids = [int(s.strip()) for s in open(split_file).read().splitlines() if s.strip()]
     return data, ids
+
+
+def _batch(img, lab, ids, sizes, draws, mean_size, mixed, compact):
+    """The dictionary every 3D builder returns (json3d's too): the images, encode_labels' `lab`, and per image its id, its original
+    (W, H) and its draws.  compact: false for the per-box keys in the static layout, or counts (host ints) -> the ragged ones."""
+    import numpy as np
+    batch = {"img": img, "calib": lab["calib"],
+             "info": [{"img_id": i, "img_size": np.array(s), "trans_inv": d["trans_inv"]} for i, s, d in zip(ids, sizes, draws)],
+             "im_file": [f"{i:06d}.txt" for i in ids], "ori_shape": [np.array(s)[::-1] for s in sizes],
+             "ratio_pad": lab["ratio_pad"], "mean_sizes": mean_size, "mixed": mixed, "counts": lab["counts"]}
+    if compact:
+        batch.update(compact(lab["counts"].tolist()))
+        del batch["counts"]
+    else:
+        batch.update({k: lab[k] for k in PER_BOX})
+    return batch
 
 
 def build_batch(root_or_split_file, indices, args, device, mode="train", compact=False, img_mode="uint8", resolution=RESOLUTION):
@@ -444,41 +477,28 @@ def build_batch(root_or_split_file, indices, args, device, mode="train", compact
     packed = pack_labels(labels, partners, P2s, [d["trans"] for d in draws], [d["flip"] for d in draws], [d["scale"] for d in draws],
                          [im.size for im in frames], device)
     lab = encode_labels(packed, resolution, args.min_depth_threshold, args.max_depth_threshold, bool(args.cam_dis), MAX_OBJS)
-    batch = {"img": img, "calib": lab["calib"],
-             "info": [{"img_id": ids[p], "img_size": np.array(im.size), "trans_inv": d["trans_inv"]} for p, im, d in zip(indices, frames, draws)],
-             "im_file": [f"{ids[p]:06d}.txt" for p in indices], "ori_shape": [np.array(im.size)[::-1] for im in frames],
-             "ratio_pad": lab["ratio_pad"], "mean_sizes": packed["mean_size"],
-             "mixed": torch.tensor([int(d["mixed"]) for d in draws], dtype=torch.uint8).to(device), "counts": lab["counts"]}
-    if compact:
-        batch.update(compact_labels(lab, lab["counts"].tolist(), [d["crop"] for d in draws], bool(args.cam_dis)))
-        del batch["counts"]
-    else:
-        batch.update({k: lab[k] for k in PER_BOX})
-    return batch
+    mixed = torch.tensor([int(d["mixed"]) for d in draws], dtype=torch.uint8).to(device)
+    return _batch(img, lab, [ids[p] for p in indices], [im.size for im in frames], draws, packed["mean_size"], mixed,
+                  compact and (lambda counts: compact_labels(lab, counts, [d["crop"] for d in draws], bool(args.cam_dis))))
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
 # the split resident on the device: decoded once, then a batch is the draws, one small upload and three launches
 # ------------------------------------------------------------------------------------------------------------------------------
 _DRAW_W = 16  # a row of the draw table: position, partner (-1: none), flip, scale, trans (6), trans_inv (6)
-_ALIGN = 16  # every frame starts on a multiple of 16 bytes of the arena
 PLAN_TABLES = (("src", torch.int64, ()), ("src2", torch.int64, ()), ("hw", torch.int32, (2,)), ("flip", torch.int32, ()),
          ("trans_inv", torch.float64, (6,)), ("img_i", torch.int32, (7,)), ("img_f", torch.float64, (19,)), ("mixed", torch.uint8, ()))
 
 
-def epoch_indices(n, batch, shuffle=True, seed=0, drop_last=False):
-    """The batches of one epoch over n dataset positions: a list of index lists that covers every position once (drop_last: without the
-    short last batch).  shuffle: a permutation from a generator of its own seeded with `seed`, so np.random's global state — the stream
-    `sample_augment` replays — is not touched."""
+def draw_table(indices, draws):
+    """sample_augment's draws for dataset positions `indices` -> the (B, 16) float64 draw table of `y3d_kitti_plan_batch`, rows
+    [position, partner or -1, flip, scale, trans (6), trans_inv (6)]"""
     import numpy as np
-    n, batch = int(n), int(batch)
-    if batch < 1 or n < 0:
-        raise Y3DError(f"epoch_indices: batch = {batch}, n = {n}")
-    order = np.random.RandomState(int(seed)).permutation(n) if shuffle else np.arange(n)
-    out = [[int(i) for i in order[s:s + batch]] for s in range(0, n, batch)]
-    if drop_last and out and len(out[-1]) < batch:
-        out.pop()
-    return out
+    table = np.empty((len(indices), _DRAW_W), np.float64)
+    for row, p, d in zip(table, indices, draws):
+        row[:4] = (p, d["partner"], d["flip"], d["scale"])
+        row[4:10], row[10:] = d["trans"].reshape(6), d["trans_inv"].reshape(6)
+    return table
 
 
 def plan_batch(split, draws, draws_dev=None, out=None):
@@ -488,77 +508,14 @@ def plan_batch(split, draws, draws_dev=None, out=None):
     split are refused from the host table.  out: optionally the eight output tensors (at least B rows each; the first B are written).
     -> dict src, src2 (B) int64, hw (B, 2) int32, flip (B) int32, trans_inv (B, 6) float64, img_i (B, 7) int32, img_f (B, 19) float64,
     mixed (B) uint8."""
-    host = torch.as_tensor(draws)
-    if host.dim() != 2 or host.shape[1] != _DRAW_W or host.dtype != torch.float64 or host.is_cuda or not host.is_contiguous():
-        raise Y3DError(f"plan_batch: the draws are a contiguous (B, {_DRAW_W}) float64 table on the host, got {tuple(host.shape)} {host.dtype}")
-    B, dev = host.shape[0], split.device
-    if draws_dev is None:
-        draws_dev = host.to(dev)
-    if draws_dev.shape != host.shape or draws_dev.dtype != torch.float64 or draws_dev.device != dev or not draws_dev.is_contiguous():
-        raise Y3DError("plan_batch: the device copy of the draws must match the host table and live on the split's device")
-    if out is None:
-        out = {k: torch.empty(B, *s, dtype=dt, device=dev) for k, dt, s in PLAN_TABLES}
-    for k, dt, s in PLAN_TABLES:
-        t = out[k]
-        if t.dtype != dt or t.device != dev or t.dim() != 1 + len(s) or t.shape[0] < B or tuple(t.shape[1:]) != s or not t.is_contiguous():
-            raise Y3DError(f"plan_batch: output {k} must be a contiguous ({B}+, {', '.join(map(str, s))}) {dt} tensor on {dev}")
+    host, draws_dev, out = check_plan(draws, _DRAW_W, split.device, PLAN_TABLES, draws_dev, out)
     lib().kitti_plan_batch(split.img_off.data_ptr(), split.frame_hw.data_ptr(), split.rec_span.data_ptr(), split.P2.data_ptr(), len(split),
-                           split.arena.data_ptr(), host.data_ptr(), draws_dev.data_ptr(), B, *[out[k].data_ptr() for k, _, _ in PLAN_TABLES],
-                           ops.stream())
+                           split.arena.data_ptr(), host.data_ptr(), draws_dev.data_ptr(), host.shape[0],
+                           *[out[k].data_ptr() for k, _, _ in PLAN_TABLES], ops.stream())
     return out
 
 
-def fill_arena(arena, offsets, padded, decode, pool, chunk):
-    """Fills a uint8 device arena with decoded frames.  `decode(pos)` -> frame pos as an (H, W, 3) uint8 array (it raises for a frame it
-    does not accept); the frame lands at byte offsets[pos], where padded[pos] bytes are its own.  Runs of consecutive frames of at most
-    `chunk` bytes are decoded by the threads of `pool` into a pinned stage and reach the arena in one copy per run."""
-    N = len(offsets)
-    runs, first = [], 0
-    for pos in range(1, N + 1):
-        if pos == N or offsets[pos] + padded[pos] - offsets[first] > chunk:
-            runs.append((first, pos))
-            first = pos
-    stage = torch.zeros(max(int(offsets[b - 1] + padded[b - 1] - offsets[a]) for a, b in runs), dtype=torch.uint8).pin_memory()
-    stage_np = stage.numpy()
-
-    def put(pos, base):
-        px = decode(pos)
-        o = int(offsets[pos]) - base
-        stage_np[o:o + px.size] = px.reshape(-1)
-
-    for a, b in runs:
-        base, end = int(offsets[a]), int(offsets[b - 1] + padded[b - 1])
-        list(pool.map(lambda pos: put(pos, base), range(a, b)))
-        arena[base:end].copy_(stage[:end - base])  # from pinned memory; returns when the stage may be refilled
-
-
-class DrawRing:
-    """`n` pinned (rows, width) float64 draw tables in flight to `device`: `upload(rows)` writes a table into the next buffer and starts
-    a non-blocking copy -> (host view, device tensor).  A buffer is rewritten only after the copy that last read it has run (one event
-    per buffer)."""
-
-    def __init__(self, width, device, n):
-        self.width, self.device, self.n, self._r = int(width), device, int(n), None
-
-    def upload(self, rows):
-        B = len(rows)
-        if self._r is None or self._r["host"][0].shape[0] < B:
-            cap = max(64, B)
-            self._r = {"host": [torch.empty(cap, self.width, dtype=torch.float64).pin_memory() for _ in range(self.n)],
-                       "event": [torch.cuda.Event() for _ in range(self.n)], "next": 0}
-        r = self._r
-        k = r["next"]
-        r["next"] = (k + 1) % self.n
-        r["event"][k].synchronize()  # (returns at once for an event never recorded)
-        host = r["host"][k][:B]
-        host.numpy()[:] = rows
-        dev = torch.empty(B, self.width, dtype=torch.float64, device=self.device)
-        dev.copy_(host, non_blocking=True)
-        r["event"][k].record()
-        return host, dev
-
-
-class DeviceSplit:
+class DeviceSplit(ResidentSplit):
     """A KITTI split decoded once and held on the device: `DeviceSplit(root_or_split_file, mode)` resolves the split as build_batch does,
     checks the bytes it needs against `max_bytes` (default: half of the device's free memory) from the PNG headers alone, then decodes
     every frame with `min(workers, 16)` threads into one uint8 arena (`arena`: each frame (H, W, 3) RGB at a multiple of 16 bytes,
@@ -570,9 +527,6 @@ class DeviceSplit:
     upload of the draw table from a ring of pinned buffers and three launches (plan_batch, the image augmentation, the label encoder).
     `frame_info` knows every frame's true size, as the reference's dataset does; the path-based builder knows those of the batch's own
     frames only, so the two draw the same mixup partners when frames that share a calibration share a size."""
-
-    RING = 4  # pinned draw tables in flight
-    CHUNK = 256 << 20  # bytes of decoded frames per upload
 
     def __init__(self, root_or_split_file, mode="train", device="cuda", max_bytes=None, workers=8):
         import os
@@ -588,7 +542,7 @@ class DeviceSplit:
             raise Y3DError(f"DeviceSplit: workers = {workers}")
         if dev.index is None:
             dev = torch.device("cuda", torch.cuda.current_device())
-        self.device, self.mode = dev, mode
+        self.mode = mode
         self.data, self.ids = _split(root_or_split_file, mode)
         N = len(self.ids)
         if N < 1:
@@ -599,71 +553,38 @@ class DeviceSplit:
         for i in self.ids:
             with Image.open(path("image_2", i, "png")) as im:
                 self.wh.append((int(im.size[0]), int(im.size[1])))
-        size = np.array([w * h * 3 for w, h in self.wh], np.int64)
-        padded = (size + _ALIGN - 1) // _ALIGN * _ALIGN
-        self.offsets = np.concatenate(([0], np.cumsum(padded)[:-1])).astype(np.int64)
-        self.nbytes = int(padded.sum())
-        allowed = int(max_bytes) if max_bytes is not None else torch.cuda.mem_get_info(dev)[0] // 2
-        if self.nbytes > allowed:
-            raise Y3DError(f"DeviceSplit: the {N} decoded frames need {self.nbytes} bytes, {allowed} bytes are allowed (max_bytes)")
-        pool = ThreadPoolExecutor(max_workers=min(int(workers), 16))
-        try:
-            # labels and calibrations, both projections of every frame
-            def tables(pos):
-                P = read_calib(path("calib", self.ids[pos], "txt"))
-                return label_records(read_label(path("label_2", self.ids[pos], "txt"))), P, flip_calib(P, self.wh[pos])
+        self._layout(dev, [(h, w) for w, h in self.wh], max_bytes)
 
+        # labels and calibrations, both projections of every frame
+        def tables(pos):
+            P = read_calib(path("calib", self.ids[pos], "txt"))
+            return label_records(read_label(path("label_2", self.ids[pos], "txt"))), P, flip_calib(P, self.wh[pos])
+
+        with ThreadPoolExecutor(max_workers=min(int(workers), 16)) as pool:
             recs, self.P2_host, flipped = zip(*pool.map(tables, range(N)))
-            self.n_lines = [len(r) for r in recs]
-            self.cam = [(float(P[0, 2]), float(P[1, 2]), float(P[0, 0]), float(P[1, 1])) for P in self.P2_host]
-            span = np.zeros((N, 2), np.int32)
-            span[:, 1] = self.n_lines
-            span[1:, 0] = np.cumsum(self.n_lines)[:-1]
-            rec = np.concatenate(recs) if sum(self.n_lines) else np.zeros((1, _REC_W))
-            up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a)).to(device=dev, dtype=dt)
-            self.rec, self.rec_span = up(rec, torch.float64), up(span, torch.int32)
-            self.img_off = up(self.offsets, torch.int64)
-            self.frame_hw = up(np.array([(h, w) for w, h in self.wh], np.int32), torch.int32)
-            self.P2 = up(np.stack([np.stack((P.reshape(12), F.reshape(12))) for P, F in zip(self.P2_host, flipped)]).astype(np.float32), torch.float32)
-            self.mean_size = up(np.asarray(CLS_MEAN_SIZE, np.float64).reshape(-1, 3), torch.float64)
-            # the arena: runs of consecutive frames decoded into a pinned stage, one copy per run
-            self.arena = torch.empty(self.nbytes, dtype=torch.uint8, device=dev)
+        self.n_lines = [len(r) for r in recs]
+        self.cam = [(float(P[0, 2]), float(P[1, 2]), float(P[0, 0]), float(P[1, 1])) for P in self.P2_host]
+        self.rec = upload(np.concatenate(recs) if sum(self.n_lines) else np.zeros((1, _REC_W)), dev, torch.float64)
+        self.P2 = upload(np.stack([np.stack((P.reshape(12), F.reshape(12))) for P, F in zip(self.P2_host, flipped)]).astype(np.float32), dev,
+                         torch.float32)
+        self.mean_size = upload(np.asarray(CLS_MEAN_SIZE, np.float64).reshape(-1, 3), dev, torch.float64)
 
-            def decode(pos):
-                with Image.open(path("image_2", self.ids[pos], "png")) as im:
-                    px = np.array(im.convert("RGB"))
-                w, h = self.wh[pos]
-                if px.shape != (h, w, 3):
-                    raise Y3DError(f"DeviceSplit: frame {self.ids[pos]:06d} decodes to {px.shape}, its header said {(h, w, 3)}")
-                return px
+        def decode(pos):
+            with Image.open(path("image_2", self.ids[pos], "png")) as im:
+                return np.array(im.convert("RGB"))
 
-            fill_arena(self.arena, self.offsets, padded, decode, pool, self.CHUNK)
-        finally:
-            pool.shutdown()
-        self._ring = DrawRing(_DRAW_W, dev, self.RING)
+        self._fill(span_table(self.n_lines), decode, lambda pos: f"frame {self.ids[pos]:06d}", workers, _DRAW_W)
 
     def __len__(self):
         return len(self.ids)
-
-    def check_device(self, device):
-        d = torch.device(device)
-        if d.type != "cuda" or (d.index is not None and d.index != self.device.index):
-            raise Y3DError(f"build_batch: the split lives on {self.device}, a batch on {d} was asked for")
 
     def frame_info(self, pos):
         """sample_augment's frame_info: ((cu, cv, fu, fv), label lines, (W, H)), the true size for every position"""
         return self.cam[pos], self.n_lines[pos], self.wh[pos]
 
-    def frame(self, pos):
-        """the decoded frame at a dataset position: an (H, W, 3) uint8 view of the arena"""
-        w, h = self.wh[pos]
-        o = int(self.offsets[pos])
-        return self.arena[o:o + h * w * 3].view(h, w, 3)
-
     def build_batch(self, indices, args, mode="train", compact=False, img_mode="uint8", resolution=RESOLUTION):
         """`build_batch(path, indices, args, device, ...)` from the resident split: the same dictionary, bit for bit.  With compact=False
         nothing here waits for the device (but a ring buffer still in flight) and no file is opened."""
-        import numpy as np
         if getattr(args, "load_depth_maps", False):
             raise Y3DError("build_batch: depth maps (load_depth_maps) are not supported")
         if mode == "test":
@@ -673,13 +594,11 @@ class DeviceSplit:
         if B < 1 or any(not 0 <= p < N for p in indices):
             raise Y3DError(f"build_batch: {B} positions, all must lie in [0, {N})")
         draws = sample_augment(N, indices, self.frame_info, args, mode, MAX_OBJS, resolution)
-        rows = []
         for pos, d in zip(indices, draws):
             if d["mixed"] and self.wh[d["partner"]] != self.wh[pos]:
                 raise Y3DError(f"build_batch: mixup partner {d['partner']} of position {pos} has another size")
-            rows.append(np.concatenate(([pos, d["partner"], d["flip"], d["scale"]], d["trans"].reshape(6), d["trans_inv"].reshape(6))))
         with torch.cuda.device(self.device):
-            host, dev = self._ring.upload(rows)
+            host, dev = self._ring.upload(draw_table(indices, draws))
             plan = plan_batch(self, host, dev)
             W, H = int(resolution[0]), int(resolution[1])
             if img_mode == "float":
@@ -690,22 +609,8 @@ class DeviceSplit:
                                   plan["trans_inv"].data_ptr(), B, H, W, 0 if img_mode == "float" else 1, img.data_ptr(), ops.stream())
             packed = {"rec": self.rec, "img_i": plan["img_i"], "img_f": plan["img_f"], "mean_size": self.mean_size}
             lab = encode_labels(packed, resolution, args.min_depth_threshold, args.max_depth_threshold, bool(args.cam_dis), MAX_OBJS)
-        batch = {"img": img, "calib": lab["calib"],
-                 "info": [{"img_id": self.ids[p], "img_size": np.array(self.wh[p]), "trans_inv": d["trans_inv"]} for p, d in zip(indices, draws)],
-                 "im_file": [f"{self.ids[p]:06d}.txt" for p in indices], "ori_shape": [np.array(self.wh[p])[::-1] for p in indices],
-                 "ratio_pad": lab["ratio_pad"], "mean_sizes": self.mean_size, "mixed": plan["mixed"], "counts": lab["counts"]}
-        if compact:
-            batch.update(compact_labels(lab, lab["counts"].tolist(), [d["crop"] for d in draws], bool(args.cam_dis)))
-            del batch["counts"]
-        else:
-            batch.update({k: lab[k] for k in PER_BOX})
-        return batch
-
-    def epoch(self, batch, args, mode="train", shuffle=True, seed=0, drop_last=False, **kw):
-        """One epoch of batches: `build_batch` over `epoch_indices(len(self), batch, shuffle, seed, drop_last)`.  A build only enqueues
-        work on the current stream, so building the next batch already overlaps the step that consumes this one."""
-        for idx in epoch_indices(len(self), batch, shuffle, seed, drop_last):
-            yield self.build_batch(idx, args, mode=mode, **kw)
+        return _batch(img, lab, [self.ids[p] for p in indices], [self.wh[p] for p in indices], draws, self.mean_size, plan["mixed"],
+                      compact and (lambda counts: compact_labels(lab, counts, [d["crop"] for d in draws], bool(args.cam_dis))))
 
 
 def save_results(results, output_dir="./outputs", class_name=("Car", "Pedestrian", "Cyclist")):
@@ -756,7 +661,6 @@ def build_test_batch(root_or_split_file, indices, device, img_mode="uint8", reso
         info.append({"img_id": ids[pos], "img_size": img_size, "trans_inv": trans_inv})
     B = len(imgs)
     img = augment_images(imgs, [None] * B, [False] * B, [d["trans_inv"] for d in info], resolution, mode="float" if img_mode == "float" else "uint8")
-    up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a)).to(device=device, dtype=dt)
-    return {"img": img, "calib": up(np.array(calib, np.float64), torch.float64), "info": info, "im_file": [f"{d['img_id']:06d}.txt" for d in info],
-            "ori_shape": [d["img_size"][::-1] for d in info], "ratio_pad": up(np.stack(ratio_pad).astype(np.float64), torch.float64),
-            "P2": up(np.stack(P2s), torch.float32)}
+    return {"img": img, "calib": upload(np.array(calib, np.float64), device, torch.float64), "info": info,
+            "im_file": [f"{d['img_id']:06d}.txt" for d in info], "ori_shape": [d["img_size"][::-1] for d in info],
+            "ratio_pad": upload(np.stack(ratio_pad).astype(np.float64), device, torch.float64), "P2": upload(np.stack(P2s), device, torch.float32)}

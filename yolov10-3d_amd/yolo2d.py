@@ -34,6 +34,8 @@ import torch
 from . import loss as _loss
 from . import ops
 from ._lib import Y3DError, lib
+from .resident import ResidentSplit, check_plan, span_table
+from .resident import upload as _up
 
 IMG_FORMATS = {"bmp", "dng", "jpeg", "jpg", "mpo", "png", "tif", "tiff", "webp", "pfm"}  # data/utils.py
 # the 2D data hyper-parameters of cfg/default.yaml
@@ -369,11 +371,6 @@ def label_records(split, samples, rec_start):
     return li, lf
 
 
-def _up(a, device):
-    import numpy as np
-    return torch.from_numpy(np.ascontiguousarray(a)).to(device)
-
-
 def pack_images(imgs, rec_i, rec_f, lut, imgsz, device):
     """Host side of augment_images: the decoded (H, W, 3) uint8 device images of the pointer table and the three record arrays ->
     dict of device tensors (one upload each)"""
@@ -413,19 +410,35 @@ def augment_images(packed, mode="uint8"):
     return out
 
 
-def pack_labels(label_rows, lab_i, lab_f, device):
-    """Host side of encode_labels: the (n, 5) float32 label table and the two record arrays -> dict of device tensors"""
+def _label_table(label_rows, seg, lab_i, lab_f, device, whose):
+    """What both label packers end with: the (n, 5) float32 label table (one dummy row when it is empty) and the two record arrays go
+    to the device.  seg: (m, 2) int [first row, rows], every run of label rows the records name; all must lie inside the table."""
     import numpy as np
-    if torch.device(device).type != "cuda":
-        raise Y3DError("pack_labels: the label encoder runs on a HIP device (no host fallback)")
     rows = np.asarray(label_rows, np.float32).reshape(-1, 5)
     n = len(rows)
+    if (seg < 0).any() or (seg.sum(1)[seg[:, 1] > 0] > n).any():
+        raise Y3DError(f"{whose} label rows lie outside the label table")
+    return {"rec": _up(rows if n else np.zeros((1, 5), np.float32), device), "n_rec": n, "lab_i": _up(lab_i, device), "lab_f": _up(lab_f, device)}
+
+
+def _static_labels(packed, max_boxes, what):
+    """The unwritten static layout both label encoders fill, for packed labels that live on the device -> (cap, dict)"""
+    cap = _loss.check_max_boxes(max_boxes) or BASE_CAP
+    li = packed["lab_i"]
+    if not li.is_cuda or not packed["rec"].is_cuda or not packed["lab_f"].is_cuda:
+        raise Y3DError(f"{what}: the packed labels must live on a HIP device (no host fallback)")
+    B, dev = li.shape[0], li.device
+    return cap, {"cls": torch.empty(B * cap, 1, dtype=torch.float32, device=dev), "bboxes": torch.empty(B * cap, 4, dtype=torch.float32, device=dev),
+                 "batch_idx": torch.empty(B * cap, dtype=torch.float32, device=dev), "counts": torch.empty(B, dtype=torch.int32, device=dev)}
+
+
+def pack_labels(label_rows, lab_i, lab_f, device):
+    """Host side of encode_labels: the (n, 5) float32 label table and the two record arrays -> dict of device tensors"""
+    if torch.device(device).type != "cuda":
+        raise Y3DError("pack_labels: the label encoder runs on a HIP device (no host fallback)")
     if lab_i.shape[1:] != (_LAB_I,) or lab_f.shape != (lab_i.shape[0], _LAB_F):
         raise Y3DError("pack_labels: record arrays of the wrong shape")
-    seg = lab_i[:, :16].reshape(-1, 2)
-    if (seg < 0).any() or (seg.sum(1)[seg[:, 1] > 0] > n).any():
-        raise Y3DError("pack_labels: a tile's label rows lie outside the label table")
-    return {"rec": _up(rows if n else np.zeros((1, 5), np.float32), device), "n_rec": n, "lab_i": _up(lab_i, device), "lab_f": _up(lab_f, device)}
+    return _label_table(label_rows, lab_i[:, :16].reshape(-1, 2), lab_i, lab_f, device, "pack_labels: a tile's")
 
 
 def encode_labels(packed, imgsz, max_boxes=None):
@@ -433,14 +446,9 @@ def encode_labels(packed, imgsz, max_boxes=None):
     cap = max_boxes or 64 rows per image: `cls` (B*cap, 1) float32, `bboxes` (B*cap, 4) float32 xywh normalised, `batch_idx` (B*cap)
     float32 (-1 on unused rows, which are zeros and which `y3d_pad_targets` skips), `counts` (B,) int32: the true number of boxes of
     each image — one with more than cap keeps its first cap in the reference's order and shows the surplus here."""
-    cap = _loss.check_max_boxes(max_boxes) or BASE_CAP
+    cap, o = _static_labels(packed, max_boxes, "encode_labels")
     li = packed["lab_i"]
-    if not li.is_cuda or not packed["rec"].is_cuda or not packed["lab_f"].is_cuda:
-        raise Y3DError("encode_labels: the packed labels must live on a HIP device (no host fallback)")
-    B, dev = li.shape[0], li.device
-    o = {"cls": torch.empty(B * cap, 1, dtype=torch.float32, device=dev), "bboxes": torch.empty(B * cap, 4, dtype=torch.float32, device=dev),
-         "batch_idx": torch.empty(B * cap, dtype=torch.float32, device=dev), "counts": torch.empty(B, dtype=torch.int32, device=dev)}
-    lib().yolo2d_encode_labels(packed["rec"].data_ptr(), int(packed["n_rec"]), li.data_ptr(), packed["lab_f"].data_ptr(), B, int(imgsz), cap,
+    lib().yolo2d_encode_labels(packed["rec"].data_ptr(), int(packed["n_rec"]), li.data_ptr(), packed["lab_f"].data_ptr(), li.shape[0], int(imgsz), cap,
                                o["cls"].data_ptr(), o["bboxes"].data_ptr(), o["batch_idx"].data_ptr(), o["counts"].data_ptr(), ops.stream())
     return o
 
@@ -478,31 +486,42 @@ def build_batch(split, indices, args, device, mode="train", max_boxes=None, comp
     return _build_square_batch(split, indices, args, device, mode, max_boxes, compact, img_mode)
 
 
-def _build_square_batch(split, indices, args, device, mode, max_boxes, compact, img_mode):
-    """build_batch over a `Split`, through `split.decode`: the host builds the five record arrays, the pointer table and the label table
-    of the batch's own frames and uploads them.  (Over a `DeviceSplit` it opens no file either: `decode` is a view of the arena.)"""
+def _frame_tables(split, frames, device):
+    """The frames a host-built batch reads, sorted -> (slot: frame -> position in the pointer table, the decoded images in that order,
+    rec_start: frame -> first row of its labels in the batch's label table, that table)"""
     import numpy as np
-    samples = [sample_augment(split, i, args, mode) for i in indices]
-    frames = sorted({t["frame"] for x in samples for pre in (x["pre"], x["pre2"]) if pre is not None for t in pre["tiles"]})
     slot = {f: n for n, f in enumerate(frames)}
     imgs = [split.decode(f, device) for f in frames]
-    ri, rf, lut = image_records(samples, slot)
-    img = augment_images(pack_images(imgs, ri, rf, lut, split.imgsz, device), img_mode)
     rec_start, row = {}, 0
     for f in frames:
         rec_start[f] = row
         row += len(split.labels[f])
-    rows = np.concatenate([split.labels[f] for f in frames])
+    return slot, imgs, rec_start, np.concatenate([split.labels[f] for f in frames]) if frames else None  # (no frames: the packers refuse)
+
+
+def _batch(img, lab, im_files, ori_shapes, shape, ratio_pad, max_boxes, compact):
+    """The dictionary every 2D builder returns: the images, the label encoder's `lab`, and per image its file, its original (h, w), the
+    `shape` it was resized into and (rect batches, else None) its ratio_pad.  compact: the per-box keys ragged, not in the static layout."""
+    batch = {"img": img, "im_file": im_files, "ori_shape": ori_shapes, "resized_shape": [shape for _ in im_files]}
+    if ratio_pad is not None:
+        batch["ratio_pad"] = ratio_pad
+    batch["counts"] = lab["counts"]
+    batch.update(compact_labels(lab, lab["counts"].tolist(), max_boxes) if compact else {k: lab[k] for k in ("cls", "bboxes", "batch_idx")})
+    return batch
+
+
+def _build_square_batch(split, indices, args, device, mode, max_boxes, compact, img_mode):
+    """build_batch over a `Split`, through `split.decode`: the host builds the five record arrays, the pointer table and the label table
+    of the batch's own frames and uploads them.  (Over a `DeviceSplit` it opens no file either: `decode` is a view of the arena.)"""
+    samples = [sample_augment(split, i, args, mode) for i in indices]
+    frames = sorted({t["frame"] for x in samples for pre in (x["pre"], x["pre2"]) if pre is not None for t in pre["tiles"]})
+    slot, imgs, rec_start, rows = _frame_tables(split, frames, device)
+    ri, rf, lut = image_records(samples, slot)
+    img = augment_images(pack_images(imgs, ri, rf, lut, split.imgsz, device), img_mode)
     li, lf = label_records(split, samples, rec_start)
     lab = encode_labels(pack_labels(rows, li, lf, device), split.imgsz, max_boxes)
-    s = split.imgsz
-    batch = {"img": img, "im_file": [split.im_files[x["index"]] for x in samples], "ori_shape": [split.size(x["index"]) for x in samples],
-             "resized_shape": [(s, s) for _ in samples], "counts": lab["counts"]}
-    if compact:
-        batch.update(compact_labels(lab, lab["counts"].tolist(), max_boxes))
-    else:
-        batch.update({k: lab[k] for k in ("cls", "bboxes", "batch_idx")})
-    return batch
+    return _batch(img, lab, [split.im_files[x["index"]] for x in samples], [split.size(x["index"]) for x in samples],
+                  (split.imgsz, split.imgsz), None, max_boxes, compact)
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
@@ -641,27 +660,18 @@ def pack_letterbox_labels(label_rows, lab_i, lab_f, device):
     import numpy as np
     if torch.device(device).type != "cuda":
         raise Y3DError("pack_letterbox_labels: the label encoder runs on a HIP device (no host fallback)")
-    rows = np.asarray(label_rows, np.float32).reshape(-1, 5)
-    n = len(rows)
     lab_i, lab_f = np.ascontiguousarray(lab_i, dtype=np.int32), np.ascontiguousarray(lab_f, dtype=np.float32)
     if lab_i.ndim != 2 or lab_i.shape[1] != 2 or lab_f.shape != (lab_i.shape[0], 4) or not len(lab_i):
         raise Y3DError("pack_letterbox_labels: record arrays of the wrong shape")
-    if (lab_i < 0).any() or (lab_i.sum(1)[lab_i[:, 1] > 0] > n).any():
-        raise Y3DError("pack_letterbox_labels: an image's label rows lie outside the label table")
-    return {"rec": _up(rows if n else np.zeros((1, 5), np.float32), device), "n_rec": n, "lab_i": _up(lab_i, device), "lab_f": _up(lab_f, device)}
+    return _label_table(label_rows, lab_i, lab_i, lab_f, device, "pack_letterbox_labels: an image's")
 
 
 def letterbox_labels(packed, H, W, max_boxes=None):
     """The validation label chain of B samples + `collate_fn`, one HIP launch, no host synchronisation (capturable), in encode_labels'
     static layout of cap = max_boxes or 64 rows per image; normalised by the (H, W) canvas."""
-    cap = _loss.check_max_boxes(max_boxes) or BASE_CAP
+    cap, o = _static_labels(packed, max_boxes, "letterbox_labels")
     li = packed["lab_i"]
-    if not li.is_cuda or not packed["rec"].is_cuda or not packed["lab_f"].is_cuda:
-        raise Y3DError("letterbox_labels: the packed labels must live on a HIP device (no host fallback)")
-    B, dev = li.shape[0], li.device
-    o = {"cls": torch.empty(B * cap, 1, dtype=torch.float32, device=dev), "bboxes": torch.empty(B * cap, 4, dtype=torch.float32, device=dev),
-         "batch_idx": torch.empty(B * cap, dtype=torch.float32, device=dev), "counts": torch.empty(B, dtype=torch.int32, device=dev)}
-    lib().letterbox_labels(packed["rec"].data_ptr(), int(packed["n_rec"]), li.data_ptr(), packed["lab_f"].data_ptr(), B, int(H), int(W), cap,
+    lib().letterbox_labels(packed["rec"].data_ptr(), int(packed["n_rec"]), li.data_ptr(), packed["lab_f"].data_ptr(), li.shape[0], int(H), int(W), cap,
                            o["cls"].data_ptr(), o["bboxes"].data_ptr(), o["batch_idx"].data_ptr(), o["counts"].data_ptr(), ops.stream())
     return o
 
@@ -679,12 +689,8 @@ def rect_records(split, samples, slot, rec_start):
     return rec, li, lf
 
 
-def _build_rect_batch(split, indices, args, device, mode, max_boxes, compact, img_mode):
-    """`collate_fn([dataset[i] for i in indices])` of the validator's rect=True YOLODataset: all indices of one rect batch, letter-boxed
-    (ratio 1 after load_image's resize) into that batch's (H, W) canvas.  -> the keys of the square path, `resized_shape` = (H, W) per
-    image, and `ratio_pad` = ((h / h0, w / w0), (left, top)) per image as `BoxStats.update_2d` reads it.  img_mode "uint8":
-    (B, H, W, 3) uint8; "float": (B, 3, H, W) float32."""
-    import numpy as np
+def _rect_indices(split, indices, args, mode):
+    """What every rect builder checks first -> the indices as ints: a validation batch, not empty, all of one rect batch"""
     _check_args(args)
     if mode != "val":
         raise Y3DError(f"yolo2d: a RectSplit builds validation batches only (mode {mode!r}); rect training batches are not supported")
@@ -694,32 +700,29 @@ def _build_rect_batch(split, indices, args, device, mode, max_boxes, compact, im
     ks = {split.batch_of(i) for i in indices}
     if len(ks) != 1:
         raise Y3DError(f"yolo2d: indices of rect batches {sorted(ks)}: a rect batch has one shape, build them one at a time")
+    return indices
+
+
+def _build_rect_batch(split, indices, args, device, mode, max_boxes, compact, img_mode):
+    """`collate_fn([dataset[i] for i in indices])` of the validator's rect=True YOLODataset: all indices of one rect batch, letter-boxed
+    (ratio 1 after load_image's resize) into that batch's (H, W) canvas.  -> the keys of the square path, `resized_shape` = (H, W) per
+    image, and `ratio_pad` = ((h / h0, w / w0), (left, top)) per image as `BoxStats.update_2d` reads it.  img_mode "uint8":
+    (B, H, W, 3) uint8; "float": (B, 3, H, W) float32."""
+    indices = _rect_indices(split, indices, args, mode)
     samples = [rect_sample(split, i) for i in indices]
     H, W = samples[0]["canvas"]
-    frames = sorted(set(indices))
-    slot = {f: n for n, f in enumerate(frames)}
-    imgs = [split.decode(f, device) for f in frames]
-    rec_start, row = {}, 0
-    for f in frames:
-        rec_start[f] = row
-        row += len(split.labels[f])
+    slot, imgs, rec_start, rows = _frame_tables(split, sorted(set(indices)), device)
     rec, li, lf = rect_records(split, samples, slot, rec_start)
     img = letterbox_images(pack_letterbox(imgs, rec, H, W, device), img_mode)
-    lab = letterbox_labels(pack_letterbox_labels(np.concatenate([split.labels[f] for f in frames]), li, lf, device), H, W, max_boxes)
-    batch = {"img": img, "im_file": [split.im_files[i] for i in indices], "ori_shape": [(s["h0"], s["w0"]) for s in samples],
-             "resized_shape": [(H, W) for _ in samples], "ratio_pad": [s["ratio_pad"] for s in samples], "counts": lab["counts"]}
-    if compact:
-        batch.update(compact_labels(lab, lab["counts"].tolist(), max_boxes))
-    else:
-        batch.update({k: lab[k] for k in ("cls", "bboxes", "batch_idx")})
-    return batch
+    lab = letterbox_labels(pack_letterbox_labels(rows, li, lf, device), H, W, max_boxes)
+    return _batch(img, lab, [split.im_files[i] for i in indices], [(s["h0"], s["w0"]) for s in samples], (H, W),
+                  [s["ratio_pad"] for s in samples], max_boxes, compact)
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
 # the split resident on the device: decoded once, then a batch is the draws, one small upload and three launches
 # ------------------------------------------------------------------------------------------------------------------------------
 _DRAW_W, _DRAW_LAYER, _DRAW_TAIL = 56, 23, 46  # Y3D_YOLO2D_DRAW_W (include/y3d.h): two layers of 23, then the sample's own nine values
-_ALIGN = 16  # every frame starts on a multiple of 16 bytes of the arena (both image kernels read their sources byte by byte)
 PLAN_TABLES = (("rec_i", torch.int32, (_REC_I,)), ("rec_f", torch.float64, (_REC_F,)), ("lut", torch.uint8, (3, 256)),
                ("lab_i", torch.int32, (_LAB_I,)), ("lab_f", torch.float32, (_LAB_F,)))
 
@@ -757,30 +760,10 @@ def plan_batch(split, draws, draws_dev=None, out=None):
     positions outside the split are refused from the host table.  out: optionally the five output tensors (at least B rows each; the
     first B are written).  -> dict rec_i (B, 112) int32 with source index = dataset position, rec_f (B, 16) float64, lut (B, 3, 256)
     uint8, lab_i (B, 20) int32 with rows counted in `split.rec`, lab_f (B, 48) float32."""
-    host = torch.as_tensor(draws)
-    if host.dim() != 2 or host.shape[1] != _DRAW_W or host.dtype != torch.float64 or host.is_cuda or not host.is_contiguous():
-        raise Y3DError(f"plan_batch: the draws are a contiguous (B, {_DRAW_W}) float64 table on the host, got {tuple(host.shape)} {host.dtype}")
-    B, dev = host.shape[0], split.device
-    if draws_dev is None:
-        draws_dev = host.to(dev)
-    if draws_dev.shape != host.shape or draws_dev.dtype != torch.float64 or draws_dev.device != dev or not draws_dev.is_contiguous():
-        raise Y3DError("plan_batch: the device copy of the draws must match the host table and live on the split's device")
-    if out is None:
-        out = {k: torch.empty(B, *s, dtype=dt, device=dev) for k, dt, s in PLAN_TABLES}
-    for k, dt, s in PLAN_TABLES:
-        t = out[k]
-        if t.dtype != dt or t.device != dev or t.dim() != 1 + len(s) or t.shape[0] < B or tuple(t.shape[1:]) != s or not t.is_contiguous():
-            raise Y3DError(f"plan_batch: output {k} must be a contiguous ({B}+, {', '.join(map(str, s))}) {dt} tensor on {dev}")
+    host, draws_dev, out = check_plan(draws, _DRAW_W, split.device, PLAN_TABLES, draws_dev, out)
     lib().yolo2d_plan_batch(split.frame_hw.data_ptr(), split.rec_span.data_ptr(), len(split), split.imgsz, host.data_ptr(), draws_dev.data_ptr(),
-                            B, *[out[k].data_ptr() for k, _, _ in PLAN_TABLES], ops.stream())
+                            host.shape[0], *[out[k].data_ptr() for k, _, _ in PLAN_TABLES], ops.stream())
     return out
-
-
-def _hip_device(device, what):
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        raise Y3DError(f"{what}: the split is held on a HIP device, not {dev} (no host fallback)")
-    return dev
 
 
 def _decode_rgb(path):
@@ -791,70 +774,31 @@ def _decode_rgb(path):
         return np.array(ImageOps.exif_transpose(im).convert("RGB"))
 
 
-class _Resident:
+class _Resident(ResidentSplit):
     """What DeviceSplit and DeviceRectSplit share: the frames of a `Split` decoded once into one uint8 device arena, and the frame tables
     indexed by dataset position (the position in `im_files`): `arena`; `img_off` (N) int64; `frame_hw` (N, 2) int32 (h0, w0); `src` (N)
     int64 device pointers arena + offset, the pointer table both image kernels take with n_src = N; `rec` (R, 5) float32, all label rows
     in file order (one dummy row when there is none; `n_rec` = R); `rec_span` (N, 2) int32 (first row, rows)."""
 
-    RING = 4  # pinned draw tables in flight
-    CHUNK = 256 << 20  # bytes of decoded frames per upload
+    def _refusals(self, device, workers):
+        """what is refused before any file is read -> the torch.device"""
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise Y3DError(f"{type(self).__name__}: the split is held on a HIP device, not {dev} (no host fallback)")
+        if int(workers) < 1:
+            raise Y3DError(f"{type(self).__name__}: workers = {workers}")
+        return dev
 
     def _load(self, dev, max_bytes, workers):
         import numpy as np
-        from concurrent.futures import ThreadPoolExecutor
-        from .kitti import DrawRing, fill_arena
-        N = self.ni
         # sizes from the file headers (Split.size's EXIF rule), the budget before anything is decoded or allocated
-        hw = np.array([self.size(i) for i in range(N)], np.int64).reshape(N, 2)
-        size = hw[:, 0] * hw[:, 1] * 3
-        padded = (size + _ALIGN - 1) // _ALIGN * _ALIGN
-        self.offsets = np.concatenate(([0], np.cumsum(padded)[:-1])).astype(np.int64)
-        self.nbytes = int(padded.sum())
-        allowed = int(max_bytes) if max_bytes is not None else torch.cuda.mem_get_info(dev)[0] // 2
-        if self.nbytes > allowed:
-            raise Y3DError(f"{type(self).__name__}: the {N} decoded frames need {self.nbytes} bytes, {allowed} bytes are allowed (max_bytes)")
-        if dev.index is None:
-            dev = torch.device("cuda", torch.cuda.current_device())
-        self.device = dev
-        up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a)).to(device=dev, dtype=dt)
+        self._layout(dev, [self.size(i) for i in range(self.ni)], max_bytes)
         n_rows = [len(r) for r in self.labels]
-        span = np.zeros((N, 2), np.int32)
-        span[:, 1] = n_rows
-        span[1:, 0] = np.cumsum(n_rows)[:-1]
-        self.n_rec = int(sum(n_rows))
-        self.span_host = span
+        self.n_rec, self.span_host = int(sum(n_rows)), span_table(n_rows)
         rec = np.concatenate(self.labels).astype(np.float32).reshape(-1, 5) if self.n_rec else np.zeros((1, 5), np.float32)
-        self.rec, self.rec_span = up(rec, torch.float32), up(span, torch.int32)
-        self.img_off, self.frame_hw = up(self.offsets, torch.int64), up(hw, torch.int32)
-        # the arena: runs of consecutive frames decoded into a pinned stage, one copy per run
-        self.arena = torch.empty(self.nbytes, dtype=torch.uint8, device=dev)
-        self.src = up(self.arena.data_ptr() + self.offsets, torch.int64)
-
-        def decode(pos):
-            px = _decode_rgb(self.im_files[pos])
-            h, w = self._hw0[pos]
-            if px.shape != (h, w, 3):
-                raise Y3DError(f"{type(self).__name__}: {self.im_files[pos]} decodes to {px.shape}, its header said {(h, w, 3)}")
-            return px
-
-        pool = ThreadPoolExecutor(max_workers=min(int(workers), 16))
-        try:
-            fill_arena(self.arena, self.offsets, padded, decode, pool, self.CHUNK)
-        finally:
-            pool.shutdown()
-        self._ring = DrawRing(_DRAW_W, dev, self.RING)
-
-    def check_device(self, device):
-        d = torch.device(device)
-        if d.type != "cuda" or (d.index is not None and d.index != self.device.index):
-            raise Y3DError(f"build_batch: the split lives on {self.device}, a batch on {d} was asked for")
-
-    def frame(self, pos):
-        """the decoded frame at a dataset position: an (h0, w0, 3) uint8 view of the arena"""
-        h, w = self._hw0[pos]
-        o = int(self.offsets[pos])
-        return self.arena[o:o + h * w * 3].view(h, w, 3)
+        self.rec = _up(rec, self.device, torch.float32)
+        self._fill(self.span_host, lambda pos: _decode_rgb(self.im_files[pos]), lambda pos: self.im_files[pos], workers, _DRAW_W)
+        self.src = _up(self.arena.data_ptr() + self.offsets, self.device, torch.int64)
 
     def decode(self, i, device):
         """`Split.decode` without the file: the arena view of frame i"""
@@ -875,9 +819,7 @@ class DeviceSplit(_Resident, Split):
     view of the arena, so the host-built path (`_build_square_batch`) runs on a DeviceSplit as well, and opens no file either."""
 
     def __init__(self, img_dir_or_list, imgsz=640, batch=16, augment=True, device="cuda", max_bytes=None, workers=8):
-        dev = _hip_device(device, "DeviceSplit")
-        if int(workers) < 1:
-            raise Y3DError(f"DeviceSplit: workers = {workers}")
+        dev = self._refusals(device, workers)
         Split.__init__(self, img_dir_or_list, imgsz, batch, augment)
         self._load(dev, max_bytes, workers)
 
@@ -896,20 +838,8 @@ class DeviceSplit(_Resident, Split):
             plan = plan_batch(self, host, dev)
             img = augment_images({"src": self.src, "rec_i": plan["rec_i"], "rec_f": plan["rec_f"], "lut": plan["lut"], "imgsz": s}, img_mode)
             lab = encode_labels({"rec": self.rec, "n_rec": self.n_rec, "lab_i": plan["lab_i"], "lab_f": plan["lab_f"]}, s, max_boxes)
-        batch = {"img": img, "im_file": [self.im_files[x["index"]] for x in samples], "ori_shape": [self.size(x["index"]) for x in samples],
-                 "resized_shape": [(s, s) for _ in samples], "counts": lab["counts"]}
-        if compact:
-            batch.update(compact_labels(lab, lab["counts"].tolist(), max_boxes))
-        else:
-            batch.update({k: lab[k] for k in ("cls", "bboxes", "batch_idx")})
-        return batch
-
-    def epoch(self, batch, args, mode="train", shuffle=True, seed=0, drop_last=False, **kw):
-        """One epoch of batches: `build_batch` over `kitti.epoch_indices(len(self), batch, shuffle, seed, drop_last)`.  A build only
-        enqueues work on the current stream, so building the next batch already overlaps the step that consumes this one."""
-        from .kitti import epoch_indices
-        for idx in epoch_indices(len(self), batch, shuffle, seed, drop_last):
-            yield self.build_batch(idx, args, mode=mode, **kw)
+        return _batch(img, lab, [self.im_files[x["index"]] for x in samples], [self.size(x["index"]) for x in samples], (s, s), None,
+                      max_boxes, compact)
 
 
 class DeviceRectSplit(_Resident, RectSplit):
@@ -921,10 +851,7 @@ class DeviceRectSplit(_Resident, RectSplit):
     file.  Any other index list of one rect batch goes through the host-built path over the arena (`_build_rect_batch`)."""
 
     def __init__(self, img_dir_or_list, imgsz=640, batch=16, stride=32, pad=0.5, device="cuda", max_bytes=None, workers=8):
-        import numpy as np
-        dev = _hip_device(device, "DeviceRectSplit")
-        if int(workers) < 1:
-            raise Y3DError(f"DeviceRectSplit: workers = {workers}")
+        dev = self._refusals(device, workers)
         RectSplit.__init__(self, img_dir_or_list, imgsz, batch, stride, pad)
         self._load(dev, max_bytes, workers)
         state = random.getstate()  # rect_sample draws Format's bgr number; the load leaves the generator as it found it
@@ -939,23 +866,14 @@ class DeviceRectSplit(_Resident, RectSplit):
             H, W = s["canvas"]
             if min(r[1:5]) < 1 or r[5] < 0 or r[6] < 0 or r[5] + r[3] > H or r[6] + r[4] > W or W % 4:
                 raise Y3DError(f"DeviceRectSplit: {self.im_files[s['index']]} does not fit its {H} x {W} canvas")
-        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.device)
-        self.lb_rec, self.lb_lab_i, self.lb_lab_f = up(rec), up(li), up(lf)
+        self.lb_rec, self.lb_lab_i, self.lb_lab_f = _up(rec, self.device), _up(li, self.device), _up(lf, self.device)
 
     def build_batch(self, indices, args, mode="val", max_boxes=None, compact=False, img_mode="uint8"):
         """`build_batch(rect_split, indices, args, device, mode="val", ...)` from the resident split: the same dictionary, bit for bit"""
         if img_mode not in ("uint8", "float"):
             raise ValueError("img_mode must be 'uint8' or 'float'")
         _loss.check_max_boxes(max_boxes)
-        _check_args(args)
-        if mode != "val":
-            raise Y3DError(f"yolo2d: a RectSplit builds validation batches only (mode {mode!r}); rect training batches are not supported")
-        indices = [int(i) for i in indices]
-        if not indices:
-            raise Y3DError("yolo2d: an empty rect batch")
-        ks = {self.batch_of(i) for i in indices}
-        if len(ks) != 1:
-            raise Y3DError(f"yolo2d: indices of rect batches {sorted(ks)}: a rect batch has one shape, build them one at a time")
+        indices = _rect_indices(self, indices, args, mode)
         a, b = indices[0], indices[0] + len(indices)
         state = random.getstate()
         rgb = [random.uniform(0, 1) > 0.0 for _ in indices]  # Format's bgr draw of every sample, as rect_sample draws it
@@ -967,10 +885,5 @@ class DeviceRectSplit(_Resident, RectSplit):
         with torch.cuda.device(self.device):
             img = letterbox_images({"src": self.src, "rec": self.lb_rec[a:b], "H": H, "W": W}, img_mode)
             lab = letterbox_labels({"rec": self.rec, "n_rec": self.n_rec, "lab_i": self.lb_lab_i[a:b], "lab_f": self.lb_lab_f[a:b]}, H, W, max_boxes)
-        batch = {"img": img, "im_file": [self.im_files[i] for i in indices], "ori_shape": [(s["h0"], s["w0"]) for s in samples],
-                 "resized_shape": [(H, W) for _ in samples], "ratio_pad": [s["ratio_pad"] for s in samples], "counts": lab["counts"]}
-        if compact:
-            batch.update(compact_labels(lab, lab["counts"].tolist(), max_boxes))
-        else:
-            batch.update({k: lab[k] for k in ("cls", "bboxes", "batch_idx")})
-        return batch
+        return _batch(img, lab, [self.im_files[i] for i in indices], [(s["h0"], s["w0"]) for s in samples], (H, W),
+                      [s["ratio_pad"] for s in samples], max_boxes, compact)
