@@ -8,6 +8,7 @@ import pytest
 import torch
 
 from conftest import GOLDEN
+from kitti_eval_ref import bev_iou, iou3d   # the independent fp64 polygon clipping, shared with test_hip_kitti_eval_edges.py
 from test_kitti_eval_host import _line, fixture_annos
 
 pytestmark = pytest.mark.gpu
@@ -65,60 +66,6 @@ def test_repeated_runs_are_bit_identical():
         for k in ("precision", "orientation", "thresholds"):
             assert np.array_equal(a[k].view(np.int64), b[k].view(np.int64)), (metric, k)
         assert not a["recall"].any()
-
-
-# ---------------------------------------------------------------------------------------------------------------------------------
-# independent fp64 restatement: rectangle corners, Sutherland-Hodgman clipping, shoelace area
-# ---------------------------------------------------------------------------------------------------------------------------------
-def corners(x, z, l, w, ry):
-    c, s = math.cos(ry), math.sin(ry)
-    local = [(-l / 2, -w / 2), (-l / 2, w / 2), (l / 2, w / 2), (l / 2, -w / 2)]
-    return [(c * u + s * v + x, -s * u + c * v + z) for u, v in local]
-
-
-def shoelace(p):
-    return 0.5 * sum(p[i][0] * p[(i + 1) % len(p)][1] - p[(i + 1) % len(p)][0] * p[i][1] for i in range(len(p)))
-
-
-def clip(subject, clipper):
-    if shoelace(clipper) < 0:
-        clipper = clipper[::-1]
-    out = subject
-    for i in range(len(clipper)):
-        a, b = clipper[i], clipper[(i + 1) % len(clipper)]
-        side = lambda p: (b[0] - a[0]) * (p[1] - a[1]) - (b[1] - a[1]) * (p[0] - a[0])
-        inp, out = out, []
-        for j in range(len(inp)):
-            p, q = inp[j], inp[(j + 1) % len(inp)]
-            sp, sq = side(p), side(q)
-            if sp >= 0:
-                out.append(p)
-            if (sp >= 0) != (sq >= 0):
-                t = sp / (sp - sq)
-                out.append((p[0] + t * (q[0] - p[0]), p[1] + t * (q[1] - p[1])))
-        if not out:
-            return []
-    return out
-
-
-def inter_fp64(a, b):
-    p = clip(corners(*a), corners(*b))
-    return abs(shoelace(p)) if len(p) >= 3 else 0.0
-
-
-def bev_iou(a, b):
-    i = inter_fp64(a, b)
-    return i / (a[2] * a[3] + b[2] * b[3] - i)
-
-
-def iou3d(g, d):
-    """g, d = (x, y, z, l, h, w, ry), y the bottom face (camera frame)"""
-    i = inter_fp64((g[0], g[2], g[3], g[5], g[6]), (d[0], d[2], d[3], d[5], d[6]))
-    iy = min(g[1], d[1]) - max(g[1] - g[4], d[1] - d[4])
-    if iy <= 0 or i <= 0:
-        return 0.0
-    v = i * iy
-    return v / (g[3] * g[4] * g[5] + d[3] * d[4] * d[5] - v)
 
 
 def annos_of(boxes, score=False):
