@@ -568,6 +568,39 @@ int y3d_predict3d_rows(const float* preds, int B, int K, const double* calib, co
                        int n_cls, double* rows, double* corners3d, double* corners_img, int* counts, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Drawing 3D predictions (draw3d.hip; plot.py): box wireframes over the camera image and filled boxes on a bird's-eye-view map, the
+ * pictures of KITTIVisualizer.plot_preds / plot_bev (utils/plotting.py:1280-1411) with exact coverage rules in place of OpenCV's
+ * anti-aliased strokes.  All geometry is f64 with FMA contraction off, every sum evaluated left to right as written; pixel (x, y) is
+ * the point (x, y).  Within one call the primitive with the LOWER index wins a pixel; a primitive with a non-finite coordinate is
+ * skipped; the result depends on the inputs alone.  No entry allocates or synchronises.
+ *   segment a -> b, thickness t, r2 = (t/2)(t/2), pixel p: d = b - a, e = p - a, len2 = d.x d.x + d.y d.y, dot = e.x d.x + e.y d.y;
+ *     dot <= 0: covered iff e.x e.x + e.y e.y <= r2; dot >= len2: the same with p - b; else c = d.x e.y - d.y e.x, covered iff
+ *     c c <= r2 len2 (no division, no square root; len2 == 0 is a disc).
+ *   quad q0..q3: E_i = (q_{i+1} - q_i) x (p - q_i) = d_i.x (p.y - q_i.y) - d_i.y (p.x - q_i.x); covered iff all four E_i >= 0 or all
+ *     four <= 0.  A quad with (q1 - q0) x (q2 - q0) + (q2 - q0) x (q3 - q0) == 0 (its doubled signed area) is skipped.
+ * The raster kernels are exact for coordinates up to 1e12 in magnitude.
+ * ---------------------------------------------------------------------------------------------- */
+/* corners3d (B, K, 8, 3), rows (B, K, 14), counts (B) as y3d_predict3d_rows writes them; P2 (B, 12); affine (B, 6) or NULL; palette
+ * (n_pal, 3) u8 -> segs (B, K * 14, 4) f64 [ax, ay, bx, by], seg_rgb (B, K * 14, 4) u8 [r, g, b, 0].  Box k owns slots k * 14 + j,
+ * j = bottom face 0-1 1-2 2-3 3-0, top face 4-5 5-6 6-7 7-4, uprights 0-4 1-5 2-6 3-7, front-face diagonals 0-5 1-4.  Per endpoint
+ * U = ((P0 x + P1 y) + P2 z) + P3 (V, W from rows 1, 2 of P2); both W < near_w: dropped; one W < near_w: that endpoint A becomes
+ * A + s (B - A) in (U, V, W), s = (near_w - W_A) / (W_B - W_A); u = U / W, v = V / W; then u' = (A00 u + A01 v) + A02,
+ * v' = (A10 u + A11 v) + A12.  Dropped segments and every slot of a box k >= counts[b] are NaN (those boxes' colours 0).  Colour:
+ * palette[clamp((int)rows[b, k, 0], 0, n_pal - 1)], a NaN class taking entry 0; rows may be NULL (every box takes entry 0).  K may be 0. */
+int y3d_box3d_segments(const double* corners3d, const double* rows, const int* counts, int B, int K, const double* P2, const double* affine,
+                       const unsigned char* palette, int n_pal, double near_w, double* segs, unsigned char* seg_rgb, void* stream);
+/* -> quads (B, K, 4, 2) f64: the bottom face's corners 0..3 as (cx + scale x, cy - scale z); quad_rgb (B, K, 4) u8 as above */
+int y3d_box3d_bev_quads(const double* corners3d, const double* rows, const int* counts, int B, int K, const unsigned char* palette,
+                        int n_pal, double scale, double cx, double cy, double* quads, unsigned char* quad_rgb, void* stream);
+/* canvas (B, H, W, 3) u8, contiguous, painted in place: only covered pixels are stored.  Image b takes its first min(nseg[b], S)
+ * segments (all S with nseg NULL) of segs (B, S, 4) / seg_rgb (B, S, 4).  thickness finite and > 0.  The canvas may overlap no input. */
+int y3d_draw_segments(unsigned char* canvas, int B, int H, int W, const double* segs, const unsigned char* seg_rgb, const int* nseg, int S,
+                      double thickness, void* stream);
+/* the same with filled convex quads: quads (B, Q, 4, 2) f64, quad_rgb (B, Q, 4) u8, nquad (B) or NULL */
+int y3d_draw_quads(unsigned char* canvas, int B, int H, int W, const double* quads, const unsigned char* quad_rgb, const int* nquad, int Q,
+                   void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * KITTI AP evaluation (kitti_eval.hip) — the evaluator behind KITTIDataset.get_stats (data/datasets/kitti.py:444-450):
  * eval_from_scrach / get_official_eval_result (data/datasets/kitti_eval.py:1268-1336, :1075-1165).
  * Boxes are packed per image, images back to back: gt / dt (N, 16) fp32 records

@@ -17,6 +17,7 @@ coordinates and their projections out.
     predictor = predict.Predictor3d(model, conf=0.25)
     dets = predictor([rgb0, rgb1], [P2_0, P2_1])   # list of {"rows" (n_i, 14), "corners3d" (n_i, 8, 3), "corners_img" (n_i, 8, 2)} float64
     results = predictor.predict_split(kitti_root, [0, 1, 2], out_dir="runs")   # the KITTI test split -> runs/preds/000000.txt ...
+    pictures, bev = predictor.annotate([rgb0, rgb1], [P2_0, P2_1], bev=True)    # the boxes drawn over the images, and from above (plot.py)
 
 The host computes the reference's unaugmented sample (data/datasets/kitti.py:130-135, :192, :404): the crop matrix of the whole image,
 `ratio = resolution / img_size`, the six calibration constants.  The device does `y3d_kitti_image_aug` (Pillow's affine resize), the
@@ -309,6 +310,55 @@ class Predictor3d:
         if static:
             return rows, c3, ci, counts
         return [{"rows": rows[b, :n], "corners3d": c3[b, :n], "corners_img": ci[b, :n]} for b, n in enumerate(counts.tolist())]
+
+    def annotate(self, images, P2s, results=None, bev=False, thickness=2):
+        """the box wireframes over the original images (plot.draw_boxes3d): images and P2s as `__call__` takes them,
+        results what `__call__` returned for them, in either form (None: the predictor runs).  The images are grouped by shape and
+        every group is uploaded, drawn and read back once; the caller's arrays and tensors are left as they are.
+        -> a list of (h, w, 3) uint8 numpy arrays, and with bev=True (that list, the BEV maps (B, 600, 1200, 3) uint8 numpy)."""
+        import numpy as np
+        from . import plot
+        if results is None:
+            results = self(images, P2s, static=True)
+        dev = next(self.model.parameters()).device
+        if dev.type != "cuda":
+            raise Y3DError("predict3d: the model must live on a HIP device (no host fallback)")
+        B = len(images)
+        if isinstance(results, (list, tuple)) and len(results) == 4 and torch.is_tensor(results[0]):
+            rows, c3, _, counts = results
+        else:  # the list form: pad to the longest image
+            if len(results) != B:
+                raise Y3DError(f"annotate: {B} images but results for {len(results)}")
+            K = max([int(d["rows"].shape[0]) for d in results] + [1])
+            rows, c3 = torch.zeros(B, K, 14, dtype=torch.float64, device=dev), torch.zeros(B, K, 8, 3, dtype=torch.float64, device=dev)
+            for b, d in enumerate(results):
+                n = int(d["rows"].shape[0])
+                rows[b, :n], c3[b, :n] = d["rows"].to(dev), d["corners3d"].to(dev)
+            counts = torch.tensor([int(d["rows"].shape[0]) for d in results], dtype=torch.int32).to(dev)
+        if rows.shape[0] != B or len(P2s) != B:
+            raise Y3DError(f"annotate: {B} images, {len(P2s)} P2 matrices and results for {rows.shape[0]} images")
+        P = np.stack([np.asarray(p.cpu() if torch.is_tensor(p) else p, np.float32).reshape(3, 4) for p in P2s]).astype(np.float64)
+        P = torch.from_numpy(P).to(dev)
+        groups = {}
+        for b, im in enumerate(images):
+            groups.setdefault(tuple(int(v) for v in im.shape), []).append(b)
+        out = [None] * B
+        for shape, idx in groups.items():
+            u8 = lambda im: im.dtype == (torch.uint8 if torch.is_tensor(im) else np.uint8)
+            if len(shape) != 3 or shape[2] != 3 or not all(u8(images[b]) for b in idx):
+                raise Y3DError("annotate: images must be (h, w, 3) uint8")
+            if torch.is_tensor(images[idx[0]]):
+                canvas = torch.stack([images[b].to(dev) for b in idx]).contiguous()
+            else:
+                canvas = torch.from_numpy(np.ascontiguousarray(np.stack([images[b] for b in idx]))).to(dev)
+            sel = torch.tensor(idx, dtype=torch.int64).to(dev)
+            plot.draw_boxes3d(canvas, c3.index_select(0, sel), rows.index_select(0, sel), counts.index_select(0, sel), P.index_select(0, sel),
+                              thickness=thickness)
+            for b, pic in zip(idx, canvas.cpu().numpy()):
+                out[b] = pic
+        if not bev:
+            return out
+        return out, plot.draw_bev(c3, rows, counts).cpu().numpy()
 
     def predict_split(self, root_or_split_file, indices, out_dir=None):
         """the KITTI test split: `kitti.build_test_batch` -> the predictor -> `kitti_results`; with out_dir, `kitti.save_results` writes
