@@ -566,6 +566,26 @@ int y3d_predict_rows(const float* preds, const float* meta, float conf, const in
 int y3d_predict3d_rows(const float* preds, int B, int K, const double* calib, const double* P2, const double* ratio,
                        const double* inv_trans, const double* mean_size, int nc, int use_camera_dis, double conf, const int* classes,
                        int n_cls, double* rows, double* corners3d, double* corners_img, int* counts, void* stream);
+/* The labels of a batch back to 3D boxes (decode_labels.hip): KITTIDataset.decode_batch (data/datasets/kitti.py:469-513, the same in
+ * waymo.py and omni3d.py) with the corners and projection of y3d_predict3d_rows, one single-wave workgroup per image.  Per-box inputs,
+ * N rows each, in the dtypes of y3d_kitti_encode_labels: cls int64, bboxes (N, 4) f64 xywh in [0, 1], center_3d (N, 2) f64,
+ * size_3d (N, 3) f64 residuals, depth f64, heading_bin int64, heading_res f64, batch_idx f32.  Layout: with counts_in (B) int32 the static
+ * one (N = B * max_objs, image b owns rows [b * max_objs, b * max_objs + min(counts_in[b], max_objs)); batch_idx is not read); with
+ * counts_in NULL the ragged one of collate_fn (image b owns the rows with batch_idx == b, in batch order; N may be 0).
+ * Per image: ori_shape (B, 2) f64 (height, width); calib (B, 6) = (cu, cv, fu, fv, tx, ty) of the original image; ratio = ratio_pad
+ * as (B, 2, 2) (ratio_pitch 4) or (B, 2) (ratio_pitch 2); trans_inv (B, 2, 3) or NULL; P2 (B, 12) or NULL (then corners_img is NULL
+ * too and nothing is projected).  undo_augment: the centre goes through trans_inv (rounded to float32 first, as affine_transform
+ * does), which must then be given; otherwise it is divided by the ratio.  mean_size (nc, 3).
+ * For the j-th owned row of image b, j < R: rows[b, j, 0:14] f64 [cls, alpha, x1, y1, x2, y2, h, w, l, x, y, z, ry, 1]; corners3d
+ * [b, j, 8, 3] and corners_img [b, j, 8, 2] as y3d_predict3d_rows writes them.  counts[b] = min(owned rows, R); slots behind are zeros.
+ * A class outside [0, nc) stays in column 0 and takes the nearest table entry's size, as y3d_kitti_decode treats it.  The entry
+ * refuses NULL or misaligned outputs (16 bytes; counts 4), R < 1, and any output whose byte range overlaps an input's or another
+ * output's.  It neither allocates nor synchronises. */
+int y3d_decode_labels(const int64_t* cls, const double* bboxes, const double* center_3d, const double* size_3d, const double* depth,
+                      const int64_t* heading_bin, const double* heading_res, const float* batch_idx, const int* counts_in, int N, int max_objs,
+                      int B, const double* ori_shape, const double* calib, const double* ratio, int ratio_pitch, const double* trans_inv,
+                      const double* P2, const double* mean_size, int nc, int use_camera_dis, int undo_augment, int R, double* rows,
+                      double* corners3d, double* corners_img, int* counts, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Drawing 3D predictions (draw3d.hip; plot.py): box wireframes over the camera image and filled boxes on a bird's-eye-view map, the

@@ -1,16 +1,76 @@
 // One row of the KITTI decode (data/datasets/kitti.py:519-576), shared by kitti_decode_kernel (post.hip) and predict3d_rows_kernel
-// (predict3d.hip) so that both compute the same bits.  The reference promotes the float32 predictions to float64 through the
+// (predict3d.hip) so that both compute the same bits; its back-projection, alpha2ry and the box corners are functions of their own, which
+// the label decode (decode_labels.hip) shares.  The reference promotes the float32 predictions to float64 through the
 // calibration constants; the float32 steps (heading angle, sigmoid, exp) are kept in float32 here as there; the size is a float64 sum stored as float32.  The
 // library is built with contraction off: the order of the operations below is the result.
 #pragma once
 #include "common.h"
+
+// Calibration.img_to_rect (kitti_utils.py:241-251) or, with use_camera_dis, camera_dis_to_rect (:286-299): the pixel (u, v) of the
+// original image at `depth` (the rect z, or the distance to the camera) -> the point (lx, ly, lz) in the rectified camera frame
+__device__ __forceinline__ void kitti_pixel_to_rect(double u, double v, double depth, const double* __restrict__ calib, int use_camera_dis,
+                                                    double& lx, double& ly, double& lz) {
+  const double cu = calib[0], cv = calib[1], fu = calib[2], fv = calib[3], tx = calib[4], ty = calib[5];
+  if (use_camera_dis) {
+    const double fd = sqrt((u - cu) * (u - cu) + (v - cv) * (v - cv) + fu * fu);
+    lx = ((u - cu) * depth) / fd + tx;
+    ly = ((v - cv) * depth) / fd + ty;
+    lz = sqrt(depth * depth - lx * lx - ly * ly);
+  } else {
+    lx = ((u - cu) * depth) / fu + tx;
+    ly = ((v - cv) * depth) / fv + ty;
+    lz = depth;
+  }
+}
+
+// Calibration.alpha2ry (kitti_utils.py:311-325) at the pixel column xc
+__device__ __forceinline__ double kitti_alpha2ry(double alpha, double xc, double cu, double fu) {
+  const double PI_D = 3.14159265358979323846;
+  double ry = alpha + atan2(xc - cu, fu);
+  if (ry > PI_D) ry -= 2 * PI_D;
+  if (ry < -PI_D) ry += 2 * PI_D;
+  return ry;
+}
+
+// Object3d.generate_corners3d (kitti_utils.py:98-114) from a decoded row's h, w, l, (x, y, z), ry, y the bottom face:
+//   xc = (l/2, l/2, -l/2, -l/2) twice, yc = (0, 0, 0, 0, -h, -h, -h, -h), zc = (w/2, -w/2, -w/2, w/2) twice
+//   X = cos(ry) xc + sin(ry) zc + x,  Y = yc + y,  Z = -sin(ry) xc + cos(ry) zc + z
+// and, when P (the 3 x 4 projection, 12 doubles) is given, Calibration.corners3d_to_img_boxes' boxes_corner (:266-284), divided whatever
+// the sign.  The eight corners are unrolled: no run-time indexed private array, so no scratch.  P == nullptr leaves ci untouched.
+__device__ __forceinline__ void kitti_box_corners(double h, double w, double l, double x, double y, double z, double ry,
+                                                  const double* __restrict__ P, double (&c3)[24], double (&ci)[16]) {
+  const double hl = l / 2, hw = w / 2;
+  const double cs = cos(ry), sn = sin(ry);
+  double p00 = 0, p01 = 0, p02 = 0, p03 = 0, p10 = 0, p11 = 0, p12 = 0, p13 = 0, p20 = 0, p21 = 0, p22 = 0, p23 = 0;
+  if (P) {
+    p00 = P[0]; p01 = P[1]; p02 = P[2]; p03 = P[3]; p10 = P[4]; p11 = P[5]; p12 = P[6]; p13 = P[7]; p20 = P[8]; p21 = P[9]; p22 = P[10];
+    p23 = P[11];
+  }
+#pragma unroll
+  for (int c = 0; c < 8; ++c) {
+    const double xc = (c & 2) ? -hl : hl;
+    const double zc = ((c & 3) == 0 || (c & 3) == 3) ? hw : -hw;
+    const double yc = c < 4 ? 0.0 : -h;
+    const double X = (cs * xc + sn * zc) + x;
+    const double Y = yc + y;
+    const double Z = (-sn * xc + cs * zc) + z;
+    c3[c * 3 + 0] = X;
+    c3[c * 3 + 1] = Y;
+    c3[c * 3 + 2] = Z;
+    if (P) {
+      const double d = ((X * p20 + Y * p21) + Z * p22) + p23;
+      ci[c * 2 + 0] = (((X * p00 + Y * p01) + Z * p02) + p03) / d;
+      ci[c * 2 + 1] = (((X * p10 + Y * p11) + Z * p12) + p13) / d;
+    }
+  }
+}
 
 // r: the row's 37 float32 values; calib: the image's (cu, cv, fu, fv, tx, ty); rw, rh: its ratio; t: its (2, 3) inverse affine or
 // nullptr (the fixed 1242/1280, 375/384 rescale); o: [cls, alpha, x1, y1, x2, y2, h, w, l, x, y, z, ry, score]
 __device__ __forceinline__ void kitti_decode_row(const float* __restrict__ r, const double* __restrict__ calib, double rw, double rh,
                                                  const double* __restrict__ t, const double* __restrict__ mean_size, int nc,
                                                  int use_camera_dis, double (&o)[14]) {
-  const double cu = calib[0], cv = calib[1], fu = calib[2], fv = calib[3], tx = calib[4], ty = calib[5];
+  const double cu = calib[0], fu = calib[2];
   int cid = (int)r[36];
   const int cm = cid < 0 ? 0 : (cid >= nc ? nc - 1 : cid);  // the reference would raise on a label outside the mean-size table
   // heading: first maximum of the 12 bin logits, residual of that bin (decode_helper.py:12-18, float32)
@@ -38,21 +98,9 @@ __device__ __forceinline__ void kitti_decode_row(const float* __restrict__ r, co
     v = (double)((r[5] * 375.f) / 384.f);
   }
   double lx, ly, lz;
-  if (use_camera_dis) {  // kitti_utils.py:286-299
-    const double fd = sqrt((u - cu) * (u - cu) + (v - cv) * (v - cv) + fu * fu);
-    lx = ((u - cu) * depth) / fd + tx;
-    ly = ((v - cv) * depth) / fd + ty;
-    lz = sqrt(depth * depth - lx * lx - ly * ly);
-  } else {               // kitti_utils.py:241-251
-    lx = ((u - cu) * depth) / fu + tx;
-    ly = ((v - cv) * depth) / fv + ty;
-    lz = depth;
-  }
+  kitti_pixel_to_rect(u, v, depth, calib, use_camera_dis, lx, ly, lz);
   ly += (double)h / 2;
-  const double PI_D = 3.14159265358979323846;
-  double ry = alpha + atan2(xc - cu, fu);  // kitti_utils.py:311-325
-  if (ry > PI_D) ry -= 2 * PI_D;
-  if (ry < -PI_D) ry += 2 * PI_D;
+  const double ry = kitti_alpha2ry(alpha, xc, cu, fu);
   const float sg = 1.f / (1.f + expf(-r[35]));
   const double score = (double)sg * sigma;
   o[0] = (double)cid; o[1] = alpha; o[2] = x1; o[3] = y1; o[4] = x2; o[5] = y2; o[6] = (double)h; o[7] = (double)w; o[8] = (double)l;

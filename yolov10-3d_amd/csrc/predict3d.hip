@@ -8,9 +8,8 @@
 //            (int)preds[.., 36] is in it (models/yolov10_3D/predict.py:23-25)
 //   compact  survivors keep their input (score) order: ballot + popcount within a wave, an LDS prefix over the four waves, a running
 //            base across chunks (the scheme of predict_rows_kernel, letterbox.hip)
-//   corners  Object3d.generate_corners3d (kitti_utils.py:98-114) in float64 from the row's own h, w, l, (x, y, z), ry, y the bottom face:
-//              xc = (l/2, l/2, -l/2, -l/2) twice, yc = (0, 0, 0, 0, -h, -h, -h, -h), zc = (w/2, -w/2, -w/2, w/2) twice
-//              X = cos(ry) xc + sin(ry) zc + x,  Y = yc + y,  Z = -sin(ry) xc + cos(ry) zc + z
+//   corners  kitti_row.h's kitti_box_corners: Object3d.generate_corners3d (kitti_utils.py:98-114) in float64 from the row's own h, w, l,
+//            (x, y, z), ry, y the bottom face, and
 //   project  Calibration.corners3d_to_img_boxes' boxes_corner (kitti_utils.py:266-284) with the full 3 x 4 P2:
 //              (P2[0] . (X, Y, Z, 1) / P2[2] . (X, Y, Z, 1),  P2[1] . (X, Y, Z, 1) / P2[2] . (X, Y, Z, 1)), divided whatever the sign
 //
@@ -72,26 +71,8 @@ __global__ void __launch_bounds__(256) predict3d_rows_kernel(const float* __rest
       const size_t j = (size_t)(base + before + rank);
 #pragma unroll
       for (int i = 0; i < 7; ++i) orow[j * 7 + i] = make_double2(v[2 * i], v[2 * i + 1]);
-      const double hl = v[8] / 2, hw = v[7] / 2, h = v[6];
-      const double cs = cos(v[12]), sn = sin(v[12]);
-      const double p00 = P[0], p01 = P[1], p02 = P[2], p03 = P[3], p10 = P[4], p11 = P[5], p12 = P[6], p13 = P[7], p20 = P[8],
-                   p21 = P[9], p22 = P[10], p23 = P[11];
       double c3[24], ci[16];
-#pragma unroll
-      for (int c = 0; c < 8; ++c) {
-        const double xc = (c & 2) ? -hl : hl;
-        const double zc = ((c & 3) == 0 || (c & 3) == 3) ? hw : -hw;
-        const double yc = c < 4 ? 0.0 : -h;
-        const double X = (cs * xc + sn * zc) + v[9];
-        const double Y = yc + v[10];
-        const double Z = (-sn * xc + cs * zc) + v[11];
-        c3[c * 3 + 0] = X;
-        c3[c * 3 + 1] = Y;
-        c3[c * 3 + 2] = Z;
-        const double d = ((X * p20 + Y * p21) + Z * p22) + p23;
-        ci[c * 2 + 0] = (((X * p00 + Y * p01) + Z * p02) + p03) / d;
-        ci[c * 2 + 1] = (((X * p10 + Y * p11) + Z * p12) + p13) / d;
-      }
+      kitti_box_corners(v[6], v[7], v[8], v[9], v[10], v[11], v[12], P, c3, ci);
 #pragma unroll
       for (int i = 0; i < 12; ++i) oc3[j * 12 + i] = make_double2(c3[2 * i], c3[2 * i + 1]);
 #pragma unroll

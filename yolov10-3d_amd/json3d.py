@@ -180,6 +180,19 @@ def compact_labels(static, counts, use_camera_dis=False, max_objs=MAX_OBJS, data
     return out
 
 
+def decode_batch_device(batch, calibs, P2=None, undo_augment=True, dataset="waymo", use_camera_dis=False, cls_mean_size=None):
+    """`kitti.decode_batch_device` with the dataset's mean sizes (`CLS_MEAN_SIZE[dataset]`): waymo.py's and omni3d.py's `decode_batch`
+    are copies of KITTI's.  calibs: the original images' six constants (`Validator3d._dataset` gives them from the split's P2)."""
+    _dataset_mode(dataset)
+    return kitti.decode_batch_device(batch, calibs, P2, undo_augment, CLS_MEAN_SIZE[dataset] if cls_mean_size is None else cls_mean_size, use_camera_dis)
+
+
+def decode_batch(batch, calibs, undo_augment=True, dataset="waymo", use_camera_dis=False, cls_mean_size=None):
+    """`kitti.decode_batch` with the dataset's mean sizes -> {im_file: [row lists]} after one read-back"""
+    _dataset_mode(dataset)
+    return kitti.decode_batch(batch, calibs, undo_augment, CLS_MEAN_SIZE[dataset] if cls_mean_size is None else cls_mean_size, use_camera_dis)
+
+
 _SPLITS = {}
 
 

@@ -5,7 +5,8 @@ from `_prepare_preds` (models/yolov10_3D/val.py:210-214) on CPU with a python lo
 residual -> alpha, size residual + class mean size, centre back-projection through the (inverse-affine'd) calibration, rotation_y,
 score = sigmoid(cls) * exp(-depth log-variance), threshold.  Here it is one launch over all B*K rows (`y3d_kitti_decode`).
 
-Further down: the one-to-many depth fusion, the image and label sides of the training / validation batches (`build_batch`), the same
+Further down: the labels of a built batch back to 3D boxes (`decode_batch_device`, `decode_batch`: the reference's `decode_batch`,
+one launch of `y3d_decode_labels`), the one-to-many depth fusion, the image and label sides of the training / validation batches (`build_batch`), the same
 batches from a split decoded once and kept on the device (`DeviceSplit`, `plan_batch`, `epoch_indices`), the unlabelled test split
 (`build_test_batch`, which `predict.Predictor3d.predict_split` reads) and `save_results`, the writer of the files a KITTI submission
 and `kitti_eval.eval_from_scratch` read.
@@ -70,6 +71,188 @@ def decode_preds(preds, calibs, im_files, ratio_pad, inv_trans, undo_augment=Tru
 def decode_preds_eval(preds, calibs, im_files, ratio_pad, inv_trans, undo_augment=True, threshold=0.001, **kw):
     """kitti.py:515-517"""
     return decode_preds(preds, calibs, im_files, ratio_pad, inv_trans, undo_augment=undo_augment, threshold=threshold, **kw)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# the labels of a batch back to 3D boxes: KITTIDataset.decode_batch (data/datasets/kitti.py:469-513) on the device
+# ------------------------------------------------------------------------------------------------------------------------------
+_LABEL_KEYS = ("cls", "bboxes", "center_3d", "size_3d", "depth", "heading_bin", "heading_res", "batch_idx")  # y3d_decode_labels' order
+_LABEL_DTYPES = {"cls": torch.int64, "bboxes": torch.float64, "center_3d": torch.float64, "size_3d": torch.float64, "depth": torch.float64,
+                 "heading_bin": torch.int64, "heading_res": torch.float64, "batch_idx": torch.float32}
+_LABEL_WIDTH = {"cls": 1, "bboxes": 4, "center_3d": 2, "size_3d": 3, "depth": 1, "heading_bin": 1, "heading_res": 1, "batch_idx": 1}
+
+
+def _calib6(calibs, B, dev, what):
+    """(B, 6) float64 on the device from a tensor, a list of six-tuples (`calib_params`) or the reference's Calibration objects"""
+    import numpy as np
+    if torch.is_tensor(calibs):
+        if not calibs.is_cuda:
+            raise Y3DError(f"{what}: a calibration tensor must live on a HIP device (or pass a list of six-tuples)")
+        c = calibs.to(torch.float64)
+    else:
+        six = [[float(getattr(k, a)) for a in ("cu", "cv", "fu", "fv", "tx", "ty")] if hasattr(k, "cu") else [float(v) for v in k] for k in calibs]
+        if any(len(r) != 6 for r in six):
+            raise Y3DError(f"{what}: a calibration is (cu, cv, fu, fv, tx, ty)")
+        c = upload(np.array(six, np.float64).reshape(-1, 6), dev, torch.float64)
+    if c.numel() != B * 6:
+        raise Y3DError(f"{what}: {B} images but calibration rows of shape {tuple(c.shape)}")
+    return c.reshape(B, 6).contiguous()
+
+
+def p2_device(P2, B, dev):
+    """(B, 3, 4) float64 on the device from a device tensor (any float dtype), an array or a list of 3 x 4 matrices"""
+    import numpy as np
+    if torch.is_tensor(P2):
+        if not P2.is_cuda:
+            raise Y3DError("decode_batch: a P2 tensor must live on a HIP device (or pass arrays)")
+        P = P2.to(torch.float64)
+    else:
+        P = upload(np.stack([np.asarray(p, np.float64).reshape(3, 4) for p in P2]), dev, torch.float64)
+    if P.numel() != B * 12:
+        raise Y3DError(f"decode_batch: {B} images but P2 of shape {tuple(P.shape)} (one 3 x 4 matrix each)")
+    return P.reshape(B, 3, 4).contiguous()
+
+
+def decode_labels(labels, counts_in, ori_shape, calib, ratio_pad, trans_inv, P2, mean_size, undo_augment=True, use_camera_dis=False,
+                  R=None, out=None):
+    """`y3d_decode_labels` on device tensors alone: no upload, no allocation beyond the outputs (none with `out`), no wait for the
+    device, so the call can be captured into a graph.  labels: the per-box tensors `cls`, `bboxes`, `center_3d`, `size_3d`, `depth`,
+    `heading_bin`, `heading_res`, `batch_idx` in encode_labels' dtypes.  counts_in (B,) int32: the static layout (`max_objs` =
+    rows / B per image); None: the ragged one (image b owns the rows with batch_idx == b).  ori_shape (B, 2) float64 (height, width),
+    calib (B, 6), ratio_pad (B, 2, 2) or (B, 2), trans_inv (B, 2, 3) or None, P2 (B, 3, 4) float64 or None, mean_size (nc, 3), all
+    float64.  out: optionally (rows (B, R, 14), corners3d (B, R, 8, 3), corners_img (B, R, 8, 2) or None, counts (B,) int32).
+    -> (rows, corners3d, corners_img or None, counts)"""
+    B = int(ori_shape.shape[0]) if torch.is_tensor(ori_shape) and ori_shape.dim() == 2 else 0
+    if B < 1 or tuple(ori_shape.shape) != (B, 2):
+        raise Y3DError("decode_labels: ori_shape must be a (B, 2) tensor of (height, width), B >= 1")
+    dev = ori_shape.device
+    missing = [k for k in _LABEL_KEYS if k not in labels]
+    if missing:
+        raise Y3DError(f"decode_labels: the batch lacks its per-box keys {missing}")
+    per_image = {"ori_shape": ori_shape, "calib": calib, "ratio_pad": ratio_pad, "mean_size": mean_size}
+    if trans_inv is not None:
+        per_image["trans_inv"] = trans_inv
+    if P2 is not None:
+        per_image["P2"] = P2
+    for k, t in per_image.items():
+        if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.float64 or not t.is_contiguous():
+            raise Y3DError(f"decode_labels: {k} must be a contiguous float64 tensor on a HIP device (no host fallback)")
+    N = int(labels["cls"].shape[0]) if torch.is_tensor(labels["cls"]) else -1
+    for k in _LABEL_KEYS:
+        t = labels[k]
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise Y3DError(f"decode_labels: {k} must be a tensor on a HIP device (no host fallback)")
+        if t.dtype != _LABEL_DTYPES[k] or not t.is_contiguous():
+            raise Y3DError(f"decode_labels: {k} must be a contiguous {str(_LABEL_DTYPES[k]).replace('torch.', '')} tensor, got {t.dtype}")
+        if t.numel() != N * _LABEL_WIDTH[k]:
+            raise Y3DError(f"decode_labels: {k} of shape {tuple(t.shape)} next to {N} rows of cls")
+    if calib.numel() != B * 6 or ratio_pad.numel() not in (B * 2, B * 4) or mean_size.dim() != 2 or mean_size.shape[1] != 3 or not mean_size.shape[0]:
+        raise Y3DError(f"decode_labels: {B} images but calib {tuple(calib.shape)}, ratio_pad {tuple(ratio_pad.shape)}, mean_size {tuple(mean_size.shape)}")
+    if (trans_inv is not None and trans_inv.numel() != B * 6) or (P2 is not None and P2.numel() != B * 12):
+        raise Y3DError(f"decode_labels: {B} images need trans_inv (B, 2, 3) and P2 (B, 3, 4)")
+    if undo_augment and trans_inv is None:
+        raise Y3DError("decode_labels: undo_augment needs trans_inv")
+    max_objs = 0
+    if counts_in is not None:
+        if not torch.is_tensor(counts_in) or not counts_in.is_cuda or counts_in.dtype != torch.int32 or tuple(counts_in.shape) != (B,):
+            raise Y3DError(f"decode_labels: counts must be a (B,) int32 tensor on a HIP device, B = {B}")
+        if N < B or N % B:
+            raise Y3DError(f"decode_labels: a static layout of {N} rows does not divide into {B} images")
+        max_objs = N // B
+    R = MAX_OBJS if R is None else int(R)
+    if R < 1:
+        raise Y3DError(f"decode_labels: R = {R} slots per image")
+    if out is None:
+        e = lambda *s, dt=torch.float64: torch.empty(*s, dtype=dt, device=dev)
+        out = (e(B, R, 14), e(B, R, 8, 3), e(B, R, 8, 2) if P2 is not None else None, e(B, dt=torch.int32))
+    rows, c3, ci, counts = out
+    if tuple(rows.shape) != (B, R, 14) or tuple(c3.shape) != (B, R, 8, 3) or tuple(counts.shape) != (B,) or (ci is not None and tuple(ci.shape) != (B, R, 8, 2)):
+        raise Y3DError(f"decode_labels: outputs must be (B, R, 14), (B, R, 8, 3), (B, R, 8, 2), (B,) with B = {B}, R = {R}")
+    if (ci is None) != (P2 is None):
+        raise Y3DError("decode_labels: corners_img goes with P2 (both or neither)")
+    for t, dt in ((rows, torch.float64), (c3, torch.float64), (ci, torch.float64), (counts, torch.int32)):
+        if t is not None and (not t.is_cuda or t.dtype != dt or not t.is_contiguous()):
+            raise Y3DError("decode_labels: the outputs must be contiguous float64 (counts: int32) tensors on a HIP device")
+    ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
+    lib().decode_labels(*[ptr(labels[k]) for k in _LABEL_KEYS], ptr(counts_in), N, max_objs, B, ori_shape.data_ptr(), calib.data_ptr(),
+                        ratio_pad.data_ptr(), 4 if ratio_pad.numel() == B * 4 else 2, ptr(trans_inv), ptr(P2), mean_size.data_ptr(),
+                        int(mean_size.shape[0]), int(bool(use_camera_dis)), int(bool(undo_augment)), R, rows.data_ptr(), c3.data_ptr(), ptr(ci),
+                        counts.data_ptr(), ops.stream())
+    return rows, c3, ci, counts
+
+
+def batch_labels(batch):
+    """the per-box tensors of a built batch in y3d_decode_labels' dtypes (the ragged form holds collate_fn's promoted dtypes, widened here
+    exactly) and its `counts` (static layout) or None (ragged)"""
+    missing = [k for k in _LABEL_KEYS if k not in batch]
+    if missing:
+        raise Y3DError(f"decode_batch: the batch lacks its per-box keys {missing}")
+    labels = {}
+    for k in _LABEL_KEYS:
+        t = batch[k]
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise Y3DError(f"decode_batch: batch[{k!r}] must be a tensor on a HIP device (no host fallback)")
+        labels[k] = t.to(_LABEL_DTYPES[k]).contiguous()
+    return labels, batch.get("counts")
+
+
+def decode_batch_device(batch, calibs, P2=None, undo_augment=True, cls_mean_size=CLS_MEAN_SIZE, use_camera_dis=False, max_objs=None):
+    """`KITTIDataset.decode_batch` (kitti.py:469-513) for a batch of `build_batch` (either layout) on the device, one launch
+    (`y3d_decode_labels`) and no read-back.  calibs: the ORIGINAL images' (cu, cv, fu, fv, tx, ty) as (B, 6) device tensor or a list of
+    six-tuples (`calib_params`; uploaded once); `trans_inv` is taken from `batch["info"]`; P2: the original images' (B, 3, 4)
+    projections (device tensor, array or list), or None.  -> rows (B, R, 14) float64 [cls, alpha, x1, y1, x2, y2, h, w, l, x, y, z, ry,
+    1], corners3d (B, R, 8, 3), corners_img (B, R, 8, 2) in original-image pixels (None without P2), counts (B,) int32; image b's
+    boxes are its first counts[b] slots in label order, the rest zeros.  R = the static layout's rows per image, or
+    min(rows of the batch, max_objs) for the ragged one (max_objs None: MAX_OBJS).  A class outside the mean-size table stays in
+    column 0 (`decode_batch` raises on it); a box behind the camera is decoded like any other (its projected corners are the plain
+    quotient; `plot.box3d_segments` clips at the near plane)."""
+    import numpy as np
+    if "ori_shape" not in batch or "ratio_pad" not in batch or "info" not in batch:
+        raise Y3DError("decode_batch: the batch lacks ori_shape, ratio_pad or info")
+    labels, counts_in = batch_labels(batch)
+    dev = labels["cls"].device
+    B = len(batch["ori_shape"])
+    if B < 1 or len(batch["info"]) != B:
+        raise Y3DError(f"decode_batch: {B} ori_shape entries, {len(batch['info'])} info entries")
+    ori = upload(np.array([[float(s[0]), float(s[1])] for s in batch["ori_shape"]], np.float64).reshape(B, 2), dev, torch.float64)
+    calib = _calib6(calibs, B, dev, "decode_batch")
+    rp = batch["ratio_pad"]
+    if not torch.is_tensor(rp) or not rp.is_cuda:
+        raise Y3DError("decode_batch: batch['ratio_pad'] must be a tensor on a HIP device (no host fallback)")
+    rp = rp.to(torch.float64).contiguous()
+    inv = None
+    if undo_augment:
+        inv = upload(np.stack([np.asarray(i["trans_inv"], np.float64).reshape(2, 3) for i in batch["info"]]), dev, torch.float64)
+    if P2 is not None:
+        P2 = p2_device(P2, B, dev)
+    ms = cls_mean_size if torch.is_tensor(cls_mean_size) else upload(np.asarray(cls_mean_size, np.float64).reshape(-1, 3), dev, torch.float64)
+    ms = ms.to(dev, torch.float64).reshape(-1, 3).contiguous()
+    N = int(labels["cls"].shape[0])
+    if counts_in is not None:
+        if N < B or N % B:
+            raise Y3DError(f"decode_batch: a static layout of {N} rows does not divide into {B} images")
+        R = N // B
+    else:
+        R = max(1, min(N, MAX_OBJS if max_objs is None else int(max_objs)))
+    return decode_labels(labels, counts_in, ori, calib, rp, inv, P2, ms, undo_augment, use_camera_dis, R)
+
+
+def decode_batch(batch, calibs, undo_augment=True, cls_mean_size=CLS_MEAN_SIZE, use_camera_dis=False, max_objs=None):
+    """kitti.py:469-513: {im_file: [[cls, alpha, x1, y1, x2, y2, h, w, l, x, y, z, ry, 1], ...]} after one read-back.  A label whose class
+    lies outside the mean-size table raises (the reference's IndexError)."""
+    rows, _, _, counts = decode_batch_device(batch, calibs, None, undo_augment, cls_mean_size, use_camera_dis, max_objs)
+    host = torch.cat((rows.reshape(rows.shape[0], -1), counts.to(rows.dtype).unsqueeze(1)), 1).cpu()
+    nc = len(cls_mean_size)
+    out = {}
+    for i, f in enumerate(batch["im_file"]):
+        n = int(host[i, -1])
+        r = host[i, :n * 14].reshape(n, 14).tolist()
+        for row in r:
+            if not 0 <= row[0] < nc:
+                raise Y3DError(f"decode_batch: {f} holds class {row[0]:g}, outside the mean-size table of {nc} classes")
+            row[0], row[13] = int(row[0]), 1
+        out[f] = r
+    return out
 
 
 # ------------------------------------------------------------------------------------------------------------------------------

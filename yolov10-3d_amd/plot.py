@@ -233,3 +233,82 @@ def corners3d_of(rows):
     yc = -h[:, None] * np.array([0.0, 0, 0, 0, 1, 1, 1, 1])
     c, s = np.cos(ry)[:, None], np.sin(ry)[:, None]
     return np.stack([(c * xc + s * zc) + loc[:, 0:1], yc + loc[:, 1:2], (-s * xc + c * zc) + loc[:, 2:3]], -1)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# label pictures: the decoded labels of a batch (kitti.decode_batch_device) drawn over its images
+# ------------------------------------------------------------------------------------------------------------------------------
+GT_BOX_COLOUR = ((255, 89, 89),)  # plot_3d_obj's 2D rectangle of a label, (1, 0.35, 0.35) (utils/plotting.py:1408)
+
+
+def box2d_segments(rows, counts, affine=None, colour=GT_BOX_COLOUR):
+    """the 2D rectangles of decoded rows (B, K, 14) (columns 2:6 = x1, y1, x2, y2 in original-image pixels) -> segs (B, K * 4, 4) float64,
+    seg_rgb (B, K * 4, 4) uint8: per row the edges top, right, bottom, left, every corner through u' = (A00 u + A01 v) + A02 (v' from
+    row 1) when the 2 x 3 `affine` is given, each product and sum rounded on its own as box3d_segments rounds them; the slots behind
+    counts are NaN.  Index arithmetic on the device, no read-back."""
+    rows = _dev_tensor(rows, torch.float64, "box2d_segments: rows")
+    if rows.dim() != 3 or rows.shape[2] != 14 or rows.shape[0] < 1:
+        raise Y3DError(f"box2d_segments: rows of shape {tuple(rows.shape)}, expected (B, K, 14)")
+    B, K = int(rows.shape[0]), int(rows.shape[1])
+    counts = _dev_tensor(counts, torch.int32, "box2d_segments: counts")
+    if tuple(counts.shape) != (B,):
+        raise Y3DError(f"box2d_segments: counts of shape {tuple(counts.shape)}, expected {(B,)}")
+    x1, y1, x2, y2 = (rows[..., c] for c in (2, 3, 4, 5))
+    pts = [(x1, y1), (x2, y1), (x2, y2), (x1, y2)]
+    if affine is not None:
+        A = _dev_tensor(affine, torch.float64, "box2d_segments: affine")
+        if A.numel() != B * 6:
+            raise Y3DError(f"box2d_segments: {B} images but affine of shape {tuple(A.shape)} (one 2 x 3 matrix each)")
+        A = A.reshape(B, 6, 1)
+        pts = [(torch.add(torch.add(torch.mul(A[:, 0], u), torch.mul(A[:, 1], v)), A[:, 2]),
+                torch.add(torch.add(torch.mul(A[:, 3], u), torch.mul(A[:, 4], v)), A[:, 5])) for u, v in pts]
+    segs = torch.stack([torch.stack((pts[e][0], pts[e][1], pts[(e + 1) % 4][0], pts[(e + 1) % 4][1]), -1) for e in range(4)], 2)  # (B, K, 4, 4)
+    live = torch.arange(K, device=rows.device).unsqueeze(0) < counts.unsqueeze(1)
+    segs = torch.where(live[..., None, None], segs, torch.full_like(segs, float("nan"))).reshape(B, K * 4, 4).contiguous()
+    rgb = torch.cat((_palette(colour, rows.device)[0], torch.zeros(1, dtype=torch.uint8, device=rows.device))).repeat(B, K * 4, 1)
+    return segs, rgb
+
+
+def draw_labels3d(canvas, rows, corners3d, counts, P2, affine=None, box2d=True, thickness=2):
+    """the decoded labels of `kitti.decode_batch_device` over canvas (B, H, W, 3) uint8, in place: the wireframes in `GT_COLOUR` through
+    `box3d_segments` and, with `box2d`, each row's 2D rectangle in `GT_BOX_COLOUR` (four segments, `box2d_segments`), as `plot_3d_obj`
+    draws a label (utils/plotting.py:1395-1410).  One `draw_segments` launch: the rectangles hold the lower indices, so they lie over the
+    wireframes as there.  P2 (B, 3, 4) float64 projects into the original image; `affine` leads from there to the canvas's frame."""
+    segs, rgb = box3d_segments(corners3d, None, counts, P2, affine, GT_COLOUR)
+    if box2d:
+        s2, c2 = box2d_segments(rows, counts, affine)
+        segs, rgb = torch.cat((s2, segs), 1), torch.cat((c2, rgb), 1)
+    return draw_segments(canvas, segs, rgb, None, thickness)
+
+
+def ratio_affine(ratio_pad, n=None):
+    """ratio_pad (B, 2, 2) or (B, 2) on the device -> the (n, 2, 3) float64 scaling from the original image to the network frame"""
+    rp = _dev_tensor(ratio_pad, torch.float64, "ratio_affine: ratio_pad")
+    r = (rp[:, 0] if rp.dim() == 3 else rp)[:n]
+    A = torch.zeros(r.shape[0], 2, 3, dtype=torch.float64, device=rp.device)
+    A[:, 0, 0], A[:, 1, 1] = r[:, 0], r[:, 1]
+    return A
+
+
+def label_pictures(batch, calibs, P2s, max_imgs=9, cls_mean_size=None, use_camera_dis=False, thickness=2):
+    """The array counterpart of `KITTIVisualizer.plot_batch` (utils/plotting.py:1232-1266): the labels of a built batch, decoded with
+    undo_augment=False exactly as plot_batch decodes them, drawn over the first `max_imgs` images of `batch["img"]` ((B, H, W, 3) uint8)
+    in the network frame (`affine` = the scaling by ratio_pad; the reference resizes the image to the original size instead).
+    calibs, P2s: the ORIGINAL images' six constants and projections, as `kitti.decode_batch_device` takes them.
+    -> (n, H, W, 3) uint8 on the device, n = min(B, max_imgs); the batch's images are left as they are.
+    What the reference's choice implies: a mirrored or cropped training frame is drawn with the original, unmirrored calibration and the
+    plain rescale, so its wireframes sit where the reference draws them, not on the augmented objects; validation frames are exact."""
+    from . import kitti
+    img = batch.get("img") if isinstance(batch, dict) else None
+    if not torch.is_tensor(img) or not img.is_cuda or img.dtype != torch.uint8 or img.dim() != 4 or img.shape[3] != 3:
+        raise Y3DError("label_pictures: batch['img'] must be a (B, H, W, 3) uint8 tensor on a HIP device (img_mode='uint8')")
+    if int(max_imgs) < 1:
+        raise Y3DError(f"label_pictures: max_imgs = {max_imgs}")
+    rows, c3, _, counts = kitti.decode_batch_device(batch, calibs, P2s, undo_augment=False,
+                                                    cls_mean_size=kitti.CLS_MEAN_SIZE if cls_mean_size is None else cls_mean_size,
+                                                    use_camera_dis=use_camera_dis)
+    n = min(int(img.shape[0]), int(max_imgs))
+    P = kitti.p2_device(P2s, int(img.shape[0]), img.device)
+    canvas = img[:n].clone()
+    return draw_labels3d(canvas, rows[:n].contiguous(), c3[:n].contiguous(), counts[:n].contiguous(), P[:n].contiguous(),
+                         ratio_affine(batch["ratio_pad"].to(torch.float64), n), True, thickness)

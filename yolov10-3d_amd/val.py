@@ -19,10 +19,10 @@ import os
 import numpy as np
 import torch
 
-from . import json3d, kitti, kitti_eval, metrics, yolo2d
+from . import json3d, kitti, kitti_eval, metrics, plot, yolo2d
 from ._lib import Y3DError
 from .graph import GraphedForward
-from .predict import _mean_sizes, raw_rows, raw_rows3d
+from .predict import _mean_sizes, predict3d_rows, raw_rows, raw_rows3d
 
 
 def _is_3d(model):
@@ -99,10 +99,20 @@ class Validator3d(_Validator):
     KITTI: `metrics/3D` = `kitti_eval.get_stats(results, label_dir or <root>/training/label_2)`.  Waymo and Omni3D: the reference's
     metric shells out to a TensorFlow environment, so `metrics/3D` keeps `Det3dMetrics`' initial value, 0.
     `resolution` applies to KITTI; the other two datasets have the fixed `json3d.RESOLUTION`.  `speed`: preprocess = the batch builder,
-    inference = the eval forward (with graph=True the replay, which includes `v10_3Dpostprocess`), postprocess = the rest."""
+    inference = the eval forward (with graph=True the replay, which includes `v10_3Dpostprocess`), postprocess = the rest.
+
+    `pictures` = n > 0 (the reference's `plot_val_samples` / `plot_predictions` take the first 3 batches): for the first n batches, up to
+    nine images each of the label picture (`plot.label_pictures`), the prediction picture (predictions at threshold 0.1, decoded with
+    undo_augment=False, under the labels' wireframes, as `plot_preds` draws them) and the BEV map with the decoded labels as `gt`, all
+    made on the device after the batch's metrics and read back once after the loop into `self.pictures`, a list of {"labels", "preds",
+    "bev"} uint8 arrays.  With pictures=0 (the default) nothing more is launched than before."""
+
+    PICTURE_CONF, PICTURE_IMGS = 0.1, 9  # plot_preds' threshold, KITTIVisualizer.max_imgs
 
     def __init__(self, model, root_or_split, args=None, dataset="kitti", batch=16, conf=0.001, max_det=50, single_cls=False, plots=True,
-                 resolution=kitti.RESOLUTION, label_dir=None, graph=False):
+                 resolution=kitti.RESOLUTION, label_dir=None, graph=False, pictures=0):
+        if int(pictures) != pictures or int(pictures) < 0:
+            raise Y3DError(f"Validator3d: pictures = {pictures!r} (the number of leading batches to draw, 0 for none)")
         super().__init__(model, True, conf, max_det, single_cls, plots, graph)
         if dataset not in ("kitti", "waymo", "omni3d"):
             raise Y3DError(f"Validator3d: dataset {dataset!r} (kitti, waymo or omni3d)")
@@ -116,9 +126,35 @@ class Validator3d(_Validator):
         self.label_dir = label_dir
         self.mean_sizes = kitti.CLS_MEAN_SIZE if dataset == "kitti" else json3d.CLS_MEAN_SIZE[dataset]
         self.results = {}
+        self.n_pictures, self.pictures = int(pictures), []
 
     def _rows(self, img):
         return raw_rows3d(self.model, img.permute(0, 3, 1, 2), self.max_det)
+
+    def _projection(self):
+        """-> position -> the original image's P2 (3, 4), next to `_dataset`'s six constants"""
+        if isinstance(self.source, kitti.DeviceSplit):
+            return lambda pos: self.source.P2_host[pos]
+        if self.dataset == "kitti":
+            data, ids = kitti._split(self.source, "val")
+            return lambda pos: kitti.read_calib(os.path.join(data, "calib", f"{ids[pos]:06d}.txt"))
+        sp = json3d.read_split(self.source, self.dataset, bool(getattr(self.args, "overfit", False)))
+        return lambda pos: sp.P2(sp.ids[pos])
+
+    def _draw(self, b, raw, c6, P2s, ms):
+        """the three pictures of one batch, device tensors (nothing is read back here)"""
+        n = min(int(b["img"].shape[0]), self.PICTURE_IMGS)
+        cam_dis = bool(getattr(self.args, "cam_dis", False))
+        P = kitti.p2_device(P2s, int(b["img"].shape[0]), self.device)
+        labels = plot.label_pictures(b, c6, P, self.PICTURE_IMGS, ms, cam_dis)
+        lrows, lc3, _, lcounts = kitti.decode_batch_device(b, c6, None, False, ms, cam_dis)
+        prow, pc3, _, pcounts = predict3d_rows(raw, c6, P, b["ratio_pad"], None, self.PICTURE_CONF, None, ms, cam_dis)
+        first = lambda *ts: [t[:n].contiguous() for t in ts]
+        affine = plot.ratio_affine(b["ratio_pad"].to(torch.float64), n)
+        preds = plot.draw_boxes3d(b["img"][:n].clone(), *first(pc3, prow, pcounts, P), affine)
+        plot.draw_labels3d(preds, *first(lrows, lc3, lcounts, P), affine, box2d=False)
+        pc3, prow, pcounts, lc3, lcounts = first(pc3, prow, pcounts, lc3, lcounts)
+        return {"labels": labels, "preds": preds, "bev": plot.draw_bev(pc3, prow, pcounts, gt=(lc3, lcounts))}
 
     def _dataset(self):
         """-> (number of images, position -> the original image's (cu, cv, fu, fv, tx, ty), as the reference's get_calib holds them)"""
@@ -145,7 +181,8 @@ class Validator3d(_Validator):
         n, calib, data = self._dataset()
         self._start()
         ms = _mean_sizes(self.mean_sizes, self.device)
-        files, kept = [], []
+        files, kept, drawn = [], [], []
+        P2_of = self._projection() if self.n_pictures else None
         for s in range(0, n, self.batch):
             idx = list(range(s, min(s + self.batch, n)))
             t0 = self._mark()
@@ -162,6 +199,9 @@ class Validator3d(_Validator):
             self._events.append((t0, t1, t2, self._mark()))
             files += list(b["im_file"])
             kept.append(torch.cat((rows, keep.unsqueeze(-1).to(rows.dtype)), -1))
+            if len(drawn) < self.n_pictures:
+                drawn.append(self._draw(b, raw, c6, [P2_of(p) for p in idx], ms))
+        self.pictures = [{k: v.cpu().numpy() for k, v in d.items()} for d in drawn]  # the one read-back of the pictures
         self.results = {}
         if kept:  # the one read-back of the rows
             host = torch.cat(kept).cpu()
