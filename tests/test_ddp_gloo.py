@@ -126,7 +126,7 @@ def _worker_real_model(rank, world, port, ret, overlap):
     head.restack()
     assert all(p.data_ptr() == ptrs[id(p)] for p in model.parameters()), "broadcast / restack moved a parameter"
     # the stacked views still alias the per-branch parameters after the broadcast
-    _, _, s1, s2, _, _ = head._stacks(0)
+    s1 = head._stacks(0).s1
     w, gm, bt, rm, rv = s1.tensors()
     off = 0
     for c in s1.convs:

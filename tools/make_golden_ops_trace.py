@@ -15,7 +15,10 @@ Cases (`CASES`): the tiny 3D model of `__graft_entry__.smoke()` (training forwar
 smallest image whose stride-32 map holds the head's 50 candidates) in bf16 and f32, bf16 with each of PACK_CACHE / STEM_FUSED /
 PROJ_BN_MFMA / DW_EVAL_FUSED / PLACEMENT off, two steps around a `bump_weight_epoch()`, the eval forward of the model folded the
 reference's way; the stem on uint8 images; the 128-wide head of tests/test_hip_fp8.py under the three fp8 switches and with
-PROJ_BN_MFMA off; the 2D `v10Detect` head with a wide and a narrow projection; eval Bottlenecks with a shortcut on both residual arms.
+PROJ_BN_MFMA off; the 2D `v10Detect` head with a wide and a narrow projection; eval Bottlenecks with a shortcut on both residual arms;
+the stacking layouts of `modules.v10Detect3d` that the models above do not have (`head3d_layout`: cls wider than the regression
+branches with every / some / no part on the fused BatchNorm projections, the uniform layout unfused at 64 channels, no second-layer
+stack, the distillation node), each in training and in eval.
 """
 from __future__ import annotations
 
@@ -220,6 +223,82 @@ def head3d(quant=None, conv=False, dgrad=False, off=None, eval_too=False):
     torch.cuda.synchronize()
 
 
+HEAD_BRANCHES = ("cls", "o2d", "s2d", "o3d", "s3d", "hd", "dep", "dep_un")
+
+
+def head3d_layout(cls_c, reg_c, fuse=True, distill=False, eval_too=True, **other):
+    """one stacking layout of `modules.v10Detect3d`: the two-level head of tests/test_hip_distill.py (`_head`) with `cls` `cls_c` wide and
+    the seven regression branches `reg_c` wide (`other`: single branches at another width), B = 2 on a 12x12 and an 8x8 map (64 cells:
+    the smallest map that holds the eval head's 50 candidates); training forward + backward, then the eval forward.  `distill`: the
+    InjectRowsFn node sits behind z1, and its backward is handed one EMPTY compact-row entry per head set and level (no row is written),
+    so that the trace holds the `distill_scatter` launches with the widths and level sizes the slots name."""
+    import torch
+    from yolov10_3d_amd import modules as M
+    torch.manual_seed(7)
+    chan = {k + "_c": other.get(k, cls_c if k == "cls" else reg_c) for k in HEAD_BRANCHES}
+    hd = M.v10Detect3d(3, (32, 64), False, chan, False, False, False, False, 2, False, False, 3, 3)
+    hd.stride = torch.tensor([8.0, 16.0])
+    hd.bias_init()
+    hd = hd.to(DEV).train()
+    with torch.no_grad():
+        for p in hd.parameters():
+            p.add_(0.02 * torch.randn_like(p))
+    hd.fuse_bn_proj, hd.distill = fuse, distill
+    g = torch.Generator().manual_seed(8)
+    xs = [torch.randn(2, 32, 12, 12, generator=g).to(DEV), torch.randn(2, 64, 8, 8, generator=g).to(DEV)]
+    out = hd([x.requires_grad_(True) for x in xs])
+    a0 = 0
+    for slot, z in zip(out.get("_y3d_distill", ()), out["o2o_embs"]):
+        for which in (0, 1):
+            C = slot["C"][which]
+            slot.setdefault("entries", []).append({
+                "rows": torch.zeros(4, C, dtype=z.dtype, device=DEV), "idx": torch.zeros(4, 2, dtype=torch.int32, device=DEV),
+                "nrows": torch.zeros(1, dtype=torch.int32, device=DEV), "scale": torch.ones(1, device=DEV), "cap": 4, "C": C,
+                "off": slot["offs"][which], "a0": a0})
+        a0 += z.shape[2] * z.shape[3]
+    sum(t.float().sum() for t in out["one2many"] + out["one2one"]).backward()
+    if eval_too:
+        with torch.no_grad():
+            hd.eval()([x.detach() for x in xs])
+    torch.cuda.synchronize()
+
+
+def head3d_wide_cls_fused():
+    """(128, 64): the parts arm with every part (cls | 14 regression branches | cls) on FusedConvBNProjFn; the 16 projected slices are
+    lined up by one `cat`.  Eval: the per-branch patch path (only the uniform layout has the stacked one)."""
+    head3d_layout(128, 64)
+
+
+def head3d_wide_cls_mixed():
+    """(128, 32): the parts arm with the two cls parts on FusedConvBNProjFn and the regression part unfused (32 is no multiple of 64): its
+    14 features are projected one by one and the 16 outputs lined up - the mixed tail."""
+    head3d_layout(128, 32)
+
+
+def head3d_wide_cls_unfused():
+    """the parts arm with no part fused: (32, 16), no width a multiple of 64, and (128, 64) with `fuse_bn_proj` off; one HeadProjFn over
+    the 16 features in canonical order."""
+    head3d_layout(32, 16)
+    head3d_layout(128, 64, fuse=False)
+
+
+def head3d_uniform_unfused():
+    """(64, 64) with `fuse_bn_proj` off: the uniform arm on FusedConvBNActFn + HeadProjSlicesFn at a width where FusedConvBNProjFn would be
+    taken otherwise.  Eval: the stacked patch path."""
+    head3d_layout(64, 64, fuse=False)
+
+
+def head3d_no_stack():
+    """regression widths not all equal (hd 32, the others 16): no second-layer stack, the per-branch second layer over one channel split of
+    z1 and one HeadProjFn.  Eval: the per-branch patch path with its temporary padding edit."""
+    head3d_layout(16, 16, hd=32)
+
+
+def head3d_distill():
+    """(128, 64) with `distill` on: InjectRowsFn between z1 and the channel split of the parts arm (training part only)."""
+    head3d_layout(128, 64, distill=True, eval_too=False)
+
+
 def head2d():
     """one level at 8x8, nc = 8: the 64 box-distribution outputs take HeadProjFn's wide (MFMA) arm, the 8 class outputs its narrow one"""
     import torch
@@ -265,7 +344,33 @@ CASES = {
     "head3d/PROJ_BN_MFMA_off": lambda: head3d(off="PROJ_BN_MFMA", eval_too=True),  # (the tiny model's 16-wide head never takes the matrix-core forms)
     "head2d": head2d,
     "bottleneck_eval": bottleneck_eval,
+    "head3d/wide_cls/fused": head3d_wide_cls_fused,
+    "head3d/wide_cls/mixed": head3d_wide_cls_mixed,
+    "head3d/wide_cls/unfused": head3d_wide_cls_unfused,
+    "head3d/uniform/unfused": head3d_uniform_unfused,
+    "head3d/no_stack": head3d_no_stack,
+    "head3d/distill": head3d_distill,
 }
+
+# the head layout cases: (launches a case must hold, launches it must not), looked at when the fixture is minted
+HEAD_LAYOUT_CALLS = {
+    "head3d/wide_cls/fused": (("proj_group_bn_bwd",), ("proj_bwd_weight", "proj_group_bwd_weight")),
+    "head3d/wide_cls/mixed": (("proj_group_bn_bwd", "proj_bwd_weight"), ("proj_group_bwd_weight",)),
+    "head3d/wide_cls/unfused": (("proj_bwd_weight",), ("proj_group_bn_bwd", "proj_group_bwd_weight")),
+    "head3d/uniform/unfused": (("proj_group_bwd_weight", "proj_group_fwd_bn_mfma"), ("proj_group_bn_bwd", "proj_bwd_weight")),
+    "head3d/no_stack": (("proj_bwd_weight",), ("proj_group_bn_bwd", "proj_group_bwd_weight", "proj_group_fwd_bn_mfma")),
+    "head3d/distill": (("proj_group_bn_bwd", "distill_scatter"), ("proj_bwd_weight",)),
+}
+
+
+def off_layout(traces):
+    """the head layout cases whose trace does not show the arm they are for"""
+    bad = []
+    for case, (must, must_not) in HEAD_LAYOUT_CALLS.items():
+        names = {c[0] for c in traces[case]}
+        if not set(must) <= names or names & set(must_not):
+            bad.append(case)
+    return bad
 
 
 def run_case(name):
@@ -385,7 +490,9 @@ def main():
     if miss and "--allow-unreached" not in sys.argv:
         sys.exit(f"arms not reached by any case: {miss}")
     print(f"arms not reached: {miss}")
-    out = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else OUT
+    if off_layout(traces):
+        sys.exit(f"head layout cases that did not reach their arm: {off_layout(traces)}")
+    out =sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else OUT
     os.makedirs(os.path.dirname(out), exist_ok=True)
     with open(out, "wb") as raw, gzip.GzipFile(filename="", fileobj=raw, mode="wb", mtime=0) as f:
         f.write(json.dumps(pack(traces), separators=(",", ":")).encode())

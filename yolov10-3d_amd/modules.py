@@ -8,8 +8,11 @@ checkpoints apply unchanged — but every forward/backward body runs on liby3d_h
 """
 from __future__ import annotations
 
+import contextlib
 import copy
+import ctypes
 import math
+from typing import NamedTuple
 
 import torch
 import torch.nn as nn
@@ -378,10 +381,38 @@ def make_anchors(shapes, strides, device, grid_cell_offset=0.5):
     return torch.cat(pts), torch.cat(st)
 
 
+def _proj_params(convs):
+    """the parameter tail of a projection node: the weights of the final 1x1 convs `convs`, then their biases"""
+    return [c.weight for c in convs] + [c.bias for c in convs]
+
+
 def _proj(branches, feats):
     """final 1x1+bias convs of several branches -> one NHWC map (their torch.cat)"""
-    n = len(branches)
-    return ops.HeadProjFn.apply(n, *feats, *[b.weight for b in branches], *[b.bias for b in branches])
+    return ops.HeadProjFn.apply(len(branches), *feats, *_proj_params(branches))
+
+
+def _decode_args(ys, no, stride):
+    """what the eval decode kernels (`head3d_decode` / `head2d_decode`) take of the level maps `ys`: the maps made pixel-dense with `no`
+    channels in the first one's dtype -> (maps, number of anchors, leading arguments: dtype code, levels, map pointers, heights, widths,
+    strides)"""
+    nl = len(ys)
+    ms = [y if (y.dtype == ys[0].dtype and ops.px_dense(y) and y.stride(3) == no) else ops._dense_any(y, ys[0].dtype) for y in ys]
+    args = (ops.code(ms[0].dtype), nl, (ctypes.c_void_p * nl)(*[y.data_ptr() for y in ms]), (ctypes.c_int * nl)(*[y.shape[2] for y in ms]),
+            (ctypes.c_int * nl)(*[y.shape[3] for y in ms]), (ctypes.c_float * nl)(*[float(s) for s in stride.tolist()[:nl]]))
+    return ms, sum(y.shape[2] * y.shape[3] for y in ms), args
+
+
+@contextlib.contextmanager
+def _unpadded(convs):
+    """the Conv modules `convs` run without padding inside the block; their own padding is back on exit"""
+    pads = [l.conv.padding for l in convs]
+    for l in convs:
+        l.conv.padding = (0, 0)
+    try:
+        yield
+    finally:
+        for l, p0 in zip(convs, pads):
+            l.conv.padding = p0
 
 
 def _conv_over_cat(m, parts):
@@ -401,6 +432,53 @@ def _conv_over_cat(m, parts):
     return ops.ConvBNActFn.apply(torch.cat(parts, 1), w, m.bn.weight, m.bn.bias, None, 0, m)
 
 
+class Part(NamedTuple):
+    """one second-layer conv of a head level: channels [lo, hi) of z1 through `stack`, a conv of `groups` groups, one per branch"""
+    lo: int
+    hi: int
+    stack: ops.StackedConvs
+    groups: int
+    first: int  # stack position of its first branch
+
+    @property
+    def branches(self):
+        return slice(self.first, self.first + self.groups)
+
+    @property
+    def width(self):
+        return (self.hi - self.lo) // self.groups
+
+
+class HeadLevelPlan(NamedTuple):
+    """how v10Detect3d stacks the 16 branches of one level (one-to-one 0..7, one-to-many 8..15 in canonical order).  Three layouts:
+      uniform     every branch equally wide: `layer2` is ONE part of 16 groups, stack order = canonical order;
+      wide cls    cls wider than the seven equally wide regression branches (M-3D: 128 vs 64): stack order [o2o cls, o2o regs, o2m regs,
+                  o2m cls] (the one-to-one half stays first: its input is detached), `layer2` = cls | 14 regression branches as one
+                  grouped conv | cls;
+      per branch  anything else: canonical order and no part; only the first layer is stacked."""
+    branches: tuple  # the 16 branch Sequentials, in stack order like mids and offs
+    mids: tuple      # first-layer width per branch
+    offs: tuple      # first channel of each branch in z1
+    pos: tuple       # canonical branch index -> stack position
+    s1: ops.StackedConvs
+    layer2: tuple    # of Part: they tile z1's channels in stack order
+    emb: tuple       # (offset, width) in z1 of the depth branch of the one-to-one and of the one-to-many set
+
+    @property
+    def o2m_range(self):
+        """z1's channels of the one-to-many half (the one-to-one half in front of it takes no input gradient)"""
+        return self.offs[8], self.offs[15] + self.mids[15]
+
+    @property
+    def uniform(self):
+        return len(self.layer2) == 1
+
+    def stacks(self):
+        yield self.s1
+        for part in self.layer2:
+            yield part.stack
+
+
 class v10Detect3d(nn.Module):
     """reference head.py:545-975.  The shipped yamls leave every constructor switch off; with `dsconv`, `half_channels` or
     `use_predecessors` on, the head is built and run branch by branch (head.py:629-650, 718-743) on the same HIP ops - the
@@ -414,6 +492,7 @@ class v10Detect3d(nn.Module):
     export = False
     shape = None
     fused = True  # sibling-branch fusion of the training forward (set False for the per-branch reference form)
+    fuse_bn_proj = True  # second layer of 64-multiple width: BatchNorm + SiLU applied inside the projections (set False for the separate passes)
     distill = False  # set by loss.DDDetectionLoss under `distillation: True`: the fused forward opens the sparse gradient path into z1
     PREDECESSORS = {"cls": (), "o2d": (), "s2d": (), "o3d": ("cls",), "s3d": ("cls",), "hd": ("cls",), "dep": ("cls", "s3d"),
                     "dep_un": ("cls", "s3d", "dep")}  # head.py:585-594
@@ -493,36 +572,31 @@ class v10Detect3d(nn.Module):
         return ys, embs
 
     def _stacks(self, i):
-        """StackedConvs of level i over [o2o branches 0..7, o2m branches 0..7] for layer 1 and layer 2.
-        -> (branches, mids, s1, s2, parts).  Uniform widths: s2 is ONE grouped stack, parts is None, the stack order is the branch
-        order.  cls wider than the seven regression branches (M-3D: 128 vs 64): `branches` / `mids` are in STACK order
-        [o2o cls, o2o regs, o2m regs, o2m cls] (the one-to-one half stays first: its input is detached), s2 is None and parts lists the
-        second layer as (lo, hi, stack, groups) over z1's channels: cls | 14 regression branches as one grouped conv | cls;
-        `pos[c]` maps the canonical branch index c (o2o 0..7, o2m 8..15) to its stack position."""
+        """the HeadLevelPlan of level i: StackedConvs over [o2o branches 0..7, o2m branches 0..7] for layer 1 and, where the widths
+        allow, layer 2 (re-made when a head set is replaced, e.g. by bias_init)"""
         key = (i, id(self.o2o_heads), id(self.o2m_heads))
         cache = self.__dict__.setdefault("_stack_cache", {})
         if key not in cache:
             canon = [h[i] for h in self.o2o_heads] + [h[i] for h in self.o2m_heads]
             cm = [b[0].conv.out_channels for b in canon]
             k2 = [b[1].conv.kernel_size for b in canon]
+            order, groups = list(range(16)), ()
             if len(set(cm)) == 1:
-                s1 = ops.StackedConvs([b[0] for b in canon])
-                s2 = ops.StackedConvs([b[1] for b in canon], groups=len(canon))
-                cache[key] = (canon, cm, s1, s2, None, list(range(16)))
+                groups = (16,)
             elif len(set(cm[1:8] + cm[9:16])) == 1 and cm[0] == cm[8] and len(set(k2)) == 1 and cm[1] % 8 == 0 and cm[0] % 8 == 0:
-                order = list(range(0, 8)) + list(range(9, 16)) + [8]
-                branches = [canon[c] for c in order]
-                mids = [cm[c] for c in order]
-                pos = [order.index(c) for c in range(16)]
-                s1 = ops.StackedConvs([b[0] for b in branches])
-                c, m = mids[0], mids[1]
-                parts = [(0, c, ops.StackedConvs([branches[0][1]]), 1),
-                         (c, c + 14 * m, ops.StackedConvs([b[1] for b in branches[1:15]], groups=14), 14),
-                         (c + 14 * m, 2 * c + 14 * m, ops.StackedConvs([branches[15][1]]), 1)]
-                cache[key] = (branches, mids, s1, None, parts, pos)
-            else:
-                s1 = ops.StackedConvs([b[0] for b in canon])
-                cache[key] = (canon, cm, s1, None, None, list(range(16)))
+                order, groups = list(range(0, 8)) + list(range(9, 16)) + [8], (1, 14, 1)
+            branches = [canon[c] for c in order]
+            mids = [cm[c] for c in order]
+            offs = [sum(mids[:j]) for j in range(16)]
+            pos = [order.index(c) for c in range(16)]
+            s1 = ops.StackedConvs([b[0] for b in branches])
+            layer2, first = [], 0
+            for g in groups:
+                last = first + g
+                layer2.append(Part(offs[first], offs[last - 1] + mids[last - 1], ops.StackedConvs([b[1] for b in branches[first:last]], groups=g), g, first))
+                first = last
+            cache[key] = HeadLevelPlan(tuple(branches), tuple(mids), tuple(offs), tuple(pos), s1, tuple(layer2),
+                                       tuple((offs[pos[c]], mids[pos[c]]) for c in (6, 14)))
         return cache[key]
 
     def restack(self):
@@ -531,81 +605,83 @@ class v10Detect3d(nn.Module):
         if self.generic:
             return  # branch-by-branch head: every Conv keeps its own parameters
         for i in range(self.nl):
-            _, _, s1, s2, parts, _ = self._stacks(i)
-            s1.tensors()
-            if s2 is not None:
-                s2.tensors()
-            for part in parts or ():
-                part[2].tensors()
+            for stack in self._stacks(i).stacks():
+                stack.tensors()
 
     def forward_train_fused(self, x):
         """Both head sets of one level as: ONE 3x3 conv Cin -> sum(mid) (the one-to-one half contributes no input gradient:
-        it sees x.detach(), head.py:820), ONE grouped conv (16 groups of mid -> mid), ONE projection launch set writing the
-        (B, 2*no, H, W) map.  Numerically identical to the per-branch form (BatchNorm is per channel)."""
+        it sees x.detach(), head.py:820), the second layer and the projections as the level's layout allows (`_layer2`; uniform widths:
+        ONE grouped conv of 16 groups of mid -> mid and ONE projection launch set), writing the (B, 2*no, H, W) map.  Numerically
+        identical to the per-branch form (BatchNorm is per channel)."""
         o2o, o2m, e_o2o, e_o2m = [], [], [], []
         self._maps = []  # the (B, 2*no, H, W) maps the two head sets are channel halves of: the fused loss takes them whole
         self._slots = []
         for i in range(self.nl):
-            branches, mids, s1, s2, parts, pos = self._stacks(i)
-            half = sum(mids[:8])
+            plan = self._stacks(i)
+            (o1, c1), (om, cm) = plan.emb
             with ops.want_fp8_copy():  # fp8 convolutions on: layer 1's BatchNorm + SiLU pass also writes the fp8 copy layer 2 reads
-                z1 = ops.FusedConvBNActFn.apply(x[i], s1, 1, (half, sum(mids)), *s1.params())
-            offs = [sum(mids[:j]) for j in range(16)]
+                z1 = ops.FusedConvBNActFn.apply(x[i], plan.s1, 1, plan.o2m_range, *plan.s1.params())
             if self.distill:
                 # feature distillation (loss.DistillFn): its gradient reaches z1 as compact rows added to layer 2's data gradient
-                slot = {"ptr": z1.data_ptr(), "offs": (offs[pos[6]], offs[pos[14]]), "C": (mids[pos[6]], mids[pos[14]])}
+                slot = {"ptr": z1.data_ptr(), "offs": (o1, om), "C": (c1, cm)}
                 z1 = ops.InjectRowsFn.apply(z1, slot)
                 self._slots.append(slot)
-            if s2 is not None and mids[0] % 64 == 0 and getattr(self, "fuse_bn_proj", True):
-                # grouped conv + BatchNorm statistics + projections with BatchNorm/SiLU applied on the fly (no activation tensor)
-                out = ops.FusedConvBNProjFn.apply(z1, s2, len(branches), offs, mids, 16, *s2.params(), *[b[2].weight for b in branches],
-                                                  *[b[2].bias for b in branches])
-            elif s2 is not None:
-                z2 = ops.FusedConvBNActFn.apply(z1, s2, len(branches), None, *s2.params())
-                out = ops.HeadProjSlicesFn.apply(z2, offs, mids, 16, *[b[2].weight for b in branches], *[b[2].bias for b in branches])
-            elif parts is not None:
-                # cls | 14 regression branches (one grouped conv) | cls over channel views of z1; every split hands ONE gradient back
-                views = ops.SplitChannelsFn.apply(z1, [lo for lo, _, _, _ in parts], [hi - lo for lo, hi, _, _ in parts])
-                fuse = getattr(self, "fuse_bn_proj", True)
-                outs_s, feats_s, k = [None] * 16, [None] * 16, 0
-                for v, (lo, hi, st2, g) in zip(views, parts):
-                    brs, w = branches[k:k + g], (hi - lo) // g
-                    if fuse and w % 64 == 0:
-                        # this part's grouped conv + BatchNorm statistics + its projections with BatchNorm / SiLU on the fly (the matrix-core
-                        # kernels of proj_bn_mfma.hip at 64 / 128 channels), as on the uniform heads: no activation tensor, no per-branch
-                        # VALU projection launches (M-3D: 32 launches of proj_bwd_weight + 64 slab folds per step)
-                        o = ops.FusedConvBNProjFn.apply(v, st2, g, [j * w for j in range(g)], [w] * g, g, *st2.params(), *[b[2].weight for b in brs],
-                                                        *[b[2].bias for b in brs])
-                        off = 0
-                        for j, b in enumerate(brs):
-                            co = b[2].weight.shape[0]
-                            outs_s[k + j] = o[:, off:off + co]
-                            off += co
-                    else:
-                        z2 = ops.FusedConvBNActFn.apply(v, st2, g, None, *st2.params())
-                        fs = [z2] if g == 1 else ops.SplitChannelsFn.apply(z2, [j * w for j in range(g)], [w] * g)
-                        for j, f in enumerate(fs):
-                            feats_s[k + j] = f
-                    k += g
-                if all(o is not None for o in outs_s):
-                    out = cat([outs_s[pos[c]] for c in range(16)])
-                elif all(f is not None for f in feats_s):
-                    canon = [branches[pos[c]] for c in range(16)]
-                    out = _proj([b[2] for b in canon], [feats_s[pos[c]] for c in range(16)])
-                else:  # mixed: project the un-fused branches one by one, then line the 16 outputs up
-                    for j in range(16):
-                        if outs_s[j] is None:
-                            outs_s[j] = _proj([branches[j][2]], [feats_s[j]])
-                    out = cat([outs_s[pos[c]] for c in range(16)])
-            else:
-                feats = [b[1](zj) for b, zj in zip(branches, ops.SplitChannelsFn.apply(z1, offs, mids))]
-                out = _proj([b[2] for b in branches], feats)
+            out = self._layer2(plan, z1)
             self._maps.append(out)
             o2o.append(out[:, : self.no])
             o2m.append(out[:, self.no:])
-            e_o2o.append(z1[:, offs[pos[6]]:offs[pos[6]] + mids[pos[6]]])
-            e_o2m.append(z1[:, offs[pos[14]]:offs[pos[14]] + mids[pos[14]]])
+            e_o2o.append(z1[:, o1:o1 + c1])
+            e_o2m.append(z1[:, om:om + cm])
         return o2o, o2m, e_o2o, e_o2m
+
+    def _layer2(self, plan, z1):
+        """second layer + projections of one level: z1 -> the (B, 2*no, H, W) map in canonical branch order"""
+        if not plan.layer2:
+            return self._layer2_per_branch(plan, z1)
+        return self._layer2_uniform(plan, z1) if plan.uniform else self._layer2_parts(plan, z1)
+
+    def _layer2_uniform(self, plan, z1):
+        s2, n = plan.layer2[0].stack, len(plan.branches)
+        proj = _proj_params([b[2] for b in plan.branches])
+        if self.fuse_bn_proj and plan.mids[0] % 64 == 0:
+            # grouped conv + BatchNorm statistics + projections with BatchNorm/SiLU applied on the fly (no activation tensor)
+            return ops.FusedConvBNProjFn.apply(z1, s2, n, plan.offs, plan.mids, 16, *s2.params(), *proj)
+        z2 = ops.FusedConvBNActFn.apply(z1, s2, n, None, *s2.params())
+        return ops.HeadProjSlicesFn.apply(z2, plan.offs, plan.mids, 16, *proj)
+
+    def _layer2_parts(self, plan, z1):
+        # cls | 14 regression branches (one grouped conv) | cls over channel views of z1; every split hands ONE gradient back
+        views = ops.SplitChannelsFn.apply(z1, [p.lo for p in plan.layer2], [p.hi - p.lo for p in plan.layer2])
+        done = []  # per branch in stack order: (projected, its slice of a projected map or its features)
+        for v, part in zip(views, plan.layer2):
+            done += self._part(plan.branches[part.branches], part, v)
+        if not any(projected for projected, _ in done):
+            return _proj([plan.branches[p][2] for p in plan.pos], [done[p][1] for p in plan.pos])
+        # project what is left one by one (none where every part is fused), then line the 16 outputs up
+        outs = [t if projected else _proj([b[2]], [t]) for (projected, t), b in zip(done, plan.branches)]
+        return cat([outs[p] for p in plan.pos])
+
+    def _part(self, brs, part, v):
+        """one part of the second layer over its channel view `v` of z1 -> per branch (True, its slice of the part's projected map) or
+        (False, its features)"""
+        g, w, s2 = part.groups, part.width, part.stack
+        if not (self.fuse_bn_proj and w % 64 == 0):
+            z2 = ops.FusedConvBNActFn.apply(v, s2, g, None, *s2.params())
+            return [(False, f) for f in ([z2] if g == 1 else ops.SplitChannelsFn.apply(z2, [j * w for j in range(g)], [w] * g))]
+        # this part's grouped conv + BatchNorm statistics + its projections with BatchNorm / SiLU on the fly (the matrix-core
+        # kernels of proj_bn_mfma.hip at 64 / 128 channels), as on the uniform heads: no activation tensor, no per-branch
+        # VALU projection launches (M-3D: 32 launches of proj_bwd_weight + 64 slab folds per step)
+        o = ops.FusedConvBNProjFn.apply(v, s2, g, [j * w for j in range(g)], [w] * g, g, *s2.params(), *_proj_params([b[2] for b in brs]))
+        outs, off = [], 0
+        for b in brs:
+            co = b[2].weight.shape[0]
+            outs.append((True, o[:, off:off + co]))
+            off += co
+        return outs
+
+    def _layer2_per_branch(self, plan, z1):
+        feats = [b[1](zj) for b, zj in zip(plan.branches, ops.SplitChannelsFn.apply(z1, plan.offs, plan.mids))]
+        return _proj([b[2] for b in plan.branches], feats)
 
     # ---- sparse (eval) path: head.py:656-716 -----------------------------------------------------------------
     def select_candidates(self, scores):
@@ -653,57 +729,51 @@ class v10Detect3d(nn.Module):
         L.patch_gather(dt, xi.data_ptr(), sb, sh, sw, idx.data_ptr(), patches.data_ptr(), B, H, W, C, K, ps, st)
         # a model folded by the reference's BaseModel.fuse() (no .bn on the branch Convs) runs branch by branch on forward_fuse
         folded = not hasattr(heads[1][i][0], "bn") if isinstance(heads[1][i][0], Conv) else False
-        _, mids, s1, s2, _, _ = self._stacks(i) if not (self.generic or folded) else (None,) * 6
-        if heads is self.o2o_heads and s2 is not None:
-            # the 7 regression branches of the one-to-one set as one stacked conv + one grouped conv on the patches
-            # (channel rows mid..8*mid of the training-time stacks), both unpadded: patch semantics of head.py:706-708
-            mid, c0 = mids[0], heads[1][i][0]
-            lo, hi = mid, 8 * mid
-            w1, g1, b1, rm1, rv1 = s1.tensors()
-            z1 = ops.conv_bn_act_eval(patches, w1[lo:hi], g1[lo:hi], b1[lo:hi], rm1[lo:hi], rv1[lo:hi], self.kernel_size_1, 1, 0, 1,
-                                      c0.has_act, c0.eps, s1.__dict__.setdefault("_eval_cache", {}), ver=s1.ver)
-            w2, g2, b2, rm2, rv2 = s2.tensors()
-            z2 = ops.conv_bn_act_eval(z1, w2[lo:hi], g2[lo:hi], b2[lo:hi], rm2[lo:hi], rv2[lo:hi], self.kernel_size_2, 1, 0, 7,
-                                      c0.has_act, c0.eps, s2.__dict__.setdefault("_eval_cache", {}), ver=s2.ver)
-            reg = ops.proj_slices_eval(z2, [j * mid for j in range(7)], mid, [heads[j][i][2].weight for j in range(1, 8)],
-                                       [heads[j][i][2].bias for j in range(1, 8)])[:, :, 0, 0]
+        plan = None if (self.generic or folded) else self._stacks(i)
+        if heads is self.o2o_heads and plan is not None and plan.uniform:
+            reg = self._patch_regression_stacked(plan, heads, i, patches)
         else:
-            feats = []
-            for j in range(1, 8):
-                br = heads[j][i]
-                # patch semantics, head.py:706-708: the branch's TOP-LEVEL Conv layers run unpadded (5x5 patch -> 1x1); the nested
-                # Sequentials of `dsconv` keep their padding there, and so here (the 5x5 result is then read at cell (0, 0) like the
-                # reference reads it).  Unlike the reference we do not leave the modules mutated.
-                convs = [l for l in list(br)[:-1] if isinstance(l, Conv)]
-                pads = [l.conv.padding for l in convs]
-                for l in convs:
-                    l.conv.padding = (0, 0)
-                try:
-                    f = patches
-                    for l in list(br)[:-1]:
-                        f = l(f)
-                    feats.append(f)
-                finally:
-                    for l, p0 in zip(convs, pads):
-                        l.conv.padding = p0
-            reg = _proj([heads[j][i][2] for j in range(1, 8)], feats)[:, :, 0, 0]  # (BK, 35)
-        reg = reg.contiguous()
+            reg = self._patch_regression_per_branch(heads, i, patches)
+        reg = reg.contiguous()  # (BK, 35)
         full = ops.nhwc_empty(B, self.no, H, W, cls.dtype, xi.device)
         L.head3d_scatter(dt, cls.data_ptr(), cls.stride(3), reg.data_ptr(), reg.stride(0), idx.data_ptr(), full.data_ptr(), B, H * W, self.nc,
                          self.no, K, st)
         return full
 
+    def _patch_regression_stacked(self, plan, heads, i, patches):
+        """the 7 regression branches of the one-to-one set as one stacked conv + one grouped conv on the patches (channel rows
+        mid..8*mid of the training-time stacks of the uniform layout), both unpadded: patch semantics of head.py:706-708"""
+        mid, c0, s1, s2 = plan.mids[0], heads[1][i][0], plan.s1, plan.layer2[0].stack
+        lo, hi = mid, 8 * mid
+        w1, g1, b1, rm1, rv1 = s1.tensors()
+        z1 = ops.conv_bn_act_eval(patches, w1[lo:hi], g1[lo:hi], b1[lo:hi], rm1[lo:hi], rv1[lo:hi], self.kernel_size_1, 1, 0, 1,
+                                  c0.has_act, c0.eps, s1.__dict__.setdefault("_eval_cache", {}), ver=s1.ver)
+        w2, g2, b2, rm2, rv2 = s2.tensors()
+        z2 = ops.conv_bn_act_eval(z1, w2[lo:hi], g2[lo:hi], b2[lo:hi], rm2[lo:hi], rv2[lo:hi], self.kernel_size_2, 1, 0, 7,
+                                  c0.has_act, c0.eps, s2.__dict__.setdefault("_eval_cache", {}), ver=s2.ver)
+        finals = [heads[j][i][2] for j in range(1, 8)]
+        return ops.proj_slices_eval(z2, [j * mid for j in range(7)], mid, [c.weight for c in finals], [c.bias for c in finals])[:, :, 0, 0]
+
+    def _patch_regression_per_branch(self, heads, i, patches):
+        feats = []
+        for j in range(1, 8):
+            layers = list(heads[j][i])[:-1]
+            # patch semantics, head.py:706-708: the branch's TOP-LEVEL Conv layers run unpadded (5x5 patch -> 1x1); the nested
+            # Sequentials of `dsconv` keep their padding there, and so here (the 5x5 result is then read at cell (0, 0) like the
+            # reference reads it).  Unlike the reference we do not leave the modules mutated.
+            with _unpadded([l for l in layers if isinstance(l, Conv)]):
+                f = patches
+                for l in layers:
+                    f = l(f)
+            feats.append(f)
+        return _proj([heads[j][i][2] for j in range(1, 8)], feats)[:, :, 0, 0]
+
     def decode(self, ys):
         """head.py:755-797: (B, no, A) fp32 with xyxy px boxes and centre-3d px (HIP kernel over the per-level NHWC maps)."""
-        import ctypes
+        ys, A, args = _decode_args(ys, self.no, self.stride)
         B = ys[0].shape[0]
-        nl = len(ys)
-        ys = [y if (y.dtype == ys[0].dtype and ops.px_dense(y) and y.stride(3) == self.no) else ops._dense_any(y, ys[0].dtype) for y in ys]
-        A = sum(y.shape[2] * y.shape[3] for y in ys)
         out = torch.empty(B, self.no, A, dtype=torch.float32, device=ys[0].device)
-        ops.lib().head3d_decode(ops.code(ys[0].dtype), nl, (ctypes.c_void_p * nl)(*[y.data_ptr() for y in ys]),
-                                (ctypes.c_int * nl)(*[y.shape[2] for y in ys]), (ctypes.c_int * nl)(*[y.shape[3] for y in ys]),
-                                (ctypes.c_float * nl)(*[float(s) for s in self.stride.tolist()[:nl]]), B, self.nc, out.data_ptr(), ops.stream())
+        ops.lib().head3d_decode(*args, B, self.nc, out.data_ptr(), ops.stream())
         return out
 
     def _probe(self, x):
@@ -800,18 +870,14 @@ class Detect(nn.Module):
     def inference(self, ys):
         """head.py:53-79: (B, 4+nc, A) fp32: xywh px boxes (DFL expectation + dist2bbox) + sigmoid scores - one HIP launch over the
         per-level NHWC maps (`y3d_head2d_decode`)"""
-        import ctypes
         if self.reg_max != 16:
             raise NotImplementedError("the DFL decode kernel is built for reg_max = 16")
-        B, nl = ys[0].shape[0], len(ys)
         if not ys[0].is_cuda:
             raise Y3DError("Detect.inference runs on the HIP kernel of post.hip: head maps must live on a HIP device")
-        ms = [y if (y.dtype == ys[0].dtype and ops.px_dense(y) and y.stride(3) == self.no) else ops._dense_any(y, ys[0].dtype) for y in ys]
-        A = sum(y.shape[2] * y.shape[3] for y in ms)
+        ms, A, args = _decode_args(ys, self.no, self.stride)
+        B = ms[0].shape[0]
         out = torch.empty(B, 4 + self.nc, A, dtype=torch.float32, device=ms[0].device)
-        ops.lib().head2d_decode(ops.code(ms[0].dtype), nl, (ctypes.c_void_p * nl)(*[y.data_ptr() for y in ms]),
-                                (ctypes.c_int * nl)(*[y.shape[2] for y in ms]), (ctypes.c_int * nl)(*[y.shape[3] for y in ms]),
-                                (ctypes.c_float * nl)(*[float(s) for s in self.stride.tolist()[:nl]]), B, self.nc, out.data_ptr(), ops.stream())
+        ops.lib().head2d_decode(*args, B, self.nc, out.data_ptr(), ops.stream())
         return out, ys
 
     def _probe(self, x, decode):
