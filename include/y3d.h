@@ -494,6 +494,25 @@ int y3d_json3d_encode_labels(const double* rec, const int* img_i, const double* 
                              int64_t* cls, double* bboxes, float* center_2d, float* size_2d, double* center_3d, double* size_3d,
                              double* depth, int64_t* heading_bin, double* heading_res, float* batch_idx, int* counts, double* calib,
                              double* ratio_pad, void* stream);
+/* Width of a row of y3d_json3d_plan_batch's draw table (float64 values). */
+enum { Y3D_JSON3D_DRAW_W = 18 };
+/* Batch plan over a Waymo / Omni3D split held in two tiers (json3d_cache.hip, json3d.DeviceSplit), one thread per image: the tables of
+ * y3d_kitti_plan_batch, for y3d_kitti_image_aug and y3d_json3d_encode_labels.  The frames at positions [0, n_dev) live in `arena` on
+ * the device, those at [n_dev, N) in pinned host memory; the ones a batch uses have been copied into `stage`, a device buffer of
+ * stage_bytes bytes, by the time this kernel runs.  Frame tables, on the device, indexed by dataset position: img_off (N) int64 byte
+ * offsets into arena, -1 at [n_dev, N) and never read there; frame_hw (N, 2) int32 (H, W); rec_span (N, 2) int32 = (first row, object
+ * count) in the split's records, a frame without annotations has a zero-length span at the running row; P2 (N, 2, 12) float64 = the
+ * calibration as read and the float32 one of the mirrored image, widened.  draws (B, Y3D_JSON3D_DRAW_W) float64 on the device,
+ * draws_host the same table in host memory: the sixteen columns of y3d_kitti_plan_batch, then the byte offset into stage of the
+ * primary's frame and of the partner's, -1 for a frame of the arena.  Refused from draws_host before the launch, nothing written: a
+ * position or partner that is no integer of [0, N) (partner: or -1); an offset other than -1 for a position below n_dev, or for no
+ * partner; for a position from n_dev on, an offset that is -1, negative, no integer multiple of 16 or not below stage_bytes.  arena
+ * may be NULL when n_dev == 0, stage when no row names an offset.  Outputs as y3d_kitti_plan_batch's: src / src2 = stage + offset or
+ * arena + img_off; img_f[:12] is a plain copy of P2[position][flip]. */
+int y3d_json3d_plan_batch(const int64_t* img_off, const int* frame_hw, const int* rec_span, const double* P2, int N, int n_dev,
+                          const unsigned char* arena, const unsigned char* stage, int64_t stage_bytes, const double* draws_host,
+                          const double* draws, int B, const unsigned char** src, const unsigned char** src2, int* hw, int* flip,
+                          double* trans_inv, int* img_i, double* img_f, unsigned char* mixed, void* stream);
 /* 2D input pipeline, image side of YOLODataset.__getitem__ (data/base.py load_image :147-182; data/augment.py Mosaic._mosaic4
  * :208-242, RandomPerspective :384-435, MixUp :337-344, RandomHSV :605-624, RandomFlip :651-681, Format._format_img :950-957) for a
  * batch, one launch (yolo2d_batch.hip states the arithmetic; float64, + - * / and floor only).  src: DEVICE table of n_src device

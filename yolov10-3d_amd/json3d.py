@@ -8,6 +8,9 @@ and the labels filtered and encoded by one launch of `y3d_json3d_encode_labels` 
 Predictions decode with the KITTI decoder and the dataset's own size table:
 `kitti.decode_preds(..., cls_mean_size=json3d.WAYMO_CLS_MEAN_SIZE)` for Waymo, the default (KITTI's table) for Omni3D.
 
+`DeviceSplit` keeps a split decoded and resident - in HBM and, behind what HBM may hold, in pinned host memory - and builds the same
+batches from it without opening a file (`plan_batch`, csrc/json3d_cache.hip).
+
 The compact form has the reference's collated dtypes.  One value differs within float32 rounding: the static layout
 stores `size_2d` as float32, so Waymo's float64 `size_2d` carries float32-rounded values.
 """
@@ -18,6 +21,7 @@ import torch
 from . import kitti, ops
 from ._lib import Y3DError, lib
 from .kitti import MAX_OBJS, PER_BOX
+from .resident import ResidentSplit, check_plan, span_table, upload
 
 DATASETS = {"waymo": 0, "omni3d": 1}  # the kernel's dataset mode
 RESOLUTION = (960, 640)  # W, H (waymo.py:31, omni3d.py:31)
@@ -210,9 +214,13 @@ def build_batch(json_file, indices, args, device, dataset="waymo", mode="train",
     and label work on the device.  `indices` are dataset positions (images in ascending id order).  -> every key collate_fn returns
     except ori_img; the per-box keys in encode_labels' static layout, or with compact=True (one read-back of the counts) in
     collate_fn's ragged shapes.  img_mode "uint8": (B, H, W, 3) uint8 for the stem; "float": the reference's (B, 3, H, W) float32.
-    `args.cam_dis` encodes the camera distance (the reference's datasets hard-code use_camera_dis = False)."""
+    `args.cam_dis` encodes the camera distance (the reference's datasets hard-code use_camera_dis = False).
+    json_file may also be a `DeviceSplit`: the same batch from the resident split, without any file access."""
     import numpy as np
     from PIL import Image
+    if isinstance(json_file, DeviceSplit):  # the split is resident (its own dataset): no file is touched
+        json_file.check_device(device)
+        return json_file.build_batch(indices, args, mode=mode, compact=compact, img_mode=img_mode)
     _dataset_mode(dataset)
     if torch.device(device).type != "cuda":
         raise Y3DError("build_batch: the batch is built on a HIP device (no host fallback)")
@@ -247,3 +255,156 @@ def build_batch(json_file, indices, args, device, dataset="waymo", mode="train",
     mixed = torch.tensor([int(d["mixed"]) for d in draws], dtype=torch.uint8).to(device)
     return kitti._batch(img, lab, [ids[p] for p in indices], [im.size for im in frames], draws, packed["mean_size"], mixed,
                         compact and (lambda counts: compact_labels(lab, counts, cam_dis, MAX_OBJS, dataset)))
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# the split resident in two tiers: decoded once into HBM and, behind what HBM may hold, into pinned host memory
+# ------------------------------------------------------------------------------------------------------------------------------
+_DRAW_W = 18  # a row of the draw table: kitti's sixteen columns, then the staging byte offset of the primary and of the partner (-1: arena)
+
+
+def draw_table(indices, draws, staged):
+    """sample_augment's draws for dataset positions `indices` -> the (B, 18) float64 draw table of `y3d_json3d_plan_batch`: the rows of
+    `kitti.draw_table`, then the byte offset of the primary's frame and of the partner's in the batch's staging buffer (`staged`:
+    {position: offset}, the host-tier frames), or -1 for a frame of the device arena and for no partner."""
+    import numpy as np
+    table = np.empty((len(indices), _DRAW_W), np.float64)
+    table[:, :16] = kitti.draw_table(indices, draws)
+    for row, p, d in zip(table, indices, draws):
+        row[16], row[17] = staged.get(p, -1), staged.get(d["partner"], -1)
+    return table
+
+
+def plan_batch(split, draws, draws_dev=None, out=None, spill=None):
+    """The per-image tables of `y3d_kitti_image_aug` and `y3d_json3d_encode_labels` for a table of draws over a DeviceSplit, one HIP
+    launch (`y3d_json3d_plan_batch`).  draws: (B, 18) float64 on the host (numpy or tensor), `draw_table`'s rows; draws_dev: the same
+    table on the device (uploaded here when None); spill: the batch's staging buffer, a uint8 tensor on the split's device that holds
+    the host-tier frames at the offsets the table names (None: the batch uses none).  The launcher refuses positions and partners
+    outside the split and staging offsets that do not fit the frame's tier or the buffer; that each staged frame also ends inside the
+    buffer is checked here, from the host sizes.  out: optionally the eight output tensors (at least B rows each; the first B are
+    written).  -> `kitti.plan_batch`'s dict."""
+    host, draws_dev, out = check_plan(draws, _DRAW_W, split.device, kitti.PLAN_TABLES, draws_dev, out)
+    nbytes = 0
+    if spill is not None:
+        if not torch.is_tensor(spill) or spill.dtype != torch.uint8 or spill.device != split.device or spill.dim() != 1 or not spill.is_contiguous():
+            raise Y3DError(f"plan_batch: the staging buffer must be a contiguous 1-D uint8 tensor on {split.device}")
+        nbytes = spill.numel()
+    N = len(split)
+    for b, row in enumerate(host.tolist()):
+        for what, pos, off in (("position", row[0], row[16]), ("partner", row[1], row[17])):
+            if off >= 0 and 0 <= pos < N and pos == int(pos) and off + int(split._frame_bytes[int(pos)]) > nbytes:
+                raise Y3DError(f"plan_batch: image {b}: {what} {pos:g} staged at {off:g} ends outside the staging buffer of {nbytes} bytes")
+    lib().json3d_plan_batch(split.img_off.data_ptr(), split.frame_hw.data_ptr(), split.rec_span.data_ptr(), split.P2.data_ptr(), N, split.n_dev,
+                            split.arena.data_ptr() if split.n_dev else None, spill.data_ptr() if nbytes else None, nbytes, host.data_ptr(),
+                            draws_dev.data_ptr(), host.shape[0], *[out[k].data_ptr() for k, _, _ in kitti.PLAN_TABLES], ops.stream())
+    return out
+
+
+class DeviceSplit(ResidentSplit):
+    """A Waymo / Omni3D split decoded once and kept resident: `DeviceSplit(json_file, dataset)` parses the split as `read_split` does,
+    reads the frame sizes from the image headers and lays the frames out in two tiers before anything is decoded or allocated
+    (`resident.tier_layout`).  Frames in dataset order go into one uint8 device arena (`arena`) while their bytes fit `max_bytes`
+    (default: half of the device's free memory); every frame behind the first one that does not fit goes into `host_arena`, allocated
+    pinned and written by the decoder threads directly; `n_dev` is the boundary.  A host tier of more than `host_bytes` is refused, so
+    the default 0 behaves like `kitti.DeviceSplit`: all in HBM, or refused.  Frames are held as originals only (the crop reads the
+    original pixels).  Device tables, indexed by dataset position: `img_off` (N) int64 (-1 in the host tier), `frame_hw` (N, 2) int32
+    (H, W), `rec` (R, 24) float64 = object_records of every frame in order, `rec_span` (N, 2) int32, `P2` (N, 2, 12) float64 (as read;
+    `flip_calib` of it, float32 widened), `mean_size`.  On the host: `P2_host`, `wh`, `n_lines`, `cam`, `ids`, `files`, `dataset`.
+
+    `build_batch` returns what `build_batch(json_file, ...)` returns, bit for bit, without touching a file: the draws, one
+    non-blocking copy per distinct host-tier frame of the batch from the pinned arena into a staging buffer, one non-blocking upload
+    of the draw table from a ring of pinned buffers and three launches (plan_batch, the image augmentation, the label encoder)."""
+
+    def __init__(self, json_file, dataset, mode="train", device="cuda", max_bytes=None, host_bytes=0, workers=8, overfit=False):
+        import numpy as np
+        from PIL import Image
+        _dataset_mode(dataset)
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise Y3DError(f"DeviceSplit: the split is held on a HIP device, not {dev} (no host fallback)")
+        if mode == "test":
+            raise Y3DError("DeviceSplit: the test split has no labels")
+        if int(workers) < 1 or int(host_bytes) < 0:
+            raise Y3DError(f"DeviceSplit: workers = {workers}, host_bytes = {host_bytes}")
+        if dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        sp = read_split(json_file, dataset, bool(overfit))
+        self.mode, self.dataset, self.ids = mode, dataset, list(sp.ids)
+        N = len(self.ids)
+        if N < 1:
+            raise Y3DError("DeviceSplit: the split lists no frame")
+        self.files = [sp.file(i) for i in self.ids]
+        # sizes from the image headers, the budget of both tiers before anything is decoded or allocated
+        self.wh = []
+        for f in self.files:
+            with Image.open(f) as im:
+                self.wh.append((int(im.size[0]), int(im.size[1])))
+        self._layout_tiers(dev, [(h, w) for w, h in self.wh], max_bytes, host_bytes)
+        recs = [sp.records(i) for i in self.ids]
+        self.P2_host = [sp.P2(i) for i in self.ids]
+        self.n_lines = [len(r) for r in recs]
+        self.cam = [(P[0, 2], P[1, 2], P[0, 0], P[1, 1]) for P in self.P2_host]
+        self.rec = upload(np.concatenate(recs) if sum(self.n_lines) else np.zeros((1, REC_W)), dev, torch.float64)
+        both = [np.stack((P.reshape(12), flip_calib(P, wh).astype(np.float64).reshape(12))) for P, wh in zip(self.P2_host, self.wh)]
+        self.P2 = upload(np.stack(both), dev, torch.float64)
+        self.mean_size = upload(np.asarray(CLS_MEAN_SIZE[dataset], np.float64).reshape(-1, 3), dev, torch.float64)
+
+        def decode(pos):
+            with Image.open(self.files[pos]) as im:
+                return np.array(im.convert("RGB"))
+
+        self._fill_tiers(span_table(self.n_lines), decode, lambda pos: f"frame {self.files[pos]}", workers, _DRAW_W)
+
+    def __len__(self):
+        return len(self.ids)
+
+    def frame_info(self, pos, primary=False):
+        """sample_augment's frame_info: ((cu, cv, fu, fv), objects, (W, H) or None).  The size is reported for a batch's primary
+        position only and None for a partner candidate, as `build_batch(json_file, ...)` reports them: the reference reads the
+        partner's size from the primary image (waymo.py:162), so a candidate is not turned down for its size."""
+        return self.cam[pos], self.n_lines[pos], (self.wh[pos] if primary else None)
+
+    def sample(self, indices, args, mode="train"):
+        """The draws of `build_batch(json_file, ...)` for `indices` from the same np.random state: one `kitti.sample_augment` per image,
+        whose first question is about the primary.  A drawn partner whose true size differs from the primary's is refused."""
+        draws = []
+        for pos in indices:
+            first = [True]
+
+            def frame_info(p, _first=first):
+                primary, _first[0] = _first[0], False
+                return self.frame_info(p, primary)
+
+            draws += kitti.sample_augment(len(self), [pos], frame_info, args, mode, MAX_OBJS, RESOLUTION)
+            d = draws[-1]
+            if d["mixed"] and self.wh[d["partner"]] != self.wh[pos]:
+                raise Y3DError(f"build_batch: mixup partner {d['partner']} of position {pos} has another size (the reference mixes "
+                               f"equal-sized frames only)")
+        return draws
+
+    def build_batch(self, indices, args, mode="train", compact=False, img_mode="uint8"):
+        """`build_batch(json_file, indices, args, device, dataset, ...)` from the resident split: the same dictionary, bit for bit.  With
+        compact=False nothing here waits for the device (but a ring buffer still in flight) and no file is opened."""
+        if mode == "test":
+            raise Y3DError("build_batch: the test split has no labels")
+        indices = [int(i) for i in indices]
+        N, B = len(self), len(indices)
+        if B < 1 or any(not 0 <= p < N for p in indices):
+            raise Y3DError(f"build_batch: {B} positions, all must lie in [0, {N})")
+        draws = self.sample(indices, args, mode)
+        with torch.cuda.device(self.device):
+            staged, spill = self._stage([p for pos, d in zip(indices, draws) for p in (pos, d["partner"])])
+            host, dev = self._ring.upload(draw_table(indices, draws, staged))
+            plan = plan_batch(self, host, dev, spill=spill)
+            W, H = RESOLUTION
+            if img_mode == "float":
+                img = torch.empty(B, 3, H, W, dtype=torch.float32, device=self.device)
+            else:
+                img = torch.empty(B, H, W, 3, dtype=torch.uint8, device=self.device)
+            lib().kitti_image_aug(plan["src"].data_ptr(), plan["src2"].data_ptr(), plan["hw"].data_ptr(), plan["flip"].data_ptr(),
+                                  plan["trans_inv"].data_ptr(), B, H, W, 0 if img_mode == "float" else 1, img.data_ptr(), ops.stream())
+            packed = {"rec": self.rec, "img_i": plan["img_i"], "img_f": plan["img_f"], "mean_size": self.mean_size, "dataset": self.dataset}
+            cam_dis = bool(getattr(args, "cam_dis", False))
+            lab = encode_labels(packed, RESOLUTION, args.min_depth_threshold, args.max_depth_threshold, cam_dis, MAX_OBJS)
+        return kitti._batch(img, lab, [self.ids[p] for p in indices], [self.wh[p] for p in indices], draws, self.mean_size, plan["mixed"],
+                            compact and (lambda counts: compact_labels(lab, counts, cam_dis, MAX_OBJS, self.dataset)))

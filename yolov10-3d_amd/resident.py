@@ -1,7 +1,9 @@
-"""What the splits held on the device share (`kitti.DeviceSplit`, `yolo2d.DeviceSplit`, `yolo2d.DeviceRectSplit`), and nothing that knows a
-dataset: the index lists of an epoch, the layout of the frame arena and its byte budget, the span table of the label rows, the decode of
-every frame into the arena, the ring of pinned draw tables, the checks of a plan kernel's tables, and `ResidentSplit`, the base class
-that holds the arena with its frame tables.
+"""What the splits held on the device share (`kitti.DeviceSplit`, `yolo2d.DeviceSplit`, `yolo2d.DeviceRectSplit`, `json3d.DeviceSplit`),
+and nothing that knows a dataset: the index lists of an epoch, the layout of the frame arena and its byte budget, the span table of
+the label rows, the decode of every frame into the arena, the ring of pinned draw tables, the checks of a plan kernel's tables, and
+`ResidentSplit`, the base class that holds the arena with its frame tables.  A split may keep the frames that its device budget cannot
+hold in a second tier, one pinned host arena (`tier_layout`, `fill_pinned`, `load_pinned`, `stage_layout`, `stage_frames`, `ResidentSplit._layout_tiers`
+/ `_fill_tiers` / `_stage`); `json3d.DeviceSplit` is the one that does.
 """
 from __future__ import annotations
 
@@ -44,6 +46,71 @@ def arena_layout(hw, max_bytes, device, who):
     if nbytes > allowed:
         raise Y3DError(f"{who}: the {len(hw)} decoded frames need {nbytes} bytes, {allowed} bytes are allowed (max_bytes)")
     return offsets, padded, nbytes
+
+
+def tier_layout(hw, max_bytes, host_bytes, device, who):
+    """`arena_layout` over two tiers.  Frames in dataset order go into the device arena while their padded bytes fit `max_bytes` (None:
+    half of the free memory of `device`); every frame from the first one that does not fit goes into one pinned host arena, a smaller
+    later one too, so the tiers meet at a single boundary.  -> (n_dev, offsets (N) int64, padded (N) int64, nbytes, host_offsets (N)
+    int64, host_nbytes): positions [0, n_dev) lie at `offsets` in the device arena of `nbytes` bytes, positions [n_dev, N) at
+    `host_offsets` in the host arena of `host_nbytes` bytes; the other tier's entry is -1; every offset is a multiple of 16.  Raises
+    when the host tier needs more than `host_bytes` (with host_bytes = 0: `arena_layout`'s refusal, and its layout when all fits);
+    nothing has been decoded or allocated by then."""
+    hw = np.asarray(hw, np.int64).reshape(-1, 2)
+    N = len(hw)
+    padded = (hw[:, 0] * hw[:, 1] * 3 + ALIGN - 1) // ALIGN * ALIGN
+    ends = np.cumsum(padded)
+    allowed = int(max_bytes) if max_bytes is not None else torch.cuda.mem_get_info(device)[0] // 2
+    host_bytes = int(host_bytes)
+    n_dev = int(np.searchsorted(ends, allowed, side="right"))  # the first frame whose end lies behind the budget
+    if n_dev < N and host_bytes == 0:
+        raise Y3DError(f"{who}: the {N} decoded frames need {int(ends[-1])} bytes, {allowed} bytes are allowed (max_bytes)")
+    nbytes = int(ends[n_dev - 1]) if n_dev else 0
+    host_nbytes = int(ends[-1]) - nbytes if N else 0
+    if host_nbytes > host_bytes:
+        raise Y3DError(f"{who}: the {N - n_dev} decoded frames behind the {n_dev} that fit the device ({allowed} bytes, max_bytes) need "
+                       f"{host_nbytes} bytes of pinned host memory, {host_bytes} bytes are allowed (host_bytes)")
+    starts = np.concatenate(([0], ends[:-1])).astype(np.int64)
+    host = np.arange(N) >= n_dev
+    return n_dev, np.where(host, -1, starts), padded, nbytes, np.where(host, starts - nbytes, -1), host_nbytes
+
+
+def stage_layout(positions, n_dev, padded):
+    """The staging buffer of one batch: the distinct host-tier positions (>= n_dev) among `positions` (primaries and partners; negative:
+    none) in the order of their first use, each once, at padded offsets.  -> ({position: byte offset}, nbytes)"""
+    at, nbytes = {}, 0
+    for p in positions:
+        p = int(p)
+        if p >= n_dev and p not in at:
+            at[p] = nbytes
+            nbytes += int(padded[p])
+    return at, nbytes
+
+
+def fill_pinned(arena, offsets, positions, decode, pool):
+    """Fills a pinned uint8 host arena: the threads of `pool` decode the frames at `positions` (`decode(pos)` -> (H, W, 3) uint8, as
+    `fill_arena` takes it) and write each straight to byte offsets[pos] of the arena, with no pageable copy in between."""
+    flat = arena.numpy()
+
+    def put(pos):
+        px = decode(pos)
+        o = int(offsets[pos])
+        flat[o:o + px.size] = px.reshape(-1)
+
+    list(pool.map(put, positions))
+
+
+def stage_frames(arena, offsets, nbytes_of, at, nbytes, device):
+    """`stage_layout`'s frames from the pinned host arena into a device buffer of the batch's own, one non-blocking copy per frame on
+    the current stream.  The buffer comes from the caching allocator, so whoever gets its memory next is ordered behind the kernels
+    that read it by the stream alone.  -> the buffer (nbytes) uint8, or None when the batch uses no host-tier frame"""
+    if not at:
+        return None
+    buf = torch.empty(nbytes, dtype=torch.uint8, device=device)
+    for pos, o in at.items():
+        n, h = int(nbytes_of[pos]), int(offsets[pos])
+        buf[o:o + n].copy_(arena[h:h + n], non_blocking=True)
+    return buf
 
 
 def span_table(rows):
@@ -92,6 +159,22 @@ def load_arena(arena, offsets, padded, hw, decode, name, workers, chunk):
 
     with ThreadPoolExecutor(max_workers=min(int(workers), 16)) as pool:
         fill_arena(arena, offsets, padded, checked, pool, chunk)
+
+
+def load_pinned(arena, offsets, positions, hw, decode, name, workers):
+    """`fill_pinned` through a pool of `min(workers, 16)` threads of its own, with `load_arena`'s refusal of a frame that does not decode
+    to the (h, w, 3) its header gave."""
+    from concurrent.futures import ThreadPoolExecutor
+
+    def checked(pos):
+        px = decode(pos)
+        h, w = int(hw[pos][0]), int(hw[pos][1])
+        if px.shape != (h, w, 3):
+            raise Y3DError(f"{name(pos)} decodes to {px.shape}, its header said {(h, w, 3)}")
+        return px
+
+    with ThreadPoolExecutor(max_workers=min(int(workers), 16)) as pool:
+        fill_pinned(arena, offsets, positions, checked, pool)
 
 
 class DrawRing:
@@ -167,14 +250,48 @@ class ResidentSplit:
                    self.CHUNK)
         self._ring = DrawRing(draw_w, dev, self.RING)
 
+    n_dev = host_arena = None  # one tier unless a subclass lays out two (`_layout_tiers`): every frame in the device arena
+
+    def _layout_tiers(self, device, hw, max_bytes, host_bytes):
+        """`_layout` over two tiers (`tier_layout`): also `n_dev`, `host_offsets`, `host_nbytes`.  `offsets` holds -1 behind n_dev."""
+        self._hw = np.asarray(hw, np.int64).reshape(-1, 2)
+        self.n_dev, self.offsets, self._padded, self.nbytes, self.host_offsets, self.host_nbytes = tier_layout(
+            self._hw, max_bytes, host_bytes, device, type(self).__name__)
+        self._frame_bytes = self._hw[:, 0] * self._hw[:, 1] * 3
+        self.device = device if device.index is not None else torch.device("cuda", torch.cuda.current_device())
+
+    def _fill_tiers(self, span, decode, name, workers, draw_w):
+        """`_fill` over two tiers: the first `n_dev` frames reach the device arena as there, the rest are decoded by the same number of
+        threads straight into `host_arena`, which is allocated pinned."""
+        dev, n = self.device, self.n_dev
+        self.rec_span, self.img_off = upload(span, dev, torch.int32), upload(self.offsets, dev, torch.int64)
+        self.frame_hw = upload(self._hw, dev, torch.int32)
+        self.arena = torch.empty(self.nbytes, dtype=torch.uint8, device=dev)
+        named = lambda pos: f"{type(self).__name__}: {name(pos)}"
+        if n:
+            load_arena(self.arena, self.offsets[:n], self._padded[:n], self._hw, decode, named, workers, self.CHUNK)
+        self.host_arena = torch.empty(self.host_nbytes, dtype=torch.uint8, pin_memory=self.host_nbytes > 0)
+        if n < len(self._hw):
+            load_pinned(self.host_arena, self.host_offsets, range(n, len(self._hw)), self._hw, decode, named, workers)
+        self._ring = DrawRing(draw_w, dev, self.RING)
+
+    def _stage(self, positions):
+        """the distinct host-tier frames among `positions` staged on the device -> ({position: byte offset}, buffer or None)"""
+        at, nbytes = stage_layout(positions, self.n_dev, self._padded)
+        return at, stage_frames(self.host_arena, self.host_offsets, self._frame_bytes, at, nbytes, self.device)
+
     def check_device(self, device):
         d = torch.device(device)
         if d.type != "cuda" or (d.index is not None and d.index != self.device.index):
             raise Y3DError(f"build_batch: the split lives on {self.device}, a batch on {d} was asked for")
 
     def frame(self, pos):
-        """the decoded frame at a dataset position: an (h, w, 3) uint8 view of the arena"""
+        """the decoded frame at a dataset position: an (h, w, 3) uint8 view of the arena (of the pinned host arena for a position of the
+        host tier)"""
         h, w = int(self._hw[pos][0]), int(self._hw[pos][1])
+        if self.n_dev is not None and pos >= self.n_dev:
+            o = int(self.host_offsets[pos])
+            return self.host_arena[o:o + h * w * 3].view(h, w, 3)
         o = int(self.offsets[pos])
         return self.arena[o:o + h * w * 3].view(h, w, 3)
 

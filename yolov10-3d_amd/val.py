@@ -92,6 +92,7 @@ class _Validator:
 class Validator3d(_Validator):
     """`YOLOv10_3DDetectionValidator` for a KITTI root or split file (dataset="kitti") or a Waymo / Omni3D split JSON.  A KITTI split
     may also be passed as a `kitti.DeviceSplit`: its frames are validated in its own order, batches are built without file access.
+    So may a Waymo / Omni3D split as a `json3d.DeviceSplit`, with `dataset` = the split's own.
 
     Per batch of `batch` consecutive dataset positions: the val batch, the eval forward, `v10_3Dpostprocess`,
     `kitti.decode_preds_device` with the dataset's mean sizes and threshold = conf, `BoxStats.update_3d`, and
@@ -120,6 +121,8 @@ class Validator3d(_Validator):
             raise Y3DError(f"Validator3d: batch = {batch}")
         if isinstance(root_or_split, kitti.DeviceSplit) and dataset != "kitti":
             raise Y3DError(f"Validator3d: a kitti.DeviceSplit holds a KITTI split, not dataset {dataset!r}")
+        if isinstance(root_or_split, json3d.DeviceSplit) and dataset != root_or_split.dataset:
+            raise Y3DError(f"Validator3d: this json3d.DeviceSplit holds a {root_or_split.dataset} split, not dataset {dataset!r}")
         self.source, self.dataset, self.batch = root_or_split, dataset, int(batch)
         self.args = args if args is not None else kitti.data_args()
         self.resolution = (int(resolution[0]), int(resolution[1])) if dataset == "kitti" else json3d.RESOLUTION
@@ -133,7 +136,7 @@ class Validator3d(_Validator):
 
     def _projection(self):
         """-> position -> the original image's P2 (3, 4), next to `_dataset`'s six constants"""
-        if isinstance(self.source, kitti.DeviceSplit):
+        if isinstance(self.source, (kitti.DeviceSplit, json3d.DeviceSplit)):
             return lambda pos: self.source.P2_host[pos]
         if self.dataset == "kitti":
             data, ids = kitti._split(self.source, "val")
@@ -164,10 +167,11 @@ class Validator3d(_Validator):
         if self.dataset == "kitti":
             data, ids = kitti._split(self.source, "val")
             return len(ids), lambda pos: kitti.calib_params(kitti.read_calib(os.path.join(data, "calib", f"{ids[pos]:06d}.txt"))), data
-        sp = json3d.read_split(self.source, self.dataset, bool(getattr(self.args, "overfit", False)))
+        resident = isinstance(self.source, json3d.DeviceSplit)  # its host tables: the float64 projections as read
+        sp = self.source if resident else json3d.read_split(self.source, self.dataset, bool(getattr(self.args, "overfit", False)))
 
         def calib(pos):
-            P = sp.P2(sp.ids[pos])
+            P = sp.P2_host[pos] if resident else sp.P2(sp.ids[pos])
             return (P[0, 2], P[1, 2], P[0, 0], P[1, 1], P[0, 3] / -P[0, 0], P[1, 3] / -P[1, 1])
 
         return len(sp), calib, None
