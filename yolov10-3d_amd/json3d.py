@@ -176,12 +176,8 @@ def compact_labels(static, counts, use_camera_dis=False, max_objs=MAX_OBJS, data
     """`kitti.compact_labels` with these datasets' dtypes: positions and yaw are float64 here, so depth (crops = all True) and
     heading_res are float64 in every image, and Waymo's recomputed box makes its size_2d float64 (Omni3D's stays float32 unless an
     image without boxes promotes it).  heading_res is gathered again from the static float64 column, not widened from float32."""
-    out = kitti.compact_labels(static, counts, [True] * len(counts), use_camera_dis, max_objs)
-    rows = torch.cat([torch.arange(b * max_objs, b * max_objs + int(c)) for b, c in enumerate(counts)]).to(static["cls"].device)
-    out["heading_res"] = static["heading_res"].index_select(0, rows).to(torch.float64)
-    if _dataset_mode(dataset) == 0:
-        out["size_2d"] = out["size_2d"].to(torch.float64)
-    return out
+    wider = {"heading_res": torch.float64, **({"size_2d": torch.float64} if _dataset_mode(dataset) == 0 else {})}
+    return kitti._compact(static, counts, [True] * len(counts), use_camera_dis, max_objs, wider)
 
 
 def decode_batch_device(batch, calibs, P2=None, undo_augment=True, dataset="waymo", use_camera_dis=False, cls_mean_size=None):
@@ -319,27 +315,12 @@ class DeviceSplit(ResidentSplit):
         import numpy as np
         from PIL import Image
         _dataset_mode(dataset)
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise Y3DError(f"DeviceSplit: the split is held on a HIP device, not {dev} (no host fallback)")
-        if mode == "test":
-            raise Y3DError("DeviceSplit: the test split has no labels")
-        if int(workers) < 1 or int(host_bytes) < 0:
-            raise Y3DError(f"DeviceSplit: workers = {workers}, host_bytes = {host_bytes}")
-        if dev.index is None:
-            dev = torch.device("cuda", torch.cuda.current_device())
+        dev = self._accept(device, mode, workers, host_bytes)
         sp = read_split(json_file, dataset, bool(overfit))
-        self.mode, self.dataset, self.ids = mode, dataset, list(sp.ids)
-        N = len(self.ids)
-        if N < 1:
-            raise Y3DError("DeviceSplit: the split lists no frame")
+        self.dataset, self.ids = dataset, list(sp.ids)
         self.files = [sp.file(i) for i in self.ids]
         # sizes from the image headers, the budget of both tiers before anything is decoded or allocated
-        self.wh = []
-        for f in self.files:
-            with Image.open(f) as im:
-                self.wh.append((int(im.size[0]), int(im.size[1])))
-        self._layout_tiers(dev, [(h, w) for w, h in self.wh], max_bytes, host_bytes)
+        self._layout_tiers(dev, self._sizes(self.files), max_bytes, host_bytes)
         recs = [sp.records(i) for i in self.ids]
         self.P2_host = [sp.P2(i) for i in self.ids]
         self.n_lines = [len(r) for r in recs]
@@ -392,19 +373,11 @@ class DeviceSplit(ResidentSplit):
         if B < 1 or any(not 0 <= p < N for p in indices):
             raise Y3DError(f"build_batch: {B} positions, all must lie in [0, {N})")
         draws = self.sample(indices, args, mode)
+        cam_dis = bool(getattr(args, "cam_dis", False))
         with torch.cuda.device(self.device):
             staged, spill = self._stage([p for pos, d in zip(indices, draws) for p in (pos, d["partner"])])
             host, dev = self._ring.upload(draw_table(indices, draws, staged))
             plan = plan_batch(self, host, dev, spill=spill)
-            W, H = RESOLUTION
-            if img_mode == "float":
-                img = torch.empty(B, 3, H, W, dtype=torch.float32, device=self.device)
-            else:
-                img = torch.empty(B, H, W, 3, dtype=torch.uint8, device=self.device)
-            lib().kitti_image_aug(plan["src"].data_ptr(), plan["src2"].data_ptr(), plan["hw"].data_ptr(), plan["flip"].data_ptr(),
-                                  plan["trans_inv"].data_ptr(), B, H, W, 0 if img_mode == "float" else 1, img.data_ptr(), ops.stream())
-            packed = {"rec": self.rec, "img_i": plan["img_i"], "img_f": plan["img_f"], "mean_size": self.mean_size, "dataset": self.dataset}
-            cam_dis = bool(getattr(args, "cam_dis", False))
-            lab = encode_labels(packed, RESOLUTION, args.min_depth_threshold, args.max_depth_threshold, cam_dis, MAX_OBJS)
+            img, lab = kitti._resident_tail(self, plan, args, cam_dis, img_mode, RESOLUTION, encode_labels, dataset=self.dataset)
         return kitti._batch(img, lab, [self.ids[p] for p in indices], [self.wh[p] for p in indices], draws, self.mean_size, plan["mixed"],
                             compact and (lambda counts: compact_labels(lab, counts, cam_dis, MAX_OBJS, self.dataset)))

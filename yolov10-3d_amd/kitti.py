@@ -543,11 +543,16 @@ def compact_labels(static, counts, crops, use_camera_dis=False, max_objs=MAX_OBJ
     """Static layout -> the ragged per-box tensors `collate_fn` returns, in its shapes and dtypes.  torch.cat promotes over every
     image's tensor: an image without boxes contributes a float64 (0,) tensor (bboxes: float32), an image's depth is float32 when it was
     neither cropped nor encoded as camera distance, heading_res and the 2D centre / size are float32.  counts: host ints (B,)."""
+    return _compact(static, counts, crops, use_camera_dis, max_objs, {})
+
+
+def _compact(static, counts, crops, use_camera_dis, max_objs, wider):
+    """compact_labels of this module and of json3d.  wider: {key: dtype} of the per-box keys a dataset holds in a wider dtype"""
     B = len(counts)
     rows = torch.cat([torch.arange(b * max_objs, b * max_objs + int(c)) for b, c in enumerate(counts)]).to(static["cls"].device)
     total = int(sum(int(c) for c in counts))
     own = {"cls": torch.int64, "bboxes": torch.float64, "center_2d": torch.float32, "size_2d": torch.float32, "center_3d": torch.float64,
-           "size_3d": torch.float64, "heading_bin": torch.int64, "heading_res": torch.float32, "batch_idx": torch.float32}
+           "size_3d": torch.float64, "heading_bin": torch.int64, "heading_res": torch.float32, "batch_idx": torch.float32, **wider}
     out = {}
     for k in PER_BOX:
         dts = []
@@ -597,6 +602,21 @@ def _batch(img, lab, ids, sizes, draws, mean_size, mixed, compact):
     else:
         batch.update({k: lab[k] for k in PER_BOX})
     return batch
+
+
+def _resident_tail(split, plan, args, cam_dis, img_mode, resolution, encode, **packed):
+    """What a resident split's `build_batch` launches behind its plan (json3d's too): the images of `img_mode` by `kitti_image_aug`
+    from the plan's tables, and the labels by `encode` (this module's encode_labels or json3d's; packed: what its dict holds beyond
+    the split's records and the plan's tables).  -> (img, lab)"""
+    B, W, H = plan["img_i"].shape[0], int(resolution[0]), int(resolution[1])
+    if img_mode == "float":
+        img = torch.empty(B, 3, H, W, dtype=torch.float32, device=split.device)
+    else:
+        img = torch.empty(B, H, W, 3, dtype=torch.uint8, device=split.device)
+    lib().kitti_image_aug(plan["src"].data_ptr(), plan["src2"].data_ptr(), plan["hw"].data_ptr(), plan["flip"].data_ptr(),
+                          plan["trans_inv"].data_ptr(), B, H, W, 0 if img_mode == "float" else 1, img.data_ptr(), ops.stream())
+    packed = dict(rec=split.rec, img_i=plan["img_i"], img_f=plan["img_f"], mean_size=split.mean_size, **packed)
+    return img, encode(packed, resolution, args.min_depth_threshold, args.max_depth_threshold, cam_dis, MAX_OBJS)
 
 
 def build_batch(root_or_split_file, indices, args, device, mode="train", compact=False, img_mode="uint8", resolution=RESOLUTION):
@@ -716,27 +736,11 @@ class DeviceSplit(ResidentSplit):
         import numpy as np
         from concurrent.futures import ThreadPoolExecutor
         from PIL import Image
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise Y3DError(f"DeviceSplit: the split is held on a HIP device, not {dev} (no host fallback)")
-        if mode == "test":
-            raise Y3DError("DeviceSplit: the test split has no labels")
-        if int(workers) < 1:
-            raise Y3DError(f"DeviceSplit: workers = {workers}")
-        if dev.index is None:
-            dev = torch.device("cuda", torch.cuda.current_device())
-        self.mode = mode
+        dev = self._accept(device, mode, workers)
         self.data, self.ids = _split(root_or_split_file, mode)
-        N = len(self.ids)
-        if N < 1:
-            raise Y3DError("DeviceSplit: the split lists no frame")
         path = lambda sub, i, ext: os.path.join(self.data, sub, f"{i:06d}.{ext}")
         # sizes from the PNG headers, the budget before anything is decoded or allocated
-        self.wh = []
-        for i in self.ids:
-            with Image.open(path("image_2", i, "png")) as im:
-                self.wh.append((int(im.size[0]), int(im.size[1])))
-        self._layout(dev, [(h, w) for w, h in self.wh], max_bytes)
+        self._layout(dev, self._sizes([path("image_2", i, "png") for i in self.ids]), max_bytes)
 
         # labels and calibrations, both projections of every frame
         def tables(pos):
@@ -744,7 +748,7 @@ class DeviceSplit(ResidentSplit):
             return label_records(read_label(path("label_2", self.ids[pos], "txt"))), P, flip_calib(P, self.wh[pos])
 
         with ThreadPoolExecutor(max_workers=min(int(workers), 16)) as pool:
-            recs, self.P2_host, flipped = zip(*pool.map(tables, range(N)))
+            recs, self.P2_host, flipped = zip(*pool.map(tables, range(len(self.ids))))
         self.n_lines = [len(r) for r in recs]
         self.cam = [(float(P[0, 2]), float(P[1, 2]), float(P[0, 0]), float(P[1, 1])) for P in self.P2_host]
         self.rec = upload(np.concatenate(recs) if sum(self.n_lines) else np.zeros((1, _REC_W)), dev, torch.float64)
@@ -780,20 +784,13 @@ class DeviceSplit(ResidentSplit):
         for pos, d in zip(indices, draws):
             if d["mixed"] and self.wh[d["partner"]] != self.wh[pos]:
                 raise Y3DError(f"build_batch: mixup partner {d['partner']} of position {pos} has another size")
+        cam_dis = bool(args.cam_dis)
         with torch.cuda.device(self.device):
             host, dev = self._ring.upload(draw_table(indices, draws))
             plan = plan_batch(self, host, dev)
-            W, H = int(resolution[0]), int(resolution[1])
-            if img_mode == "float":
-                img = torch.empty(B, 3, H, W, dtype=torch.float32, device=self.device)
-            else:
-                img = torch.empty(B, H, W, 3, dtype=torch.uint8, device=self.device)
-            lib().kitti_image_aug(plan["src"].data_ptr(), plan["src2"].data_ptr(), plan["hw"].data_ptr(), plan["flip"].data_ptr(),
-                                  plan["trans_inv"].data_ptr(), B, H, W, 0 if img_mode == "float" else 1, img.data_ptr(), ops.stream())
-            packed = {"rec": self.rec, "img_i": plan["img_i"], "img_f": plan["img_f"], "mean_size": self.mean_size}
-            lab = encode_labels(packed, resolution, args.min_depth_threshold, args.max_depth_threshold, bool(args.cam_dis), MAX_OBJS)
+            img, lab = _resident_tail(self, plan, args, cam_dis, img_mode, resolution, encode_labels)
         return _batch(img, lab, [self.ids[p] for p in indices], [self.wh[p] for p in indices], draws, self.mean_size, plan["mixed"],
-                      compact and (lambda counts: compact_labels(lab, counts, [d["crop"] for d in draws], bool(args.cam_dis))))
+                      compact and (lambda counts: compact_labels(lab, counts, [d["crop"] for d in draws], cam_dis)))
 
 
 def save_results(results, output_dir="./outputs", class_name=("Car", "Pedestrian", "Cyclist")):

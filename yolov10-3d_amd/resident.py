@@ -233,6 +233,31 @@ class ResidentSplit:
     RING = 4  # pinned draw tables in flight
     CHUNK = 256 << 20  # bytes of decoded frames per upload
 
+    def _accept(self, device, mode, workers, host_bytes=None):
+        """The checks a labelled split's constructor makes before it reads anything (host_bytes: only for a split with a host tier);
+        sets `mode`.  -> the device with its index"""
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise Y3DError(f"DeviceSplit: the split is held on a HIP device, not {dev} (no host fallback)")
+        if mode == "test":
+            raise Y3DError("DeviceSplit: the test split has no labels")
+        if int(workers) < 1 or (host_bytes is not None and int(host_bytes) < 0):
+            raise Y3DError(f"DeviceSplit: workers = {workers}" + ("" if host_bytes is None else f", host_bytes = {host_bytes}"))
+        self.mode = mode
+        return dev if dev.index is not None else torch.device("cuda", torch.cuda.current_device())
+
+    def _sizes(self, files):
+        """The split's image files -> `wh`, every frame's (W, H) from the file headers alone; refuses a split without frames.
+        -> (h, w) per frame, what `_layout` takes"""
+        from PIL import Image
+        if len(files) < 1:
+            raise Y3DError("DeviceSplit: the split lists no frame")
+        self.wh = []
+        for f in files:
+            with Image.open(f) as im:
+                self.wh.append((int(im.size[0]), int(im.size[1])))
+        return [(h, w) for w, h in self.wh]
+
     def _layout(self, device, hw, max_bytes):
         """(h, w) per frame -> `offsets`, `nbytes`: the budget before anything is decoded or allocated, then `device` with its index"""
         self._hw = np.asarray(hw, np.int64).reshape(-1, 2)
