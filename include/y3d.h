@@ -444,6 +444,13 @@ int y3d_kitti_image_aug(const unsigned char* const* src, const unsigned char* co
  * 64 KiB of LDS; more is an error and nothing is written. */
 int y3d_kde_depth_fusion(const float* predsO, int B, int K, const float* predsM, int KM, int C, float thres, float iou_thres, int nprop,
                          float* out, void* stream);
+/* Depth of the 3D validator's rows from a supplied depth map — YOLOv10_3DDetectionValidator.dino_depth_pred models/yolov10_3D/val.py:61-76:
+ * rows (B, K, C) post-processed rows [xyxy | centre-3d x (4), y (5), network-input pixels | ... | depth (C-4) | ...], map (B, Hm, Wm),
+ * all fp32; out (B, K, C) = rows with column C-4 replaced by map[b, iy, ix], ix = column 4 truncated toward zero and clamped to
+ * [0, Wm-1], iy the same from column 5 and Hm.  The clamp is done in float BEFORE the conversion: !(c >= 0) -> 0, c >= dim -> dim-1, so a
+ * NaN reads index 0 and a huge value the last index (the reference's `.long()` is undefined for both).  C >= 8, no empty size, out must
+ * not overlap rows or map, no NULL: otherwise an error and nothing is written. */
+int y3d_rows_depth_from_map(const float* rows, int B, int K, int C, const float* map, int Hm, int Wm, float* out, void* stream);
 /* KITTI decode of the post-processed detections (data/datasets/kitti.py:519-576 `decode_preds`, called by the validator's
  * `_prepare_preds`, models/yolov10_3D/val.py:210-214).  preds (B, K, 37) fp32 rows [xyxy | centre-3d | size residual | 24 heading |
  * depth | depth log-variance | score logit | label]; calib (B, 6) = (cu, cv, fu, fv, tx, ty) of the original image; ratio (B, 2) =

@@ -502,6 +502,31 @@ __global__ __launch_bounds__(256) void kitti_decode_kernel(const float* __restri
   keep[idx] = v[13] < threshold ? 0 : 1;
 }
 
+// float coordinate -> index into a dimension of `dim` cells: truncation toward zero, clamped IN FLOAT before the conversion (a NaN or a
+// negative value reads cell 0, anything >= dim the last cell; the conversion itself then only sees 0 <= c < dim)
+__device__ __forceinline__ int map_index(float c, int dim) {
+  if (!(c >= 0.f)) return 0;
+  if (c >= (float)dim) return dim - 1;
+  return (int)c;
+}
+
+// dino_depth_pred (val.py:61-76): out = rows with the depth column read from the map at the truncated centre-3d; one thread per element
+// (rows of 37 floats are not 16-byte aligned and a batch of 32 is 237 KB: dword accesses, coalesced along the row; the launch is the cost)
+__global__ __launch_bounds__(256) void rows_depth_from_map_kernel(const float* __restrict__ rows, const float* __restrict__ map, float* __restrict__ out,
+                                                                  long total, int K, int C, int Hm, int Wm) {
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+    const int c = (int)(i % C);
+    float v = rows[i];
+    if (c == C - 4) {
+      const long row = i / C;
+      const float* r = rows + row * C;
+      const int ix = map_index(r[4], Wm), iy = map_index(r[5], Hm);
+      v = map[((row / K) * Hm + iy) * Wm + ix];
+    }
+    out[i] = v;
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -642,6 +667,17 @@ int y3d_kitti_decode(const float* preds, int B, int K, const double* calib, cons
   Y3D_CHECK(preds && calib && ratio && mean_size && out && keep, "kitti_decode: null argument");
   hipLaunchKernelGGL(kitti_decode_kernel, dim3((B * K + 255) / 256), dim3(256), 0, (hipStream_t)stream, preds, B, K, calib, ratio, inv_trans, mean_size,
                      nc, use_camera_dis, threshold, out, keep);
+  Y3D_LAUNCH_CHECK();
+  return Y3D_OK;
+}
+
+int y3d_rows_depth_from_map(const float* rows, int B, int K, int C, const float* map, int Hm, int Wm, float* out, void* stream) {
+  Y3D_CHECK(rows && map && out, "rows_depth_from_map: null argument");
+  Y3D_CHECK(B >= 1 && K >= 1 && C >= 8 && Hm >= 1 && Wm >= 1, "rows_depth_from_map: bad sizes (B=%d, K=%d, C=%d, map %d x %d; C >= 8)", B, K, C, Hm, Wm);
+  const long total = (long)B * K * C, cells = (long)B * Hm * Wm;
+  const uintptr_t o0 = (uintptr_t)out, o1 = o0 + total * 4, r0 = (uintptr_t)rows, m0 = (uintptr_t)map;
+  Y3D_CHECK((o1 <= r0 || r0 + total * 4 <= o0) && (o1 <= m0 || m0 + cells * 4 <= o0), "rows_depth_from_map: out overlaps an input");
+  hipLaunchKernelGGL(rows_depth_from_map_kernel, dim3(ew_grid(total)), dim3(256), 0, (hipStream_t)stream, rows, map, out, total, K, C, Hm, Wm);
   Y3D_LAUNCH_CHECK();
   return Y3D_OK;
 }

@@ -274,6 +274,26 @@ def aggregate_o2m_preds(predsO, predsM, thres=0.1, iou_thres=0.9, nprop=500):
     return out
 
 
+def depth_from_map(rows, depth_maps):
+    """`YOLOv10_3DDetectionValidator.dino_depth_pred` (val.py:61-76) without the depth network: rows (B, K, C) post-processed rows and
+    depth_maps (B, Hm, Wm) on the device -> a new (B, K, C) float32 tensor, rows with the depth column (C - 4) read from the map at the
+    centre-3d (columns 4, 5: network-input pixels) truncated toward zero and clamped to the map; NaN and negative centres read index 0
+    (include/y3d.h states the rule).  One HIP launch (`y3d_rows_depth_from_map`), capturable.  Inputs of another float dtype or strided
+    views are taken through a float32 contiguous copy; the inputs are left as they are."""
+    if not (torch.is_tensor(rows) and torch.is_tensor(depth_maps)) or rows.dim() != 3 or depth_maps.dim() != 3 or rows.shape[0] != depth_maps.shape[0]:
+        raise Y3DError(f"depth_from_map: expected rows (B, K, C) and depth maps (B, Hm, Wm), got {tuple(getattr(rows, 'shape', ()))} / "
+                       f"{tuple(getattr(depth_maps, 'shape', ()))}")
+    if rows.device.type != "cuda" or depth_maps.device != rows.device:
+        raise Y3DError("depth_from_map needs the rows and the depth maps on one HIP device (no host fallback)")
+    if not (rows.is_floating_point() and depth_maps.is_floating_point()):
+        raise Y3DError("depth_from_map: rows and depth maps must be floating point")
+    R, D = rows.detach().float().contiguous(), depth_maps.detach().float().contiguous()
+    out = torch.empty_like(R)
+    B, K, C = R.shape
+    lib().rows_depth_from_map(R.data_ptr(), B, K, C, D.data_ptr(), D.shape[1], D.shape[2], out.data_ptr(), ops.stream())
+    return out
+
+
 # ------------------------------------------------------------------------------------------------------------------------------
 # f3: image side of the input pipeline (data/datasets/kitti.py:132-206) on the device
 # ------------------------------------------------------------------------------------------------------------------------------

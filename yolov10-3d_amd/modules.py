@@ -494,6 +494,7 @@ class v10Detect3d(nn.Module):
     fused = True  # sibling-branch fusion of the training forward (set False for the per-branch reference form)
     fuse_bn_proj = True  # second layer of 64-multiple width: BatchNorm + SiLU applied inside the projections (set False for the separate passes)
     distill = False  # set by loss.DDDetectionLoss under `distillation: True`: the fused forward opens the sparse gradient path into z1
+    eval_one2many = False  # the eval forward also returns "one2many": the dense one-to-many head (the validator's use_o2m_depth reads it)
     PREDECESSORS = {"cls": (), "o2d": (), "s2d": (), "o3d": ("cls",), "s3d": ("cls",), "hd": ("cls",), "dep": ("cls", "s3d"),
                     "dep_un": ("cls", "s3d", "dep")}  # head.py:585-594
 
@@ -547,29 +548,33 @@ class v10Detect3d(nn.Module):
         """per-branch form (one head set): the reference's own loop, head.py:718-743.  The default head's training forward uses the fused
         form below; the constructor switches run here."""
         ys, embs = [], []
-        names = list(self.output_channels)
         for i in range(self.nl):
-            feats, outs, emb = [], {}, None
-            for j, module in enumerate(heads):
-                br = module[i]
-                pre = self.predecessors[names[j]] if self.use_predecessors else ()
-                if pre:  # head.py:727-737: level map + detached earlier outputs (depth / 65) along the channels
-                    e = _conv_over_cat(br[0], [x[i]] + [(outs[q] / self.dep_norm if q == "dep" else outs[q]).detach() for q in pre])
-                else:
-                    e = br[0](x[i])
-                if j == 6:
-                    emb = e
-                if self.use_predecessors:
-                    outs[names[j]] = _proj([br[2]], [br[1](e)])
-                else:
-                    feats.append(br[1](e))
-            if self.use_predecessors:
-                dt = ops.compute_dtype()
-                ys.append(torch.cat([o.to(dt) for o in outs.values()], 1))
-            else:
-                ys.append(_proj([module[i][2] for module in heads], feats))
+            y, emb = self._forward_feat_level(x[i], heads, i)
+            ys.append(y)
             embs.append(emb)
         return ys, embs
+
+    def _forward_feat_level(self, xi, heads, i):
+        """level i of `forward_feat` -> (map, embedding of the depth branch)"""
+        names = list(self.output_channels)
+        feats, outs, emb = [], {}, None
+        for j, module in enumerate(heads):
+            br = module[i]
+            pre = self.predecessors[names[j]] if self.use_predecessors else ()
+            if pre:  # head.py:727-737: level map + detached earlier outputs (depth / 65) along the channels
+                e = _conv_over_cat(br[0], [xi] + [(outs[q] / self.dep_norm if q == "dep" else outs[q]).detach() for q in pre])
+            else:
+                e = br[0](xi)
+            if j == 6:
+                emb = e
+            if self.use_predecessors:
+                outs[names[j]] = _proj([br[2]], [br[1](e)])
+            else:
+                feats.append(br[1](e))
+        if self.use_predecessors:
+            dt = ops.compute_dtype()
+            return torch.cat([o.to(dt) for o in outs.values()], 1), emb
+        return _proj([module[i][2] for module in heads], feats), emb
 
     def _stacks(self, i):
         """the HeadLevelPlan of level i: StackedConvs over [o2o branches 0..7, o2m branches 0..7] for layer 1 and, where the widths
@@ -693,7 +698,13 @@ class v10Detect3d(nn.Module):
         ops.lib().topk_cells(ops.code(scores.dtype), scores.data_ptr(), scores.stride(3), B, H * W, nc, self.max_det, idx.data_ptr(), ops.stream())
         return idx
 
-    def inference_forward_feat(self, x, heads):
+    def inference_forward_feat(self, x, heads, dense=None):
+        """the sparse eval maps of head set `heads`, one per level; with `dense` (a head set: `eval_one2many`) -> (those, the dense
+        maps of `dense`), every level's dense chain behind its sparse one on the same stream"""
+        if dense is None:
+            level = lambda i: self._inference_level(x, heads, i)
+        else:
+            level = lambda i: (self._inference_level(x, heads, i), self._dense_level(x[i], dense, i))
         if self.use_predecessors:
             raise RuntimeError("use_predecessors has no eval path: the reference's patch forward (head.py:694-716) feeds the branches bare "
                                "feature patches and fails on the channel count")
@@ -707,11 +718,12 @@ class v10Detect3d(nn.Module):
             for i in range(self.nl):
                 pool[i].wait_stream(cur)
                 with torch.cuda.stream(pool[i]):
-                    ys[i] = self._inference_level(x, heads, i)
+                    ys[i] = level(i)
             for i in range(self.nl):
                 cur.wait_stream(pool[i])
-            return ys
-        return [self._inference_level(x, heads, i) for i in range(self.nl)]
+        else:
+            ys = [level(i) for i in range(self.nl)]
+        return ys if dense is None else ([y for y, _ in ys], [m for _, m in ys])
 
     def _inference_level(self, x, heads, i):
         ps = self.patch_size
@@ -768,6 +780,40 @@ class v10Detect3d(nn.Module):
             feats.append(f)
         return _proj([heads[j][i][2] for j in range(1, 8)], feats)[:, :, 0, 0]
 
+    # ---- dense eval path of one head set: `_forward` in eval mode, head.py:800-812 ------------------------------
+    def _dense_level(self, xi, heads, i):
+        """the dense (B, no, H, W) map of head set `heads` on level i in eval mode: padding intact, running statistics, no patches.
+        Uniform stacked layout (not `generic`, not folded): the set's rows of the training-time stacks; anything else - the M-3D
+        "wide cls" layout, per-branch layouts, `dsconv` / `half_channels`, a folded model - the branch modules' own eval forward."""
+        c0 = heads[1][i][0]
+        folded = not hasattr(c0, "bn") if isinstance(c0, Conv) else False
+        plan = None if (self.generic or folded) else self._stacks(i)
+        if plan is not None and plan.uniform and heads is self.o2m_heads:
+            return self._dense_stacked(plan, heads, i, xi)
+        return self._forward_feat_level(xi, heads, i)[0]
+
+    def _dense_stacked(self, plan, heads, i, xi):
+        """the one-to-many set as one stacked conv + one grouped conv of 8 groups + one projection launch (channel rows 8*mid..16*mid
+        of the stacks of the uniform layout), both convs with their own padding k // 2"""
+        mid, c0, s1, s2 = plan.mids[0], heads[1][i][0], plan.s1, plan.layer2[0].stack
+        lo, hi = 8 * mid, 16 * mid
+        xi = ops.to_nhwc(xi, ops.compute_dtype())
+        w1, g1, b1, rm1, rv1 = s1.tensors()
+        z1 = ops.conv_bn_act_eval(xi, w1[lo:hi], g1[lo:hi], b1[lo:hi], rm1[lo:hi], rv1[lo:hi], self.kernel_size_1, 1, self.kernel_size_1 // 2, 1,
+                                  c0.has_act, c0.eps, s1.__dict__.setdefault("_eval_cache", {}), ver=s1.ver)
+        w2, g2, b2, rm2, rv2 = s2.tensors()
+        z2 = ops.conv_bn_act_eval(z1, w2[lo:hi], g2[lo:hi], b2[lo:hi], rm2[lo:hi], rv2[lo:hi], self.kernel_size_2, 1, self.kernel_size_2 // 2, 8,
+                                  c0.has_act, c0.eps, s2.__dict__.setdefault("_eval_cache", {}), ver=s2.ver)
+        finals = [heads[j][i][2] for j in range(8)]
+        return ops.proj_slices_eval(z2, [j * mid for j in range(8)], mid, [c.weight for c in finals], [c.bias for c in finals])
+
+    def _one2many_heads(self):
+        heads = getattr(self, "o2m_heads", None)
+        if heads is None or len(heads) != len(self.output_channels) or any(len(h) < self.nl for h in heads):
+            raise Y3DError("eval_one2many: this head has no one-to-many branches (o2m_heads is gone); the dense one-to-many forward "
+                           "of use_o2m_depth needs them")
+        return heads
+
     def decode(self, ys):
         """head.py:755-797: (B, no, A) fp32 with xyxy px boxes and centre-3d px (HIP kernel over the per-level NHWC maps)."""
         ys, A, args = _decode_args(ys, self.no, self.stride)
@@ -780,7 +826,11 @@ class v10Detect3d(nn.Module):
         """shape probe (see _host): the reference's constructor reads `forward(zeros)["one2many"]` shapes, nn/tasks.py:306-307"""
         maps = [_meta(xi.shape[0], self.no, *xi.shape[2:]) for xi in x]
         if not self.training:
-            return {"one2one": (torch.empty(x[0].shape[0], self.no, sum(m.shape[2] * m.shape[3] for m in maps), device="meta"), maps), "o2o_embs": None}
+            y = lambda: torch.empty(x[0].shape[0], self.no, sum(m.shape[2] * m.shape[3] for m in maps), device="meta")
+            out = {"one2one": (y(), maps), "o2o_embs": None}
+            if self.eval_one2many:
+                out["one2many"] = (y(), list(maps))
+            return out
         embs = [_meta(xi.shape[0], self.dep[i][0].conv.out_channels if isinstance(self.dep[i][0], Conv) else self.dep[i][0][-1].conv.out_channels,
                       *xi.shape[2:]) for i, xi in enumerate(x)]
         return {"one2many": maps, "one2one": list(maps), "o2m_embs": embs, "o2o_embs": list(embs), "depth_maps": torch.empty(1)}
@@ -790,8 +840,11 @@ class v10Detect3d(nn.Module):
         if _host(x):
             return self._probe(x)
         if not self.training:
-            maps = self.inference_forward_feat([xi.detach() for xi in x], self.o2o_heads)
-            return {"one2one": (self.decode(maps), maps), "o2o_embs": None}
+            if not self.eval_one2many:
+                maps = self.inference_forward_feat([xi.detach() for xi in x], self.o2o_heads)
+                return {"one2one": (self.decode(maps), maps), "o2o_embs": None}
+            maps, maps_m = self.inference_forward_feat([xi.detach() for xi in x], self.o2o_heads, self._one2many_heads())
+            return {"one2one": (self.decode(maps), maps), "o2o_embs": None, "one2many": (self.decode(maps_m), maps_m)}
         fused = self.fused and not self.generic
         if fused:
             one2one, one2many, o2o_embs, o2m_embs = self.forward_train_fused(x)

@@ -21,7 +21,8 @@ coordinates and their projections out.
 
 The host computes the reference's unaugmented sample (data/datasets/kitti.py:130-135, :192, :404): the crop matrix of the whole image,
 `ratio = resolution / img_size`, the six calibration constants.  The device does `y3d_kitti_image_aug` (Pillow's affine resize), the
-eval forward, `v10_3Dpostprocess`, and `y3d_predict3d_rows` (KITTI decode, confidence / class filter, ordered compaction, corners and
+eval forward, `v10_3Dpostprocess` (with `use_o2m_depth=True` also the dense one-to-many head, its post-process and the depth vote
+`y3d_kde_depth_fusion`), and `y3d_predict3d_rows` (KITTI decode, confidence / class filter, ordered compaction, corners and
 their projection; csrc/predict3d.hip)."""
 from __future__ import annotations
 
@@ -205,11 +206,63 @@ def predict3d_rows(preds, calib6, P2, ratio, inv_trans, conf, classes=None, cls_
     return rows, c3, ci, counts
 
 
-def raw_rows3d(model, img, max_det):
-    """eval forward + `v10_3Dpostprocess` + the cat of models/yolov10_3D/val.py:46-47 -> (B, max_det, 37) float32"""
-    y = model(img)["one2one"][0]
-    reg, scores, labels = _loss.v10_3Dpostprocess(y.permute(0, 2, 1), max_det, model.yaml["nc"])
+O2M_FACTOR = 5      # the one-to-many post-process keeps max_det * 5 rows (val.py:52)
+O2M_ROWS_MAX = 3902  # the most one-to-many rows `y3d_kde_depth_fusion` holds in LDS
+
+
+def rows3d(y, max_det, nc):
+    """`v10_3Dpostprocess` + the cat of models/yolov10_3D/val.py:46-47: y (B, nc + 35, A) decoded head output -> (B, max_det, 37) float32"""
+    reg, scores, labels = _loss.v10_3Dpostprocess(y.permute(0, 2, 1), max_det, nc)
     return torch.cat((reg, scores.unsqueeze(-1), labels.unsqueeze(-1)), -1).float()
+
+
+def check_o2m(max_det, A):
+    """the refusals of the one-to-many depth vote, before anything is launched: the one-to-many post-process needs max_det * 5 anchors,
+    the fusion kernel keeps max_det * 5 rows in LDS"""
+    km = int(max_det) * O2M_FACTOR
+    if km > O2M_ROWS_MAX:
+        raise Y3DError(f"use_o2m_depth: max_det = {max_det} asks for {km} one-to-many rows, the depth fusion holds at most {O2M_ROWS_MAX} "
+                       f"(max_det <= {O2M_ROWS_MAX // O2M_FACTOR})")
+    if km > int(A):
+        raise Y3DError(f"use_o2m_depth: max_det = {max_det} asks for {km} one-to-many rows, the head has {A} anchors "
+                       f"(max_det <= {int(A) // O2M_FACTOR} at this image size)")
+
+
+def o2m_rows3d(yO, yM, max_det, nc):
+    """the validator's `postprocess` with use_o2m_depth (val.py:44-55) on the decoded outputs of the two head sets, (B, nc + 35, A) each:
+    `v10_3Dpostprocess(yO, max_det)`, `v10_3Dpostprocess(yM, max_det * 5)`, the two cats, `kitti.aggregate_o2m_preds` at its defaults
+    -> (fused rows (B, max_det, 37), rowsO, rowsM (B, max_det * 5, 37)).  Three launches, capturable."""
+    if yO.shape != yM.shape:
+        raise Y3DError(f"use_o2m_depth: one-to-one output {tuple(yO.shape)} but one-to-many output {tuple(yM.shape)}")
+    check_o2m(max_det, yO.shape[-1])
+    rowsO, rowsM = rows3d(yO, max_det, nc), rows3d(yM, max_det * O2M_FACTOR, nc)
+    return kitti.aggregate_o2m_preds(rowsO, rowsM), rowsO, rowsM
+
+
+def anchors_of(model, img):
+    """the number of anchors of the 3D head for the (B, 3, H, W) image: one per cell of every level"""
+    H, W = int(img.shape[-2]), int(img.shape[-1])
+    return sum((-(-H // int(s))) * (-(-W // int(s))) for s in model.model[-1].stride.tolist())
+
+
+def raw_rows3d(model, img, max_det, use_o2m_depth=False, depth_maps=None):
+    """eval forward + `v10_3Dpostprocess` + the cat of models/yolov10_3D/val.py:46-47 -> (B, max_det, 37) float32.
+    use_o2m_depth: the head also runs its dense one-to-many set (`v10Detect3d.eval_one2many`, set for this call) and the depths become
+    the vote of `o2m_rows3d`; refused before any launch when max_det * 5 exceeds the anchors or the fusion kernel's 3902 rows.
+    depth_maps (B, Hm, Wm): the reference's `elif use_dino_depth` - the depths are read from the maps (`kitti.depth_from_map`); with
+    both, one-to-many wins and the maps are not read, as in the reference."""
+    nc = model.yaml["nc"]
+    if not use_o2m_depth:
+        rows = rows3d(model(img)["one2one"][0], max_det, nc)
+        return rows if depth_maps is None else kitti.depth_from_map(rows, depth_maps)
+    check_o2m(max_det, anchors_of(model, img))
+    head = model.model[-1]
+    was, head.eval_one2many = head.eval_one2many, True
+    try:
+        out = model(img)
+    finally:
+        head.eval_one2many = was
+    return o2m_rows3d(out["one2one"][0], out["one2many"][0], max_det, nc)[0]
 
 
 def kitti_results(rows, counts, im_files):
@@ -231,7 +284,7 @@ def kitti_results(rows, counts, im_files):
 
 class Predictor3d:
     def __init__(self, model, conf=0.25, classes=None, max_det=50, resolution=kitti.RESOLUTION, cls_mean_size=kitti.CLS_MEAN_SIZE,
-                 use_camera_dis=False):
+                 use_camera_dis=False, use_o2m_depth=False):
         from .modules import v10Detect3d
         if not isinstance(model.model[-1], v10Detect3d):
             raise Y3DError("predict3d: a 3D model is expected (predict.Predictor takes the 2D models)")
@@ -243,6 +296,7 @@ class Predictor3d:
         self.conf, self.max_det = float(conf), int(max_det)
         self.classes = None if classes is None else [int(c) for c in (classes if isinstance(classes, (list, tuple)) else [classes])]
         self.cls_mean_size, self.use_camera_dis = cls_mean_size, bool(use_camera_dis)
+        self.use_o2m_depth = bool(use_o2m_depth)  # the depths become the vote of the one-to-many proposals (raw_rows3d)
         self._cls_dev = None
 
     def plan(self, shapes, P2s):
@@ -303,7 +357,7 @@ class Predictor3d:
         if self.classes is not None and (self._cls_dev is None or self._cls_dev.device != dev):
             self._cls_dev = torch.tensor(self.classes, dtype=torch.int32).to(dev)
         with torch.no_grad():
-            raw = raw_rows3d(self.model, img.permute(0, 3, 1, 2), self.max_det)
+            raw = raw_rows3d(self.model, img.permute(0, 3, 1, 2), self.max_det, use_o2m_depth=self.use_o2m_depth)
         up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
         rows, c3, ci, counts = predict3d_rows(raw, up(p["calib6"]), up(p["P2"]), up(p["ratio"]), up(p["trans_inv"]), self.conf,
                                               self._cls_dev if self.classes is not None else None, self.cls_mean_size, self.use_camera_dis)

@@ -20,6 +20,7 @@ import numpy as np
 import torch
 
 from . import json3d, kitti, kitti_eval, metrics, plot, yolo2d
+from . import loss as _loss
 from ._lib import Y3DError
 from .graph import GraphedForward
 from .predict import _mean_sizes, predict3d_rows, raw_rows, raw_rows3d
@@ -46,12 +47,15 @@ class _Validator:
         self.seen = 0
         self.speed = {"preprocess": 0.0, "inference": 0.0, "loss": 0.0, "postprocess": 0.0}
 
+    def _graph_key(self, img):
+        return tuple(img.shape)
+
     def _raw(self, img):
         """img (B, H, W, 3) uint8 -> the post-processed rows of the eval forward, eagerly or replayed from one hipGraph per shape"""
         if not self.graph:
             with torch.no_grad():
                 return self._rows(img)
-        key = tuple(img.shape)
+        key = self._graph_key(img)
         if key not in self._graphs:
             self._graphs[key] = GraphedForward(self._rows, img)
         return self._graphs[key](img)
@@ -106,12 +110,21 @@ class Validator3d(_Validator):
     nine images each of the label picture (`plot.label_pictures`), the prediction picture (predictions at threshold 0.1, decoded with
     undo_augment=False, under the labels' wireframes, as `plot_preds` draws them) and the BEV map with the decoded labels as `gt`, all
     made on the device after the batch's metrics and read back once after the loop into `self.pictures`, a list of {"labels", "preds",
-    "bev"} uint8 arrays.  With pictures=0 (the default) nothing more is launched than before."""
+    "bev"} uint8 arrays.  With pictures=0 (the default) nothing more is launched than before.
+
+    The depth refinements of the reference's `postprocess` (val.py:33-59), both off by default (the defaults fall back
+    to `args.use_o2m_depth` / `args.use_dino_depth`) and off meaning the launches above, call for call:
+    `use_o2m_depth`: the head's `eval_one2many` is set for the run, and the depth of every row becomes the vote of the one-to-many
+    proposals (`predict.o2m_rows3d`: both post-processes and `kitti.aggregate_o2m_preds`; with graph=True all of it is replayed).
+    `use_dino_depth`: `depth_fn`, or the callable registered with `loss.set_teacher`, is called on the batch image (a (B, 3, H, W) uint8 view) under
+    no_grad, `(depth_maps, embeddings) = fn(img)`, outside the graph and after the replay, and the depths are read from its maps
+    (`kitti.depth_from_map`, launched eagerly).  With both switches one-to-many wins, as in the reference.  Decode, `BoxStats`,
+    confusion matrix, pictures and `results` take the refined rows."""
 
     PICTURE_CONF, PICTURE_IMGS = 0.1, 9  # plot_preds' threshold, KITTIVisualizer.max_imgs
 
     def __init__(self, model, root_or_split, args=None, dataset="kitti", batch=16, conf=0.001, max_det=50, single_cls=False, plots=True,
-                 resolution=kitti.RESOLUTION, label_dir=None, graph=False, pictures=0):
+                 resolution=kitti.RESOLUTION, label_dir=None, graph=False, pictures=0, use_o2m_depth=None, use_dino_depth=None, depth_fn=None):
         if int(pictures) != pictures or int(pictures) < 0:
             raise Y3DError(f"Validator3d: pictures = {pictures!r} (the number of leading batches to draw, 0 for none)")
         super().__init__(model, True, conf, max_det, single_cls, plots, graph)
@@ -130,9 +143,32 @@ class Validator3d(_Validator):
         self.mean_sizes = kitti.CLS_MEAN_SIZE if dataset == "kitti" else json3d.CLS_MEAN_SIZE[dataset]
         self.results = {}
         self.n_pictures, self.pictures = int(pictures), []
+        self.use_o2m_depth = bool(getattr(self.args, "use_o2m_depth", False) if use_o2m_depth is None else use_o2m_depth)
+        self.use_dino_depth = bool(getattr(self.args, "use_dino_depth", False) if use_dino_depth is None else use_dino_depth)
+        if depth_fn is not None and not callable(depth_fn):
+            raise Y3DError("Validator3d: depth_fn must be a callable, (depth_maps, embeddings) = depth_fn(img)")
+        self.depth_fn = depth_fn
 
     def _rows(self, img):
-        return raw_rows3d(self.model, img.permute(0, 3, 1, 2), self.max_det)
+        return raw_rows3d(self.model, img.permute(0, 3, 1, 2), self.max_det, use_o2m_depth=self.use_o2m_depth)
+
+    def _graph_key(self, img):
+        # one hipGraph per shape and state of the switch (off: the shape alone, as before)
+        return (tuple(img.shape), "o2m") if self.use_o2m_depth else tuple(img.shape)
+
+    def _depth_callable(self):
+        """the depth network of `use_dino_depth`: `depth_fn`, else the callable registered with `loss.set_teacher`"""
+        fn = self.depth_fn if self.depth_fn is not None else _loss.get_teacher()
+        if fn is None:
+            raise Y3DError("use_dino_depth needs a depth map: pass depth_fn to Validator3d or register a callable with "
+                           "loss.set_teacher(fn), (depth_maps, embeddings) = fn(img); the DINOv2 teacher itself is not part of this package")
+        return fn
+
+    def _dino_depth(self, raw, img, fn):
+        """the reference's `elif use_dino_depth` (val.py:57-58, :61-76): eagerly, after the forward (or its replay)"""
+        with torch.no_grad():
+            depth_maps = fn(img.permute(0, 3, 1, 2))[0]
+        return kitti.depth_from_map(raw, depth_maps)
 
     def _projection(self):
         """-> position -> the original image's P2 (3, 4), next to `_dataset`'s six constants"""
@@ -182,6 +218,15 @@ class Validator3d(_Validator):
         return json3d.build_batch(self.source, idx, self.args, self.device, dataset=self.dataset, mode="val", compact=True)
 
     def _run(self):
+        dino = self._depth_callable() if self.use_dino_depth and not self.use_o2m_depth else None
+        head = self.model.model[-1]
+        was, head.eval_one2many = head.eval_one2many, self.use_o2m_depth
+        try:
+            return self._run_batches(dino)
+        finally:
+            head.eval_one2many = was
+
+    def _run_batches(self, dino):
         n, calib, data = self._dataset()
         self._start()
         ms = _mean_sizes(self.mean_sizes, self.device)
@@ -193,6 +238,8 @@ class Validator3d(_Validator):
             b = self._batch(idx)
             t1 = self._mark()
             raw = self._raw(b["img"])
+            if dino is not None:
+                raw = self._dino_depth(raw, b["img"], dino)
             t2 = self._mark()
             c6 = metrics._upload(np.array([calib(p) for p in idx], np.float64), self.device)
             inv = metrics._upload(np.stack([np.asarray(i["trans_inv"], np.float64).reshape(2, 3) for i in b["info"]]), self.device)
