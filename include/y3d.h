@@ -723,8 +723,8 @@ int y3d_ap_per_class(const int* tp, const double* conf, const int* cls, int64_t 
                      void* stream);
 
 /* ------------------------------------------------------------------------------------------------
- * Optimizer step as multi-tensor launches (optim.hip): clip_grad_norm_ + SGD(nesterov, weight decay) — engine/trainer.py:567-575,
- * 734-790.  All table arguments are DEVICE arrays: tensor t has sizes[t] fp32 elements at param_ptrs[t] / grad_ptrs[t] / buf_ptrs[t];
+ * Optimizer step as multi-tensor launches (optim.hip): clip_grad_norm_ + SGD(nesterov, weight decay), AdamW, and the rest of the
+ * reference's list (Adam, Adamax, NAdam, RAdam, RMSprop) — engine/trainer.py:567-575, 734-790.  All table arguments are DEVICE arrays: tensor t has sizes[t] fp32 elements at param_ptrs[t] / grad_ptrs[t] / buf_ptrs[t];
  * workgroup c handles elements [chunk_off[c]*chunk, +chunk) of tensor chunk_tensor[c].
  * ---------------------------------------------------------------------------------------------- */
 int y3d_mt_sqnorm(const int64_t* grad_ptrs, const int64_t* sizes, const int* chunk_tensor, const int* chunk_off, int nchunks, int chunk,
@@ -745,6 +745,43 @@ int y3d_mt_sgd(const int64_t* param_ptrs, const int64_t* grad_ptrs, const int64_
 int y3d_mt_adamw(const int64_t* param_ptrs, const int64_t* grad_ptrs, const int64_t* m_ptrs, const int64_t* v_ptrs, const int64_t* sizes,
                  const float* lr, const float* wd, const int* chunk_tensor, const int* chunk_off, int nchunks, int chunk, float beta1, float beta2,
                  float eps, float bias_corr1, float bias_corr2_sqrt, const float* norm_clip, void* stream);
+/* The reference's remaining optimizers (engine/trainer.py:776-781: Adam, Adamax, NAdam, RAdam, RMSProp) and a schedulable momentum.
+ *
+ * y3d_mt_step_scalars: one workgroup, after y3d_mt_clip_coef.  Reads the finite flag norm_clip[2] and the applied-step count
+ * t = norm_clip[3] and writes, computed in double and rounded once to float, what the update kernels need that depends only on t
+ * (betas as fp32 values, as the update kernels use them):
+ *   [0] 1-beta1^t   [1] 1-beta2^t   [2] sqrt([0])   [3] sqrt([1])
+ *   [4] mu_t = beta1 (1 - 0.5 0.96^(t momentum_decay))   [5] mu_{t+1}   [6] mu_product (fp32 STATE: *= mu_t, 1 before the first applied
+ *   step)   [7] mu_product mu_{t+1}   [12] (1-mu_t)/(1-mu_product)   [13] mu_{t+1}/(1-[7])                      (torch.optim.NAdam)
+ *   [8] rho_t = rho_inf - 2 t beta2^t/(1-beta2^t)   [9] rho_t > 5 (decided in double) ? 1 : 0   [10] the rectification factor
+ *   sqrt((rho_t-4)(rho_t-2)rho_inf / ((rho_inf-4)(rho_inf-2)rho_t)) when [9], else 0                             (torch.optim.RAdam)
+ *   [11] t   [14], [15] unused
+ * A skipped step (norm_clip[2] == 0) leaves all Y3D_STEP_SCALARS floats as they are. */
+#define Y3D_STEP_SCALARS 16
+int y3d_mt_step_scalars(const float* norm_clip, float beta1, float beta2, double momentum_decay, float* step_scalars, void* stream);
+/* One step of torch.optim.{Adam, Adamax, NAdam, RAdam, RMSprop} in torch's single-tensor arithmetic (foreach=False, amsgrad / centered /
+ * maximize off, coupled weight decay g += wd*p), tables and skip rule as y3d_mt_sgd; norm_clip may be NULL (coefficient 1, no skip).
+ * g = grad*clip (+ wd*p);  s0 / s1 are the two state buffers:
+ *   ADAM    m += (1-beta1)(g-m); v = beta2 v + (1-beta2) g^2; p -= lr/[0] * m / (sqrt(v)/[3] + eps)
+ *   ADAMAX  m as above; u = max(beta2 u, |g| + eps); p -= lr/[0] * m / u
+ *   NADAM   m, v as ADAM; d = sqrt(v/[1]) + eps; p -= lr [12] * g/d; p -= lr [13] * m/d
+ *   RADAM   m, v as ADAM; [9] ? p -= m/[0] * lr * ([3] / (sqrt(v) + eps)) * [10] : p -= m/[0] * lr
+ *   RMSPROP s0 = beta2 s0 + (1-beta2) g^2 (beta2 = alpha); q = g / (sqrt(s0) + eps); momentum[t] > 0 ? (s1 = momentum[t] s1 + q;
+ *           p -= lr s1) : p -= lr q.   beta1 and step_scalars are not read; `momentum` is a per-tensor device table like lr / wd
+ * ([i]: step_scalars[i]; `momentum` is read by RMSPROP only and may be NULL otherwise) */
+#define Y3D_OPT_ADAM 0
+#define Y3D_OPT_ADAMAX 1
+#define Y3D_OPT_NADAM 2
+#define Y3D_OPT_RADAM 3
+#define Y3D_OPT_RMSPROP 4
+int y3d_mt_update(int kind, const int64_t* param_ptrs, const int64_t* grad_ptrs, const int64_t* s0_ptrs, const int64_t* s1_ptrs,
+                  const int64_t* sizes, const float* lr, const float* wd, const float* momentum, const int* chunk_tensor, const int* chunk_off,
+                  int nchunks, int chunk, float beta1, float beta2, float eps, const float* step_scalars, const float* norm_clip, void* stream);
+/* y3d_mt_sgd with the momentum read from a per-tensor device table next to lr / wd, so that a captured step follows a momentum
+ * schedule (the reference's warm-up, engine/trainer.py:392-393) through in-place writes of that table */
+int y3d_mt_sgd_tab(const int64_t* param_ptrs, const int64_t* grad_ptrs, const int64_t* buf_ptrs, const int64_t* sizes, const float* lr,
+                   const float* wd, const float* momentum, const int* chunk_tensor, const int* chunk_off, int nchunks, int chunk, int nesterov,
+                   int first_step, const float* norm_clip, void* stream);
 /* ModelEMA.update (utils/torch_utils.py:431-443, called from optimizer_step engine/trainer.py:574-575): e = e*decay + (1-decay)*m over
  * every floating-point state_dict tensor, reps[t] times for tensor t (the reference walks state_dict KEYS, and the aliased one-to-one
  * head branches appear under two keys each).  guard: NULL, or y3d_mt_clip_coef's array — the update is then a no-op when

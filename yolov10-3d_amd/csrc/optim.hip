@@ -140,6 +140,201 @@ __global__ __launch_bounds__(256) void mt_adamw_kernel(const long* __restrict__ 
   }
 }
 
+// ---- the reference's remaining optimizers (engine/trainer.py:776-781: Adam, Adamax, NAdam, RAdam, RMSProp) --------------------------------
+// Everything that depends only on the number of APPLIED steps is computed once per step by mt_step_scalars_kernel (double, rounded once
+// to float) into a Y3D_STEP_SCALARS-float array; the update kernels read it.  Index names: include/y3d.h.
+enum { S_BC1 = 0, S_BC2, S_BC1_SQRT, S_BC2_SQRT, S_MU, S_MU_NEXT, S_MU_PROD, S_MU_PROD_NEXT, S_RHO, S_RECT_ON, S_RECT, S_T, S_NADAM_G, S_NADAM_M };
+enum { K_ADAM = 0, K_ADAMAX = 1, K_NADAM = 2, K_RADAM = 3, K_RMSPROP = 4 };
+
+// clip: mt_clip_kernel's array.  A skipped step (clip[2] == 0) leaves every scalar, mu_product included, as it is.
+__global__ __launch_bounds__(64) void mt_step_scalars_kernel(const float* __restrict__ clip, float beta1, float beta2, double momentum_decay,
+                                                             float* __restrict__ scal) {
+  if (threadIdx.x != 0 || clip[2] == 0.f) return;
+  const double t = (double)clip[3], b1 = (double)beta1, b2 = (double)beta2;
+  const double p2 = pow(b2, t);
+  const double bc1 = 1.0 - pow(b1, t), bc2 = 1.0 - p2;
+  scal[S_BC1] = (float)bc1;
+  scal[S_BC2] = (float)bc2;
+  scal[S_BC1_SQRT] = (float)sqrt(bc1);
+  scal[S_BC2_SQRT] = (float)sqrt(bc2);
+  // torch.optim.NAdam: mu_t, mu_{t+1}, and mu_product *= mu_t (fp32 state; 1 before the first applied step)
+  const double mu = b1 * (1.0 - 0.5 * pow(0.96, t * momentum_decay));
+  const double mu_next = b1 * (1.0 - 0.5 * pow(0.96, (t + 1.0) * momentum_decay));
+  const float mp = (float)((double)(t == 1.0 ? 1.f : scal[S_MU_PROD]) * mu);
+  const double mp_next = (double)mp * mu_next;
+  scal[S_MU] = (float)mu;
+  scal[S_MU_NEXT] = (float)mu_next;
+  scal[S_MU_PROD] = mp;
+  scal[S_MU_PROD_NEXT] = (float)mp_next;
+  scal[S_NADAM_G] = (float)((1.0 - mu) / (1.0 - (double)mp));
+  scal[S_NADAM_M] = (float)(mu_next / (1.0 - mp_next));
+  // torch.optim.RAdam: length of the approximated SMA, the rho_t > 5 decision (taken in double) and the rectification factor
+  const double rho_inf = 2.0 / (1.0 - b2) - 1.0;
+  const double rho = rho_inf - 2.0 * t * p2 / bc2;
+  const bool on = rho > 5.0;
+  scal[S_RHO] = (float)rho;
+  scal[S_RECT_ON] = on ? 1.f : 0.f;
+  scal[S_RECT] = on ? (float)sqrt((rho - 4.0) * (rho - 2.0) * rho_inf / ((rho_inf - 4.0) * (rho_inf - 2.0) * rho)) : 0.f;
+  scal[S_T] = (float)t;
+}
+
+// per-workgroup constants of one tensor's update; k0..k2 and arm by kind (mt_update_kernel)
+struct UpdCoef {
+  float c, l, w, b2, w1, w2, eps, k0, k1, k2;
+  int arm;
+};
+
+// one element, torch's single-tensor arithmetic (foreach=False, not capturable).  a, b: the two state buffers
+//   Adam / NAdam / RAdam: exp_avg, exp_avg_sq;  Adamax: exp_avg, exp_inf;  RMSprop: square_avg, momentum_buffer
+template <int KIND>
+__device__ __forceinline__ void upd(float& p, const float g, float& a, float& b, const UpdCoef& k) {
+  const float pv = p;
+  float gv = g * k.c;
+  if (k.w != 0.f) gv += k.w * pv;  // coupled L2 decay: grad.add(param, alpha=weight_decay)
+  if (KIND == K_RMSPROP) {
+    const float sq = a * k.b2 + k.w2 * gv * gv;  // square_avg.mul_(alpha).addcmul_(grad, grad, value=1 - alpha)
+    a = sq;
+    const float q = gv / (sqrtf(sq) + k.eps);
+    if (k.arm) {  // momentum > 0
+      const float bv = b * k.k0 + q;
+      b = bv;
+      p = pv - k.l * bv;
+    } else {
+      p = pv - k.l * q;
+    }
+    return;
+  }
+  const float mv = a + k.w1 * (gv - a);  // exp_avg.lerp_(grad, 1 - beta1)
+  a = mv;
+  if (KIND == K_ADAMAX) {
+    const float d = b * k.b2, e = fabsf(gv) + k.eps;
+    const float un = d > e ? d : e;  // exp_inf = max(beta2 * exp_inf, |grad| + eps)
+    b = un;
+    p = pv - k.k0 * (mv / un);  // k0 = lr / (1 - beta1^t)
+    return;
+  }
+  const float vv = b * k.b2 + k.w2 * gv * gv;
+  b = vv;
+  if (KIND == K_ADAM) {  // k0 = lr / (1 - beta1^t), k1 = sqrt(1 - beta2^t)
+    p = pv - k.k0 * (mv / (sqrtf(vv) / k.k1 + k.eps));
+  } else if (KIND == K_NADAM) {  // k0 = lr (1 - mu_t) / (1 - mu_product), k1 = lr mu_{t+1} / (1 - mu_product mu_{t+1}), k2 = 1 - beta2^t
+    const float denom = sqrtf(vv / k.k2) + k.eps;
+    const float p1 = pv - k.k0 * (gv / denom);
+    p = p1 - k.k1 * (mv / denom);
+  } else {  // K_RADAM: k0 = 1 - beta1^t, k1 = sqrt(1 - beta2^t), k2 = rectification factor, arm = rho_t > 5
+    const float bce = mv / k.k0;
+    if (k.arm) p = pv - ((bce * k.l) * (k.k1 / (sqrtf(vv) + k.eps))) * k.k2;
+    else p = pv - bce * k.l;
+  }
+}
+
+// One parameter chunk per workgroup, chunk tables and skip rule of mt_sgd / mt_adamw.  16-byte accesses when the four pointers allow.
+// mom: per-tensor momentum table (RMSprop only); scal: mt_step_scalars_kernel's array (not read by RMSprop).
+template <int KIND>
+__global__ __launch_bounds__(256) void mt_update_kernel(const long* __restrict__ pptr, const long* __restrict__ gptr, const long* __restrict__ aptr,
+                                                        const long* __restrict__ bptr, const long* __restrict__ sizes, const float* __restrict__ lr,
+                                                        const float* __restrict__ wd, const float* __restrict__ mom, const int* __restrict__ ctensor,
+                                                        const int* __restrict__ coff, int chunk, float beta1, float beta2, float eps,
+                                                        const float* __restrict__ scal, const float* __restrict__ clip) {
+  const int t = ctensor[blockIdx.x];
+  const long off = (long)coff[blockIdx.x] * chunk;
+  float* p = (float*)pptr[t] + off;
+  const float* g = (const float*)gptr[t] + off;
+  float* a = (float*)aptr[t] + off;
+  float* b = (float*)bptr[t] + off;
+  long n = sizes[t] - off;
+  if (n > chunk) n = chunk;
+  if (clip && clip[2] == 0.f) return;  // skipped step (non-finite gradient norm): parameters and state stay
+  UpdCoef k;
+  k.c = clip ? clip[1] : 1.f;
+  k.l = lr[t];
+  k.w = wd[t];
+  k.b2 = beta2;
+  k.w1 = 1.f - beta1;
+  k.w2 = 1.f - beta2;
+  k.eps = eps;
+  k.k0 = k.k1 = k.k2 = 0.f;
+  k.arm = 0;
+  if (KIND == K_ADAM) {
+    k.k0 = k.l / scal[S_BC1];
+    k.k1 = scal[S_BC2_SQRT];
+  } else if (KIND == K_ADAMAX) {
+    k.k0 = k.l / scal[S_BC1];
+  } else if (KIND == K_NADAM) {
+    k.k0 = k.l * scal[S_NADAM_G];
+    k.k1 = k.l * scal[S_NADAM_M];
+    k.k2 = scal[S_BC2];
+  } else if (KIND == K_RADAM) {
+    k.k0 = scal[S_BC1];
+    k.k1 = scal[S_BC2_SQRT];
+    k.k2 = scal[S_RECT];
+    k.arm = scal[S_RECT_ON] != 0.f;
+  } else {
+    k.k0 = mom[t];
+    k.arm = k.k0 > 0.f;
+  }
+  if (((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)a) | ((uintptr_t)b)) & 15) == 0) {
+    const long n4 = n >> 2;
+    for (long i = threadIdx.x; i < n4; i += 256) {
+      float4 P = ((float4*)p)[i], A = ((float4*)a)[i], B = ((float4*)b)[i];
+      const float4 G = ((const float4*)g)[i];
+      upd<KIND>(P.x, G.x, A.x, B.x, k);
+      upd<KIND>(P.y, G.y, A.y, B.y, k);
+      upd<KIND>(P.z, G.z, A.z, B.z, k);
+      upd<KIND>(P.w, G.w, A.w, B.w, k);
+      ((float4*)a)[i] = A;
+      ((float4*)b)[i] = B;
+      ((float4*)p)[i] = P;
+    }
+    for (long i = (n4 << 2) + threadIdx.x; i < n; i += 256) upd<KIND>(p[i], g[i], a[i], b[i], k);
+  } else {
+    for (long i = threadIdx.x; i < n; i += 256) upd<KIND>(p[i], g[i], a[i], b[i], k);
+  }
+}
+
+// mt_sgd_kernel with the momentum read from a per-tensor device table next to lr / wd: a captured step follows a momentum schedule
+// (warm-up, engine/trainer.py:392-393) through in-place writes of the table
+__device__ __forceinline__ void upd_sgd(float& p, const float g, float& b, float c, float l, float w, float momentum, int nesterov, int first) {
+  const float pv = p;
+  float gv = g * c;
+  if (w != 0.f) gv += w * pv;
+  const float bv = first ? gv : momentum * b + gv;
+  b = bv;
+  const float step = nesterov ? gv + momentum * bv : bv;
+  p = pv - l * step;
+}
+
+__global__ __launch_bounds__(256) void mt_sgd_tab_kernel(const long* __restrict__ pptr, const long* __restrict__ gptr, const long* __restrict__ bptr,
+                                                         const long* __restrict__ sizes, const float* __restrict__ lr, const float* __restrict__ wd,
+                                                         const float* __restrict__ mom, const int* __restrict__ ctensor, const int* __restrict__ coff,
+                                                         int chunk, int nesterov, int first, const float* __restrict__ clip) {
+  const int t = ctensor[blockIdx.x];
+  const long off = (long)coff[blockIdx.x] * chunk;
+  float* p = (float*)pptr[t] + off;
+  const float* g = (const float*)gptr[t] + off;
+  float* b = (float*)bptr[t] + off;
+  long n = sizes[t] - off;
+  if (n > chunk) n = chunk;
+  if (clip && clip[2] == 0.f) return;
+  const float c = clip ? clip[1] : 1.f, l = lr[t], w = wd[t], m = mom[t];
+  if (((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)b)) & 15) == 0) {
+    const long n4 = n >> 2;
+    for (long i = threadIdx.x; i < n4; i += 256) {
+      float4 P = ((float4*)p)[i], B = ((float4*)b)[i];
+      const float4 G = ((const float4*)g)[i];
+      upd_sgd(P.x, G.x, B.x, c, l, w, m, nesterov, first);
+      upd_sgd(P.y, G.y, B.y, c, l, w, m, nesterov, first);
+      upd_sgd(P.z, G.z, B.z, c, l, w, m, nesterov, first);
+      upd_sgd(P.w, G.w, B.w, c, l, w, m, nesterov, first);
+      ((float4*)b)[i] = B;
+      ((float4*)p)[i] = P;
+    }
+    for (long i = (n4 << 2) + threadIdx.x; i < n; i += 256) upd_sgd(p[i], g[i], b[i], c, l, w, m, nesterov, first);
+  } else {
+    for (long i = threadIdx.x; i < n; i += 256) upd_sgd(p[i], g[i], b[i], c, l, w, m, nesterov, first);
+  }
+}
+
 // ModelEMA.update (utils/torch_utils.py:431-443): e = e * d + (1 - d) * m, applied reps[t] times to tensor t (an EMA tensor that the
 // reference's state_dict lists under several keys -- the aliased one-to-one head branches -- is updated once per key)
 __global__ __launch_bounds__(256) void mt_ema_kernel(const long* __restrict__ eptr, const long* __restrict__ mptr, const long* __restrict__ sizes,
@@ -208,6 +403,48 @@ int y3d_mt_adamw(const int64_t* param_ptrs, const int64_t* grad_ptrs, const int6
   hipLaunchKernelGGL(mt_adamw_kernel, dim3(nchunks), dim3(256), 0, (hipStream_t)stream, (const long*)param_ptrs, (const long*)grad_ptrs,
                      (const long*)m_ptrs, (const long*)v_ptrs, (const long*)sizes, lr, wd, chunk_tensor, chunk_off, chunk, beta1, beta2, eps,
                      bias_corr1, bias_corr2_sqrt, norm_clip);
+  Y3D_LAUNCH_CHECK();
+  return Y3D_OK;
+}
+
+int y3d_mt_step_scalars(const float* norm_clip, float beta1, float beta2, double momentum_decay, float* step_scalars, void* stream) {
+  Y3D_CHECK(norm_clip && step_scalars, "mt_step_scalars: null array");
+  Y3D_CHECK(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f, "mt_step_scalars: betas must lie in [0, 1)");
+  hipLaunchKernelGGL(mt_step_scalars_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, norm_clip, beta1, beta2, momentum_decay, step_scalars);
+  Y3D_LAUNCH_CHECK();
+  return Y3D_OK;
+}
+
+int y3d_mt_update(int kind, const int64_t* param_ptrs, const int64_t* grad_ptrs, const int64_t* s0_ptrs, const int64_t* s1_ptrs,
+                  const int64_t* sizes, const float* lr, const float* wd, const float* momentum, const int* chunk_tensor, const int* chunk_off,
+                  int nchunks, int chunk, float beta1, float beta2, float eps, const float* step_scalars, const float* norm_clip, void* stream) {
+  Y3D_CHECK(nchunks >= 1 && chunk >= 256, "mt_update: empty chunk table");
+  Y3D_CHECK(kind >= K_ADAM && kind <= K_RMSPROP, "mt_update: kind must be one of Y3D_OPT_ADAM .. Y3D_OPT_RMSPROP");
+  Y3D_CHECK(kind == K_RMSPROP ? momentum != nullptr : step_scalars != nullptr,
+            "mt_update: RMSprop needs the momentum table, the Adam family the step scalars");
+#define Y3D_UPD(K)                                                                                                                             \
+  hipLaunchKernelGGL(mt_update_kernel<K>, dim3(nchunks), dim3(256), 0, (hipStream_t)stream, (const long*)param_ptrs, (const long*)grad_ptrs,   \
+                     (const long*)s0_ptrs, (const long*)s1_ptrs, (const long*)sizes, lr, wd, momentum, chunk_tensor, chunk_off, chunk, beta1,  \
+                     beta2, eps, step_scalars, norm_clip)
+  switch (kind) {
+    case K_ADAM: Y3D_UPD(K_ADAM); break;
+    case K_ADAMAX: Y3D_UPD(K_ADAMAX); break;
+    case K_NADAM: Y3D_UPD(K_NADAM); break;
+    case K_RADAM: Y3D_UPD(K_RADAM); break;
+    default: Y3D_UPD(K_RMSPROP); break;
+  }
+#undef Y3D_UPD
+  Y3D_LAUNCH_CHECK();
+  return Y3D_OK;
+}
+
+int y3d_mt_sgd_tab(const int64_t* param_ptrs, const int64_t* grad_ptrs, const int64_t* buf_ptrs, const int64_t* sizes, const float* lr,
+                   const float* wd, const float* momentum, const int* chunk_tensor, const int* chunk_off, int nchunks, int chunk, int nesterov,
+                   int first_step, const float* norm_clip, void* stream) {
+  Y3D_CHECK(nchunks >= 1 && chunk >= 256, "mt_sgd_tab: empty chunk table");
+  Y3D_CHECK(momentum, "mt_sgd_tab: null momentum table");
+  hipLaunchKernelGGL(mt_sgd_tab_kernel, dim3(nchunks), dim3(256), 0, (hipStream_t)stream, (const long*)param_ptrs, (const long*)grad_ptrs,
+                     (const long*)buf_ptrs, (const long*)sizes, lr, wd, momentum, chunk_tensor, chunk_off, chunk, nesterov, first_step, norm_clip);
   Y3D_LAUNCH_CHECK();
   return Y3D_OK;
 }
