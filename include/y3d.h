@@ -733,6 +733,11 @@ int y3d_mt_sqnorm(const int64_t* grad_ptrs, const int64_t* sizes, const int* chu
  * all-reduced over RCCL (ddp.FlatGradReducer; reference: DistributedDataParallel's gradient buckets, engine/trainer.py:225-236) */
 int y3d_mt_copy(const int64_t* src_ptrs, const int64_t* dst_ptrs, const int64_t* sizes, const int* chunk_tensor, const int* chunk_off,
                 int nchunks, int chunk, float scale, void* stream);
+/* acc_t += grad_t for every tensor of the table (same table layout), one fp32 add per element: a micro-batch's gradients into the
+ * accumulation arena of optim.GradAccumulator (reference: the `accumulate` backward passes per optimizer step, engine/trainer.py:384-386,
+ * 411-413, which autograd adds tensor by tensor) */
+int y3d_mt_grad_acc(const int64_t* acc_ptrs, const int64_t* grad_ptrs, const int64_t* sizes, const int* chunk_tensor, const int* chunk_off,
+                    int nchunks, int chunk, void* stream);
 /* out[0] = total gradient L2 norm, out[1] = min(1, max_norm / (norm + 1e-6)) */
 int y3d_mt_clip_coef(const float* partials, int nchunks, float max_norm, float* out_norm_clip, void* stream);
 /* g = grad*clip (+ wd*p); buf = first ? g : momentum*buf + g; p -= lr * (nesterov ? g + momentum*buf : buf) */

@@ -356,9 +356,46 @@ __global__ __launch_bounds__(256) void mt_ema_kernel(const long* __restrict__ ep
   }
 }
 
+// acc_t[i] += grad_t[i] for every tensor t of the table: one micro-batch's gradients added into the accumulation arena
+// (optim.GradAccumulator; reference: autograd's AccumulateGrad over the `accumulate` backward passes of one optimizer step,
+// engine/trainer.py:384-386, 411-413).  Tables and chunking of mt_copy_kernel; 8 B read + 4 B written per element.
+__global__ __launch_bounds__(256) void mt_grad_acc_kernel(const long* __restrict__ aptr, const long* __restrict__ gptr, const long* __restrict__ sizes,
+                                                          const int* __restrict__ ctensor, const int* __restrict__ coff, int chunk) {
+  const int t = ctensor[blockIdx.x];
+  const long off = (long)coff[blockIdx.x] * chunk;
+  float* a = (float*)aptr[t] + off;
+  const float* g = (const float*)gptr[t] + off;
+  long n = sizes[t] - off;
+  if (n > chunk) n = chunk;
+  if (((((uintptr_t)a) | ((uintptr_t)g)) & 15) == 0) {
+    const long n4 = n >> 2;
+    for (long i = threadIdx.x; i < n4; i += 256) {
+      float4 A = ((float4*)a)[i];
+      const float4 G = ((const float4*)g)[i];
+      A.x += G.x;
+      A.y += G.y;
+      A.z += G.z;
+      A.w += G.w;
+      ((float4*)a)[i] = A;
+    }
+    for (long i = (n4 << 2) + threadIdx.x; i < n; i += 256) a[i] += g[i];
+  } else {
+    for (long i = threadIdx.x; i < n; i += 256) a[i] += g[i];
+  }
+}
+
 }  // namespace
 
 extern "C" {
+
+int y3d_mt_grad_acc(const int64_t* acc_ptrs, const int64_t* grad_ptrs, const int64_t* sizes, const int* chunk_tensor, const int* chunk_off,
+                    int nchunks, int chunk, void* stream) {
+  Y3D_CHECK(nchunks >= 1 && chunk >= 256, "mt_grad_acc: empty chunk table");
+  hipLaunchKernelGGL(mt_grad_acc_kernel, dim3(nchunks), dim3(256), 0, (hipStream_t)stream, (const long*)acc_ptrs, (const long*)grad_ptrs,
+                     (const long*)sizes, chunk_tensor, chunk_off, chunk);
+  Y3D_LAUNCH_CHECK();
+  return Y3D_OK;
+}
 
 int y3d_mt_copy(const int64_t* src_ptrs, const int64_t* dst_ptrs, const int64_t* sizes, const int* chunk_tensor, const int* chunk_off,
                 int nchunks, int chunk, float scale, void* stream) {

@@ -654,6 +654,141 @@ class ModelEMA:
                 setattr(self.ema, k, v)
 
 
+ACC_ALIGN = 4  # elements: every arena view starts on a 16-byte boundary, so the accumulate launch takes its 16-byte path
+
+
+def accum_layout(sizes, chunk=CHUNK, align=ACC_ALIGN):
+    """Host only: the arena of GradAccumulator for tensors of `sizes` elements.  -> (offsets, total): tensor t owns arena elements
+    [offsets[t], offsets[t] + sizes[t]), every offset a multiple of `align`, `total` the arena's length"""
+    offs, pos = [], 0
+    for n in sizes:
+        offs.append(pos)
+        pos += (int(n) + align - 1) // align * align
+    return offs, pos
+
+
+def chunk_map(sizes, chunk=CHUNK):
+    """Host only: the (chunk_tensor, chunk_off) tables of the multi-tensor launches: workgroup c handles elements
+    [chunk_off[c] * chunk, + chunk) of tensor chunk_tensor[c]"""
+    ct, co = [], []
+    for t, n in enumerate(sizes):
+        for c in range((int(n) + chunk - 1) // chunk):
+            ct.append(t)
+            co.append(c)
+    return ct, co
+
+
+class GradAccumulator:
+    """The gradient sum of the `accumulate` micro-batches of one optimizer step (engine/trainer.py:384-386, 411-413) in a flat fp32
+    arena, one `y3d_mt_grad_acc` launch per micro-batch instead of autograd's one add per parameter tensor:
+
+        loss.backward(); acc.add()      # every micro-batch: arena += p.grad for every parameter, p.grad = None
+        acc.bind(); opt.step(); acc.reset()
+
+    The arena of zeros is allocated on first use; parameter i owns the view `views[i]` at a multiple of 4 elements.  The first add()
+    after a reset() fixes the window's active set (the parameters that carry a gradient); a later add() with another set raises before
+    anything is launched - autograd would tolerate it, the tables do not.  bind() hands the arena views to the optimizer as `p.grad`:
+    fixed addresses, so its gradient pointer table is uploaded once.  reset() zeroes the arena, takes the views off the parameters and
+    forgets the set.  `count`: adds since the last reset."""
+
+    def __init__(self, params):
+        self.params = [p for p in params if p.requires_grad]
+        if not self.params:
+            raise ValueError("GradAccumulator: no parameters")
+        self.sizes = [p.numel() for p in self.params]
+        self.offsets, self.total = accum_layout(self.sizes)
+        self.arena = self.views = None
+        self.count = 0
+        self._active = None
+        self._tabs = {}
+        self._bound = False
+
+    def _ensure(self):
+        if self.arena is None:
+            dev = self.params[0].device
+            if dev.type != "cuda":
+                raise Y3DError("GradAccumulator needs parameters on a HIP device")
+            self.arena = torch.zeros(self.total, dtype=torch.float32, device=dev)
+            self.views = [self.arena[o:o + n].view_as(p) for o, n, p in zip(self.offsets, self.sizes, self.params)]
+        return self.arena
+
+    def _table(self, active):
+        key = tuple(active)
+        tb = self._tabs.get(key)
+        if tb is None:
+            dev = self._ensure().device
+            sizes = [self.sizes[i] for i in active]
+            ct, co = chunk_map(sizes)
+            tb = {"n": len(ct), "host_sizes": sizes, "sizes": torch.tensor(sizes, dtype=torch.int64, device=dev),
+                  "ct": torch.tensor(ct, dtype=torch.int32, device=dev), "co": torch.tensor(co, dtype=torch.int32, device=dev),
+                  "aptr": torch.tensor([self.views[i].data_ptr() for i in active], dtype=torch.int64, device=dev), "up": None, "gkey": None,
+                  "gptr": None}
+            self._tabs[key] = tb
+        return tb
+
+    @torch.no_grad()
+    def add(self, uploader=None):
+        """arena += p.grad over every parameter that has one, then p.grad = None.  uploader: a PtrUploader of the caller's (a hipGraph
+        capture keeps one of depth 1 alive for its replays); by default the accumulator's own rotating one, written only when the
+        gradient addresses changed"""
+        active = [i for i, p in enumerate(self.params) if p.grad is not None]
+        if not active:
+            raise Y3DError("GradAccumulator.add: no parameter has a gradient")
+        if self._bound:
+            raise Y3DError("GradAccumulator.add: the arena is bound as the parameters' gradients (bind()): reset() first")
+        if self._active is not None and active != self._active:
+            raise Y3DError(f"GradAccumulator.add: {len(active)} parameters carry a gradient, the window began with {len(self._active)} "
+                           "(the active set may not change between reset() calls)")
+        tb = self._table(active)
+        grads = []
+        for i in active:
+            p = self.params[i]
+            g = p.grad
+            if g.dtype != torch.float32 or not g.is_contiguous():
+                g = p.grad = g.float().contiguous()
+            grads.append(g)
+        if len(tb["host_sizes"]) != len(grads):
+            raise Y3DError(f"GradAccumulator.add: a table of {len(tb['host_sizes'])} tensors for {len(grads)} gradients")
+        for i, g, n in zip(active, grads, tb["host_sizes"]):
+            if not (n == self.params[i].numel() == g.numel()):
+                raise Y3DError(f"GradAccumulator.add: parameter {i} has {self.params[i].numel()} elements, its gradient {g.numel()}, "
+                               f"the table {n}")
+        gkey = [g.data_ptr() for g in grads]
+        if uploader is not None:
+            if uploader.n != len(gkey):
+                raise Y3DError(f"GradAccumulator.add: the uploader holds {uploader.n} pointers, {len(gkey)} gradients")
+            gptr = uploader.upload(gkey)
+        else:
+            if gkey != tb["gkey"]:
+                if tb["up"] is None:
+                    tb["up"] = PtrUploader(len(gkey), self.arena.device)
+                tb["gptr"], tb["gkey"] = tb["up"].upload(gkey), gkey
+            gptr = tb["gptr"]
+        lib().mt_grad_acc(tb["aptr"].data_ptr(), gptr.data_ptr(), tb["sizes"].data_ptr(), tb["ct"].data_ptr(), tb["co"].data_ptr(), tb["n"],
+                          CHUNK, ops.stream())
+        for i in active:
+            self.params[i].grad = None
+        self._active = active
+        self.count += 1
+
+    def bind(self):
+        """p.grad = the arena view, for the window's active set"""
+        if self._active is None:
+            raise Y3DError("GradAccumulator.bind: nothing was added since the last reset()")
+        for i in self._active:
+            self.params[i].grad = self.views[i]
+        self._bound = True
+
+    def reset(self):
+        if self.arena is not None:
+            self.arena.zero_()
+        if self._bound:
+            for i in self._active:
+                if self.params[i].grad is self.views[i]:
+                    self.params[i].grad = None
+        self._active, self._bound, self.count = None, False, 0
+
+
 OPTIMIZERS = ("Adam", "Adamax", "AdamW", "NAdam", "RAdam", "SGD", "auto")
 
 

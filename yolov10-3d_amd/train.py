@@ -1,0 +1,342 @@
+"""The training loop: the reference's `_setup_train` / `_do_train` (engine/trainer.py:307-322, 331-474) over the parts this package
+already has - a resident split's `epoch()`, the dual-assignment losses, `build_optimizer`, `optim.Schedule`, `optim.ModelEMA`, the
+one-call validators - with the `accumulate` micro-batches of an optimizer step summed by `optim.GradAccumulator` (one launch per
+micro-batch).  Micro-batches are launched eagerly; `graph.GraphedTrainStep` cannot express "backward without a step".
+
+    trainer = y3d.train.Trainer(model, kitti.DeviceSplit(root), lambda m: val.Validator3d(m, val_split, batch=64, plots=False),
+                                epochs=100, batch=32, save_dir="runs/s3d")
+    trainer.fit()
+
+What is restated, line by line (engine/trainer.py):
+  :307      accumulate = max(round(nbs / batch), 1)                                    plan()
+  :308      weight_decay * batch * accumulate / nbs                                    scaled_weight_decay()
+  :309      iterations = ceil(n / max(batch, nbs)) * epochs -> build_optimizer         optimizer_iterations()
+  :320      EarlyStopping(patience) (utils/torch_utils.py:553-595)                     EarlyStopping
+  :331-332  nb, nw                                                                     plan()
+  :365-371  close_mosaic / close_mixup: args.mosaic / args.mixup = 0 from epochs - close_* on
+  :377      optimizer.zero_grad() at the epoch start (drops a leftover micro-batch)    accum.reset()
+  :384-393  warm-up of accumulate, lr and momentum                                     plan(), Schedule.iteration
+  :403-405  tloss running mean (on the device; read back once per epoch)
+  :411-413  ni - last_opt_step >= accumulate -> optimizer_step                         plan()
+  :442      ema.update_attr
+  :445-449  when to validate, save_metrics (results.csv), the stopper
+  :454-455, :514-541  last.pt / best.pt / epoch{n}.pt
+  :470      scheduler.step()                                                           Schedule.epoch_end
+  :567-575  clip, step, zero_grad, ema.update                                          accum.bind / opt.step / accum.reset / ema.update
+  :588-591  best_fitness
+  :695-720  resume
+
+Where this loop differs, on purpose: a checkpoint holds state_dicts (the reference pickles the model objects and halves the EMA), the
+EMA stays fp32; a resumed run continues exactly where the straight run would be - the learning-rate factor of the epoch it starts, the
+accumulation window (`last_opt_step` comes from plan(), which always counts from epoch 0) and the random streams are restored, where the
+reference restarts its window counter and keeps the previous epoch's factor for one epoch; a step with a non-finite gradient norm is
+skipped on the device and the EMA update with it (optim.FusedSGD.step); there is no GradScaler (bf16 needs none), no callbacks but one
+`on_epoch_end` hook, no
+plots of training samples, no time limit, no AutoBatch, no multi-GPU, no HTL (the loss kernels take host gains)."""
+from __future__ import annotations
+
+import math
+import os
+import random
+from datetime import datetime
+
+import numpy as np
+import torch
+
+from . import loss as _loss
+from . import ops
+from ._lib import Y3DError
+from .optim import GradAccumulator, ModelEMA, Schedule, build_optimizer
+
+CKPT_KEYS = ("epoch", "best_fitness", "model", "ema", "updates", "optimizer", "train_args", "train_metrics", "history", "rng", "stopper", "date")
+EMA_ATTRS = ("yaml", "nc", "args", "names", "stride", "class_weights")  # engine/trainer.py:442
+
+
+def plan(n, batch, epochs, nbs=64, warmup_epochs=3.0):
+    """Host only.  One row (epoch, i, ni, accumulate, step) per iteration of a run over n images: `accumulate` as the reference holds
+    it at that iteration (engine/trainer.py:307, 384-386) and whether the optimizer steps after it (:411-413)."""
+    n, batch, epochs = int(n), int(batch), int(epochs)
+    if n < 1 or batch < 1 or epochs < 1:
+        raise Y3DError(f"plan: n = {n}, batch = {batch}, epochs = {epochs}")
+    nb = math.ceil(n / batch)
+    nw = max(round(warmup_epochs * nb), 100) if warmup_epochs > 0 else -1
+    accumulate = max(round(nbs / batch), 1)
+    last_opt_step = -1
+    rows = []
+    for ni in range(nb * epochs):
+        if ni <= nw:
+            accumulate = max(1, int(np.interp(ni, [0, nw], [1, nbs / batch]).round()))
+        step = ni - last_opt_step >= accumulate
+        if step:
+            last_opt_step = ni
+        rows.append((ni // nb, ni % nb, ni, accumulate, step))
+    return rows
+
+
+def scaled_weight_decay(weight_decay, batch, nbs=64):
+    """engine/trainer.py:307-308"""
+    return weight_decay * batch * max(round(nbs / batch), 1) / nbs
+
+
+def optimizer_iterations(n, batch, epochs, nbs=64):
+    """engine/trainer.py:309: what build_optimizer's `auto` decides on"""
+    return math.ceil(n / max(batch, nbs)) * epochs
+
+
+class EarlyStopping:
+    """utils/torch_utils.py:553-595: stop when `patience` epochs have passed without a fitness at least as good as the best"""
+
+    def __init__(self, patience=50):
+        self.best_fitness, self.best_epoch = 0.0, 0
+        self.patience = patience or float("inf")
+        self.possible_stop = False
+
+    def __call__(self, epoch, fitness):
+        if fitness is None:
+            return False
+        if fitness >= self.best_fitness:
+            self.best_epoch, self.best_fitness = epoch, fitness
+        delta = epoch - self.best_epoch
+        self.possible_stop = delta >= self.patience - 1
+        return delta >= self.patience
+
+    def state_dict(self):
+        return {"best_fitness": self.best_fitness, "best_epoch": self.best_epoch, "patience": self.patience, "possible_stop": self.possible_stop}
+
+    def load_state_dict(self, sd):
+        self.best_fitness, self.best_epoch, self.possible_stop = sd["best_fitness"], sd["best_epoch"], sd["possible_stop"]
+
+
+def better_fitness(best, fitness):
+    """engine/trainer.py:589-590 -> the new best_fitness"""
+    return fitness if (not best or best < fitness) else best
+
+
+def validates(epoch, epochs, val_period, possible_stop=False, stop=False, val=True):
+    """engine/trainer.py:445-446"""
+    return bool((val and ((epoch + 1) % val_period == 0 or (epochs - epoch) <= 10)) or epoch + 1 == epochs or possible_stop or stop)
+
+
+def preprocess_batch(batch):
+    """the builders' (B, H, W, 3) uint8 image as the (B, 3, H, W) view the stem takes; everything else as it is"""
+    img = batch["img"]
+    if img.dtype == torch.uint8 and img.dim() == 4 and img.shape[-1] == 3 and img.is_contiguous():
+        batch = dict(batch)
+        batch["img"] = img.permute(0, 3, 1, 2)
+    return batch
+
+
+def load_optimizer(opt, sd):
+    """a checkpoint's `optimizer` -> opt: torch's layout (groups' hyper-parameters, state buffers, Adam's step count), then the native
+    counters behind it (steps applied / skipped, NAdam's mu_product) exactly as they were"""
+    opt.load_state_dict(sd)
+    native = sd.get("native")
+    if native is not None and opt._state is None:
+        flat, _, _, present = opt._convert_torch(sd)
+        opt._seen.update(present)
+        opt.load_state_dict({"steps": native["steps"], "flat": flat, "norm_clip": native["norm_clip"]})
+
+
+class Trainer:
+    """`Trainer(model, train_split, validator).fit()`; see the module docstring.  Defaults: the reference's cfg/default.yaml.
+
+    train_split: anything with `__len__` and `epoch(batch, args, shuffle=, seed=)` that yields batch dicts on the model's device (the
+    four resident splits).  validator: `model -> callable -> results dict with "fitness"`, called once with the EMA model.
+    fit() seeds numpy, torch and random with `seed` (a resumed run restores their states instead); epoch e is drawn with seed + e.
+    After fit(): `history` (one dict per epoch: epoch, the loss items by name, lr/pg*, the validation results, fitness),
+    `best_fitness`, `ema`, `opt`."""
+
+    def __init__(self, model, train_split, validator=None, epochs=400, batch=32, nbs=64, optimizer="auto", lr0=0.001, lrf=0.01, momentum=0.937,
+                 weight_decay=0.0005, warmup_epochs=3.0, warmup_momentum=0.8, warmup_bias_lr=0.1, cos_lr=False, close_mixup=0, close_mosaic=0,
+                 val_period=1, patience=150, save_dir=None, save_period=-1, seed=0, data_args=None, max_norm=10.0, resume=None):
+        if getattr(getattr(model, "args", None), "htl", False):
+            raise NotImplementedError("Trainer: htl (hierarchical task learning) weights the loss items per epoch; the loss kernels take "
+                                      "their gains from the host when the criterion is built")
+        if int(batch) < 1 or int(epochs) < 1:
+            raise Y3DError(f"Trainer: batch = {batch}, epochs = {epochs}")
+        import torch.distributed as dist
+        if isinstance(model, torch.nn.parallel.DistributedDataParallel) or (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1):
+            raise Y3DError("Trainer: single GPU only (ddp.FlatGradReducer and its no_sync stay the caller's)")
+        self.ckpt = None
+        if resume is not None:
+            self.ckpt = torch.load(resume, map_location="cpu", weights_only=False)
+            missing = [k for k in CKPT_KEYS if k not in self.ckpt]
+            if missing:
+                raise Y3DError(f"Trainer: {resume} is not a checkpoint of this trainer (no {', '.join(missing)})")
+            if self.ckpt["epoch"] + 1 >= int(epochs) or self.ckpt["epoch"] < 0:
+                raise Y3DError(f"{resume} training to {int(epochs)} epochs is finished, nothing to resume.\n"
+                               "Start a new training without resuming, i.e. Trainer(...) without resume")
+        dev = next(model.parameters()).device
+        if dev.type != "cuda":
+            raise Y3DError(f"Trainer: the model must live on a HIP device, not {dev} (no host fallback)")
+        n = len(train_split)
+        if n < 1:
+            raise Y3DError("Trainer: the training split is empty")
+        self.model, self.split, self.make_validator, self.device = model, train_split, validator, dev
+        self.epochs, self.batch, self.nbs = int(epochs), int(batch), int(nbs)
+        self.train_args = dict(epochs=self.epochs, batch=self.batch, nbs=self.nbs, optimizer=optimizer, lr0=lr0, lrf=lrf, momentum=momentum,
+                               weight_decay=weight_decay, warmup_epochs=warmup_epochs, warmup_momentum=warmup_momentum,
+                               warmup_bias_lr=warmup_bias_lr, cos_lr=bool(cos_lr), close_mixup=close_mixup, close_mosaic=close_mosaic,
+                               val_period=val_period, patience=patience, save_period=save_period, seed=seed, max_norm=max_norm)
+        self.val_period, self.save_period, self.seed, self.max_norm = int(val_period), int(save_period), int(seed), max_norm
+        self.close_mixup, self.close_mosaic = int(close_mixup), int(close_mosaic)
+        self.save_dir = save_dir
+        if data_args is None:
+            from . import kitti
+            data_args = kitti.data_args()
+        self.data_args = data_args
+        self.nb = math.ceil(n / self.batch)
+        self.plan = plan(n, self.batch, self.epochs, self.nbs, warmup_epochs)
+        # engine/trainer.py:307-317
+        self.opt = build_optimizer(model, name=optimizer, lr=lr0, momentum=momentum, decay=scaled_weight_decay(weight_decay, self.batch, self.nbs),
+                                   iterations=optimizer_iterations(n, self.batch, self.epochs, self.nbs), device_momentum=True)
+        if self.opt.auto is not None:
+            warmup_bias_lr = self.opt.auto["warmup_bias_lr"]  # :763
+        for m in model.modules():  # the fused head's stacked storage, before the EMA copies the model
+            if hasattr(m, "restack"):
+                m.restack()
+        self.ema = ModelEMA(model)
+        # ... and the copy's own, before its first update: a restack REPLACES the BatchNorm buffer objects of the head, ModelEMA's table
+        # holds the objects it found at its first update, and the validator's forward would otherwise restack the copy behind its back
+        # (the updates after the first validation would then go to the orphaned buffers)
+        for m in self.ema.ema.modules():
+            if hasattr(m, "restack"):
+                m.restack()
+        self.sched = Schedule(self.opt, self.epochs, self.nb, lrf=lrf, cos_lr=cos_lr, warmup_epochs=warmup_epochs, warmup_momentum=warmup_momentum,
+                              warmup_bias_lr=warmup_bias_lr, nbs=self.nbs, batch=self.batch)
+        self.stopper, self.stop = EarlyStopping(patience), False
+        # no arena when no window of the run holds more than one micro-batch
+        self.accum = GradAccumulator(model.parameters()) if max(r[3] for r in self.plan) > 1 else None
+        self.names = _loss.loss_names(getattr(model, "args", None))
+        self.history, self.best_fitness, self.fitness, self.metrics = [], None, None, {}
+        self.start_epoch = 0
+        self.validator = None
+        self.on_epoch_end = None  # callable(history row): tools/train.py prints its line from it
+        if self.ckpt is not None:
+            self._resume(self.ckpt)
+
+    # ---- checkpoints ---------------------------------------------------------------------------------------------------------------
+    def _resume(self, ck):
+        """engine/trainer.py:695-720, and everything else the run holds"""
+        self.model.load_state_dict(ck["model"])
+        self.ema.ema.load_state_dict(ck["ema"])
+        self.ema.updates = ck["updates"]
+        load_optimizer(self.opt, ck["optimizer"])
+        self.best_fitness, self.history = ck["best_fitness"], list(ck["history"])
+        self.stopper.load_state_dict(ck["stopper"])
+        self.start_epoch = ck["epoch"] + 1
+        self.sched.epoch_end(ck["epoch"])  # the factor of the epoch the run continues with
+        ops.bump_weight_epoch()
+
+    def checkpoint(self, epoch):
+        opt_sd = self.opt.state_dict(torch_format=True)
+        st = self.opt._state
+        opt_sd["native"] = {"steps": self.opt._steps, "norm_clip": None if st is None else st["norm_clip"].detach().cpu().clone()}
+        cpu = lambda sd: {k: v.detach().cpu().clone() for k, v in sd.items()}
+        rng = {"numpy": np.random.get_state(), "torch": torch.get_rng_state(), "torch_cuda": torch.cuda.get_rng_state(self.device),
+               "random": random.getstate()}
+        return {"epoch": epoch, "best_fitness": self.best_fitness, "model": cpu(self.model.state_dict()),
+                "ema": {k: (v.float() if v.is_floating_point() else v) for k, v in cpu(self.ema.ema.state_dict()).items()},
+                "updates": self.ema.updates, "optimizer": opt_sd, "train_args": dict(self.train_args),
+                "train_metrics": {**self.metrics, "fitness": self.fitness}, "history": list(self.history), "rng": rng,
+                "stopper": self.stopper.state_dict(), "date": datetime.now().isoformat()}
+
+    def _save(self, epoch):
+        """engine/trainer.py:536-541"""
+        wdir = os.path.join(self.save_dir, "weights")
+        os.makedirs(wdir, exist_ok=True)
+        ck = self.checkpoint(epoch)
+        torch.save(ck, os.path.join(wdir, "last.pt"))
+        if self.best_fitness == self.fitness:
+            torch.save(ck, os.path.join(wdir, "best.pt"))
+        if self.save_period > 0 and epoch > 0 and epoch % self.save_period == 0:
+            torch.save(ck, os.path.join(wdir, f"epoch{epoch}.pt"))
+
+    def _save_metrics(self, epoch, row):
+        """engine/trainer.py:639-645"""
+        os.makedirs(self.save_dir, exist_ok=True)
+        path = os.path.join(self.save_dir, "results.csv")
+        keys, vals = list(row), list(row.values())
+        n = len(row) + 1
+        head = "" if os.path.exists(path) else (("%23s," * n % tuple(["epoch"] + keys)).rstrip(",") + "\n")
+        with open(path, "a") as f:
+            f.write(head + ("%23.5g," * n % tuple([epoch + 1] + vals)).rstrip(",") + "\n")
+
+    # ---- one micro-batch -----------------------------------------------------------------------------------------------------------
+    def _micro(self, batch):
+        """forward + loss + backward (+ accumulate) of one micro-batch -> loss items"""
+        loss, items = self.model(preprocess_batch(batch))
+        loss.backward()
+        del loss
+        if self.accum is not None:
+            self.accum.add()
+        return items
+
+    def _optimizer_step(self):
+        """engine/trainer.py:567-575"""
+        if self.accum is not None:
+            self.accum.bind()
+        self.opt.step(max_norm=self.max_norm)
+        if self.accum is not None:
+            self.accum.reset()
+        else:
+            self.opt.zero_grad(set_to_none=True)
+        self.ema.update(self.model, guard=self.opt.last_norm)
+
+    # ---- the loop ------------------------------------------------------------------------------------------------------------------
+    def fit(self):
+        if self.ckpt is None:
+            random.seed(self.seed)
+            np.random.seed(self.seed)
+            torch.manual_seed(self.seed)
+        else:
+            rng = self.ckpt["rng"]
+            random.setstate(rng["random"])
+            np.random.set_state(rng["numpy"])
+            torch.set_rng_state(rng["torch"])
+            torch.cuda.set_rng_state(rng["torch_cuda"], self.device)
+            self.ckpt = None
+        if self.make_validator is not None and self.validator is None:
+            self.validator = self.make_validator(self.ema.ema)
+        model, args = self.model, self.data_args
+        for epoch in range(self.start_epoch, self.epochs):
+            self.epoch = epoch
+            model.train()
+            if self.close_mosaic > 0 and epoch >= self.epochs - self.close_mosaic and hasattr(args, "mosaic"):
+                args.mosaic = 0.0
+            if self.close_mixup > 0 and epoch >= self.epochs - self.close_mixup and hasattr(args, "mixup"):
+                args.mixup = 0.0
+            # :377 zero_grad: a micro-batch left over from the last epoch's final window is dropped
+            if self.accum is not None:
+                self.accum.reset()
+            self.opt.zero_grad(set_to_none=True)
+            tloss = None
+            for i, batch in enumerate(self.split.epoch(self.batch, args, shuffle=True, seed=self.seed + epoch)):
+                _, _, ni, _, step = self.plan[epoch * self.nb + i]
+                self.sched.iteration(ni, epoch)
+                items = self._micro(batch).detach().float()
+                tloss = items.clone() if tloss is None else (tloss * i + items) / (i + 1)
+                if step:
+                    self._optimizer_step()
+            lr = {f"lr/pg{j}": g["lr"] for j, g in enumerate(self.opt.param_groups)}
+            self.ema.update_attr(model, include=EMA_ATTRS)
+            final = epoch + 1 == self.epochs
+            if self.validator is not None and validates(epoch, self.epochs, self.val_period, self.stopper.possible_stop, self.stop):
+                self.metrics = {k: float(v) for k, v in self.validator().items()}
+                self.fitness = self.metrics.pop("fitness", None)
+                self.best_fitness = better_fitness(self.best_fitness, self.fitness)
+            tloss = tloss.cpu()  # the epoch's one read-back of the loss items
+            names = self.names if len(self.names) == tloss.numel() else [f"loss_{j}" for j in range(tloss.numel())]  # (2D models)
+            losses = dict(zip(names, (float(v) for v in tloss)))
+            row = {**{f"train/{k}": v for k, v in losses.items()}, **self.metrics, **lr}
+            self.history.append({"epoch": epoch, **losses, **lr, **self.metrics, "fitness": self.fitness})
+            self.stop |= self.stopper(epoch + 1, self.fitness) or final
+            if self.save_dir is not None:
+                self._save_metrics(epoch, row)
+                self._save(epoch)
+            self.sched.epoch_end(epoch)
+            if self.on_epoch_end is not None:
+                self.on_epoch_end(self.history[-1])
+            if self.stop:
+                break
+        return self.history
