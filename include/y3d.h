@@ -357,6 +357,23 @@ int y3d_loss3d(int dtype, int nl, const void* const* maps, const int64_t* psw, v
                const int* W, const float* strides, int B, int nc, const float* gt, int n, const uint8_t* fg_mask,
                const int* target_gt_idx, const float* target_scores, const float* scal, float w_loss2d, float w_cls, float w_depth,
                float w_offset3d, float w_size3d, float w_heading, float grad_scale, float* partials, float* items, void* stream);
+/* y3d_loss3d with device-side item weights (hierarchical task learning, engine/trainer.py:398-400).  item_w: 6 device floats in the
+ * order of items[].  Every gradient channel belongs to one item - class logits: cls; nc+0..3: box2d; nc+4..5: offset3d; nc+6..8: size3d;
+ * nc+9..32: heading; nc+33..34: depth - and is stored as (d(item)/d(map) * grad_scale) * item_w[item].  items[6] stay UNWEIGHTED by
+ * item_w, exactly as y3d_loss3d writes them; total[0] = (float) sum_j (double)item_w[j] * (double)items[j], j ascending.
+ * grads == NULL: no gradient row is stored (a pass under no_grad).  Nothing is read back: item_w may change between two launches. */
+int y3d_loss3d_weighted(int dtype, int nl, const void* const* maps, const int64_t* psw, void* const* grads, const int64_t* gsw, const int* H,
+                        const int* W, const float* strides, int B, int nc, const float* gt, int n, const uint8_t* fg_mask,
+                        const int* target_gt_idx, const float* target_scores, const float* scal, float w_loss2d, float w_cls, float w_depth,
+                        float w_offset3d, float w_size3d, float w_heading, float grad_scale, float* partials, float* items,
+                        const float* item_w, float* total, void* stream);
+/* Hierarchical task learning, utils/htl.py:23-56 `compute_weight` on device state (htl.hip): one launch of one workgroup, fp32, in the
+ * reference's operation order.  items: the current 12 loss items (one-to-many set first); time_value = min((epoch - 5) / (T - 5), 1),
+ * computed by the caller in double.  State: ring (stat_epochs x 12 floats, oldest first) with its fill count, init_diff[12] with its
+ * have_init flag, weights[12] (output: w / sum(w) * 6), status (bit 0 is SET, never cleared, when a weight or the sum is not finite).
+ * stat_epochs in 3..8.  The current items enter the ring after the weights were computed. */
+int y3d_htl_update(const float* items, float time_value, int stat_epochs, float* ring, int* count, float* init_diff, int* have_init,
+                   float* weights, int* status, void* stream);
 
 /* Feature distillation, utils/loss.py:1156-1188 SupervisionLoss.forward_head as called at :893-898, for one head set (distill.hip).
  * embs[l]: (B, H[l], W[l], >= C) NHWC slice of the depth branch's first-layer output at level l (pointer at its channel 0, pixel

@@ -4,6 +4,7 @@
     python tools/train.py yolov10s_3D.yaml --data waymo/train.json --val waymo/val.json --dataset waymo         # Waymo / Omni3D split JSONs
     python tools/train.py yolov10n.yaml --data /data/coco/images/train2017 --val /data/coco/images/val2017     # 2D: image directories / lists
     python tools/train.py yolov10s_3D.yaml --data /data/kitti --resume runs/s3d/weights/last.pt --save-dir runs/s3d
+    python tools/train.py yolov10s_3D.yaml --data /data/kitti --htl --save-dir runs/s3d_htl                     # hierarchical task learning
 
 The training split is decoded once and held on the device (`kitti.DeviceSplit`, `json3d.DeviceSplit`, `yolo2d.DeviceSplit`); the
 validator (`val.Validator3d` / `val.Validator2d`, twice the training batch as in the reference) runs on the EMA model.  Without --val
@@ -50,6 +51,7 @@ def parser():
     ap.add_argument("--save-period", type=int, default=-1)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--max-norm", type=float, default=10.0)
+    ap.add_argument("--htl", action="store_true", help="3D models: hierarchical task learning (cfg/default.yaml:121), weights kept on the device")
     ap.add_argument("--resume", help="a last.pt of this trainer: continue at its epoch + 1")
     return ap
 
@@ -88,7 +90,7 @@ def main(argv=None):
                       momentum=a.momentum, weight_decay=a.weight_decay, warmup_epochs=a.warmup_epochs, warmup_momentum=a.warmup_momentum,
                       warmup_bias_lr=a.warmup_bias_lr, cos_lr=a.cos_lr, close_mixup=a.close_mixup, close_mosaic=a.close_mosaic,
                       val_period=a.val_period, patience=a.patience, save_dir=a.save_dir, save_period=a.save_period, seed=a.seed,
-                      data_args=data_args, max_norm=a.max_norm, resume=a.resume)
+                      data_args=data_args, max_norm=a.max_norm, resume=a.resume, htl=a.htl or None)
 
     def line(h):
         skip = ("epoch", "fitness")

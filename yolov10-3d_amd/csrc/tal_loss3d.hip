@@ -197,11 +197,19 @@ struct LossW { float loss2d, cls, depth, offset3d, size3d, heading; };
 // per anchor: six loss terms (already divided by the normalisers) and the gradient of their sum times `gscale` wrt the 38 logits
 // NC = number of classes as a template parameter: the gradient row gr[] is indexed by nc + j, and with a run-time nc the array
 // lived in scratch (176 B per lane)
-template <typename T, int NC>
+// WT = 1 (y3d_loss3d_weighted): every stored channel is multiplied by the device weight of the item it belongs to (item_w[6], in the
+// order of LossW / items[]), after the gscale product; `store` = 0 writes no gradient row at all.  The items stay unweighted.
+// item of row channel c (c < NC: a class logit): loss2d nc+0..3, offset3d nc+4..5, size3d nc+6..8, heading nc+9..32, depth nc+33..34
+template <int NC>
+__device__ __forceinline__ constexpr int item_of(int c) {
+  return c < NC ? 1 : (c < NC + 4 ? 0 : (c < NC + 6 ? 3 : (c < NC + 9 ? 4 : (c < NC + 33 ? 5 : 2))));
+}
+
+template <typename T, int NC, int WT>
 __global__ __launch_bounds__(256) void loss_kernel(Levels L, const unsigned char* __restrict__ fg, const int* __restrict__ gt_idx,
                                                    const float* __restrict__ tscores, const float* __restrict__ gt,
                                                    const float* __restrict__ scal, LossW w, float gscale, float* __restrict__ part,
-                                                   int n) {
+                                                   int n, const float* __restrict__ item_w, int store) {
   __shared__ float sh[6][256];
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   float l[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -286,8 +294,18 @@ __global__ __launch_bounds__(256) void loss_kernel(Levels L, const unsigned char
 #pragma unroll
       for (int j = 0; j < 12; ++j) gr[nc + 21 + j] = j == tb ? gres : 0.f;  // static indices: a run-time gr[.. + tb] puts gr[] in scratch
     }
+    if (WT) {
+      if (store) {
+        float iw[6];
 #pragma unroll
-    for (int c = 0; c < NC + 35; ++c) TT<T>::st(gp + c, gr[c] * gscale);
+        for (int j = 0; j < 6; ++j) iw[j] = item_w[j];
+#pragma unroll
+        for (int c = 0; c < NC + 35; ++c) TT<T>::st(gp + c, (gr[c] * gscale) * iw[item_of<NC>(c)]);
+      }
+    } else {
+#pragma unroll
+      for (int c = 0; c < NC + 35; ++c) TT<T>::st(gp + c, gr[c] * gscale);
+    }
   }
 #pragma unroll
   for (int j = 0; j < 6; ++j) sh[j][threadIdx.x] = l[j];
@@ -302,9 +320,12 @@ __global__ __launch_bounds__(256) void loss_kernel(Levels L, const unsigned char
   if (threadIdx.x < 6) part[(long)blockIdx.x * 6 + threadIdx.x] = sh[threadIdx.x][0];
 }
 
-__global__ __launch_bounds__(256) void loss_final_kernel(const float* __restrict__ part, int nblk, float* __restrict__ items) {
+// item_w != NULL (y3d_loss3d_weighted): total[0] = (float) sum_j (double)item_w[j] * (double)items[j], j ascending
+__global__ __launch_bounds__(256) void loss_final_kernel(const float* __restrict__ part, int nblk, float* __restrict__ items,
+                                                         const float* __restrict__ item_w, float* __restrict__ total) {
   // 6 loss items x nblk block partials: 240 threads = 40 row lanes x 6 items, fp64, folded through LDS in a fixed order
   __shared__ double sh[40][6];
+  __shared__ float fin[6];
   const int t = threadIdx.x;
   const int j = t % 6, r = t / 6;
   if (r < 40) {
@@ -318,6 +339,15 @@ __global__ __launch_bounds__(256) void loss_final_kernel(const float* __restrict
 #pragma unroll
     for (int k = 0; k < 40; ++k) a += sh[k][t];
     items[t] = (float)a;
+    fin[t] = (float)a;
+  }
+  if (item_w == nullptr) return;
+  __syncthreads();
+  if (t == 0) {
+    double a = 0.0;
+#pragma unroll
+    for (int j = 0; j < 6; ++j) a += (double)item_w[j] * (double)fin[j];
+    total[0] = (float)a;
   }
 }
 
@@ -403,12 +433,37 @@ int y3d_loss3d(int dtype, int nl, const void* const* maps, const int64_t* psw, v
   LossW w{w_loss2d, w_cls, w_depth, w_offset3d, w_size3d, w_heading};
   hipStream_t st = (hipStream_t)stream;
   int nblk = cdiv((long)B * L.A, 256);
-#define Y3D_L3D(T, NC) hipLaunchKernelGGL((loss_kernel<T, NC>), dim3(nblk), dim3(256), 0, st, L, fg_mask, target_gt_idx, target_scores, gt, scal, w, grad_scale, partials, n)
+#define Y3D_L3D(T, NC) hipLaunchKernelGGL((loss_kernel<T, NC, 0>), dim3(nblk), dim3(256), 0, st, L, fg_mask, target_gt_idx, target_scores, gt, scal, w, grad_scale, partials, n, (const float*)nullptr, 1)
 #define Y3D_L3D_NC(T) switch (nc) { case 1: Y3D_L3D(T, 1); break; case 2: Y3D_L3D(T, 2); break; case 3: Y3D_L3D(T, 3); break; case 4: Y3D_L3D(T, 4); break; default: Y3D_L3D(T, 5); break; }
   if (dtype == Y3D_BF16) { Y3D_L3D_NC(bf16_t) } else { Y3D_L3D_NC(float) }
 #undef Y3D_L3D_NC
 #undef Y3D_L3D
-  hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(256), 0, st, partials, nblk, items);
+  hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(256), 0, st, partials, nblk, items, (const float*)nullptr, (float*)nullptr);
+  Y3D_LAUNCH_CHECK();
+  return Y3D_OK;
+}
+
+int y3d_loss3d_weighted(int dtype, int nl, const void* const* maps, const int64_t* psw, void* const* grads, const int64_t* gsw, const int* H,
+                        const int* W, const float* strides, int B, int nc, const float* gt, int n, const uint8_t* fg_mask,
+                        const int* target_gt_idx, const float* target_scores, const float* scal, float w_loss2d, float w_cls, float w_depth,
+                        float w_offset3d, float w_size3d, float w_heading, float grad_scale, float* partials, float* items,
+                        const float* item_w, float* total, void* stream) {
+  Levels L;
+  if (fill_levels(L, dtype, nl, maps, psw, grads, gsw, H, W, strides, B, nc, nc + 35)) return Y3D_ERR_INVALID;
+  Y3D_CHECK(item_w && total, "loss3d_weighted: item_w and total must be device pointers");
+  if (grads) {
+    for (int i = 0; i < nl; ++i) Y3D_CHECK(grads[i] != nullptr, "loss3d_weighted: grads[%d] is NULL (pass grads = NULL to store no rows)", i);
+  }
+  const int store = grads ? 1 : 0;
+  LossW w{w_loss2d, w_cls, w_depth, w_offset3d, w_size3d, w_heading};
+  hipStream_t st = (hipStream_t)stream;
+  int nblk = cdiv((long)B * L.A, 256);
+#define Y3D_L3D(T, NC) hipLaunchKernelGGL((loss_kernel<T, NC, 1>), dim3(nblk), dim3(256), 0, st, L, fg_mask, target_gt_idx, target_scores, gt, scal, w, grad_scale, partials, n, item_w, store)
+#define Y3D_L3D_NC(T) switch (nc) { case 1: Y3D_L3D(T, 1); break; case 2: Y3D_L3D(T, 2); break; case 3: Y3D_L3D(T, 3); break; case 4: Y3D_L3D(T, 4); break; default: Y3D_L3D(T, 5); break; }
+  if (dtype == Y3D_BF16) { Y3D_L3D_NC(bf16_t) } else { Y3D_L3D_NC(float) }
+#undef Y3D_L3D_NC
+#undef Y3D_L3D
+  hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(256), 0, st, partials, nblk, items, item_w, total);
   Y3D_LAUNCH_CHECK();
   return Y3D_OK;
 }

@@ -13,6 +13,9 @@ as test comparators live in tests/torch_assigners.py, not here.
 Feature distillation (`distillation: True`; SupervisionLoss.forward_head :1156-1188): the seventh item of each 3D head set runs on
 csrc/distill.hip (`DistillFn`) over a teacher feature map the caller supplies (batch["teacher_emb"] or `set_teacher`); the DINOv2
 teacher network itself is not part of the package.
+
+Hierarchical task learning (`htl: True`, engine/trainer.py:398-400): `DetectLoss3d.set_item_weights(table)` makes both 3D routes read 12
+device weights (train.HtlWeights) in the kernel `y3d_loss3d_weighted`: gradient rows times the weight of their item, loss = sum(w * items).
 """
 from __future__ import annotations
 
@@ -263,15 +266,19 @@ def loss_names(args):
 
 def _loss3d_set(cfg, gt, n_used, calib, mean_sizes, map_ptrs, psw, grad_ptrs, gsw, Hs, Ws, B, dtype, dev):
     """one head set on the HIP kernels: assignment + six loss items + gradient rows written at grad_ptrs (pixel stride gsw).
-    -> (items[6], fg (B, A) uint8, gt_idx (B, A) int32, target_scores (B, A, nc))"""
+    -> (items[6], fg (B, A) uint8, gt_idx (B, A) int32, target_scores (B, A, nc))
+    A cfg with an item-weight table (cfg[8]: 6 device floats, `set_item_weights`) takes y3d_loss3d_weighted instead: the rows come out
+    times the weight of their item, the items as ever, and a fifth result `total` (1 float) = sum(item_w * items); grad_ptrs None (a
+    pass under no_grad): no rows are stored."""
     L = lib()
     strides, nc, topk, alpha, beta, gamma, w = cfg[:7]
     mode = cfg[7] if len(cfg) > 7 else 11  # assigner mode bits (include/y3d.h: y3d_tal3d_assign); default tal_2d | tal_3d | constrain_anchors, l1
+    item_w = cfg[8] if len(cfg) > 8 else None
     dt, st, nl = ops.code(dtype), ops.stream(), len(map_ptrs)
     A = sum(h * w_ for h, w_ in zip(Hs, Ws))
     n = gt.shape[1]
     PV = ctypes.c_void_p * nl
-    c_maps, c_grads = PV(*map_ptrs), PV(*grad_ptrs)
+    c_maps, c_grads = PV(*map_ptrs), (PV(*grad_ptrs) if grad_ptrs is not None else None)
     c_psw, c_gsw = (ctypes.c_int64 * nl)(*psw), (ctypes.c_int64 * nl)(*gsw)
     c_H, c_W = (ctypes.c_int * nl)(*Hs), (ctypes.c_int * nl)(*Ws)
     c_st = (ctypes.c_float * nl)(*strides)
@@ -291,6 +298,12 @@ def _loss3d_set(cfg, gt, n_used, calib, mean_sizes, map_ptrs, psw, grad_ptrs, gs
     nblk = (B * A + 255) // 256
     part = torch.empty(nblk * 6, dtype=torch.float32, device=dev)
     items = torch.empty(6, dtype=torch.float32, device=dev)
+    if item_w is not None:
+        total = torch.empty(1, dtype=torch.float32, device=dev)
+        L.loss3d_weighted(dt, nl, c_maps, c_psw, c_grads, c_gsw, c_H, c_W, c_st, B, nc, gt.data_ptr(), n, fg.data_ptr(), gi.data_ptr(),
+                          ts.data_ptr(), scal.data_ptr(), w[0], w[1], w[2], w[3], w[4], w[5], 1.0, part.data_ptr(), items.data_ptr(),
+                          item_w.data_ptr(), total.data_ptr(), st)
+        return items, fg, gi, ts, total
     L.loss3d(dt, nl, c_maps, c_psw, c_grads, c_gsw, c_H, c_W, c_st, B, nc, gt.data_ptr(), n, fg.data_ptr(), gi.data_ptr(), ts.data_ptr(),
              scal.data_ptr(), w[0], w[1], w[2], w[3], w[4], w[5], 1.0, part.data_ptr(), items.data_ptr(), st)
     return items, fg, gi, ts
@@ -299,7 +312,8 @@ def _loss3d_set(cfg, gt, n_used, calib, mean_sizes, map_ptrs, psw, grad_ptrs, gs
 class Loss3dFn(torch.autograd.Function):
     """One head set: task-aligned assignment (no grad) + the six 3D loss terms + d(sum of terms)/d(head maps), on the fused HIP
     kernels.  apply(cfg, gt(B,n,17), n_used, calib, mean_sizes, *maps) -> (sum_of_items, items[6], fg_mask, target_gt_idx, target_scores);
-    n_used: device int32 from pad_targets (or None: walk all n rows)."""
+    n_used: device int32 from pad_targets (or None: walk all n rows).  A cfg of `DDDetectionLoss.cfg` with an item-weight table
+    (`set_item_weights`): the weighted entry, sum_of_items = sum(table * items), and no gradient rows when the cfg was made under no_grad."""
 
     @staticmethod
     def forward(ctx, cfg, gt, n_used, calib, mean_sizes, *maps):
@@ -309,21 +323,23 @@ class Loss3dFn(torch.autograd.Function):
                 raise Y3DError("Loss3dFn: head maps must be pixel-dense NHWC tensors on a HIP device")
         B, no = maps[0].shape[:2]
         Hs, Ws = [m.shape[2] for m in maps], [m.shape[3] for m in maps]
-        grads = [ops.nhwc_empty(B, no, h, w_, dtype, dev) for h, w_ in zip(Hs, Ws)]
-        items, fg, gi, ts = _loss3d_set(cfg, gt.float().contiguous(), n_used, calib.float().contiguous(), mean_sizes.float().contiguous(),
-                                        [m.data_ptr() for m in maps], [m.stride(3) for m in maps], [g.data_ptr() for g in grads],
-                                        [no] * len(maps), Hs, Ws, B, dtype, dev)
+        weighted, store = len(cfg) > 8, not (len(cfg) > 9 and not cfg[9])
+        grads = [ops.nhwc_empty(B, no, h, w_, dtype, dev) for h, w_ in zip(Hs, Ws)] if store else []
+        items, fg, gi, ts, *tot = _loss3d_set(cfg, gt.float().contiguous(), n_used, calib.float().contiguous(), mean_sizes.float().contiguous(),
+                                              [m.data_ptr() for m in maps], [m.stride(3) for m in maps],
+                                              [g.data_ptr() for g in grads] if store else None, [no] * len(maps), Hs, Ws, B, dtype, dev)
         ctx.save_for_backward(*grads)
+        ctx.nmaps = len(maps)
         ctx.set_materialize_grads(False)  # no zero-filled gradients for the assignment outputs
-        total = items.sum()
+        total = tot[0].reshape(()) if weighted else items.sum()
         ctx.mark_non_differentiable(items, fg, gi, ts)
         return total, items, fg, gi, ts
 
     @staticmethod
     def backward(ctx, d_total, *unused):
         grads = ctx.saved_tensors
-        if d_total is None:
-            return (None,) * (5 + len(grads))
+        if d_total is None or not grads:
+            return (None,) * (5 + ctx.nmaps)
         return (None, None, None, None, None, *[g * d_total.to(g.dtype) for g in grads])
 
 
@@ -343,24 +359,27 @@ class DualLoss3dFn(torch.autograd.Function):
         B, no2 = maps[0].shape[:2]
         no, esz = no2 // 2, maps[0].element_size()
         Hs, Ws = [m.shape[2] for m in maps], [m.shape[3] for m in maps]
-        grads = [ops.nhwc_empty(B, no2, h, w_, dtype, dev) for h, w_ in zip(Hs, Ws)]
+        weighted, store = len(cfg1) > 8, not (len(cfg1) > 9 and not cfg1[9])
+        grads = [ops.nhwc_empty(B, no2, h, w_, dtype, dev) for h, w_ in zip(Hs, Ws)] if store else []
         gt, calib, mean_sizes = gt.float().contiguous(), calib.float().contiguous(), mean_sizes.float().contiguous()
         outs = []
         for cfg, off in ((cfg1, 0), (cfgm, no)):
             outs.append(_loss3d_set(cfg, gt, n_used, calib, mean_sizes, [m.data_ptr() + off * esz for m in maps], [m.stride(3) for m in maps],
-                                    [g.data_ptr() + off * esz for g in grads], [no2] * len(maps), Hs, Ws, B, dtype, dev))
+                                    [g.data_ptr() + off * esz for g in grads] if store else None, [no2] * len(maps), Hs, Ws, B, dtype, dev))
         ctx.save_for_backward(*grads)
-        ctx.no = no
+        ctx.no, ctx.nmaps = no, len(maps)
         ctx.set_materialize_grads(False)
-        (i1, fg1, gi1, ts1), (im, fgm, gim, tsm) = outs
+        (i1, fg1, gi1, ts1, *tot1), (im, fgm, gim, tsm, *totm) = outs
         ctx.mark_non_differentiable(i1, im, fg1, gi1, ts1, fgm, gim, tsm)
+        if weighted:  # the item-weight table is set: the two `total`s of y3d_loss3d_weighted
+            return tot1[0].reshape(()), i1, totm[0].reshape(()), im, fg1, gi1, ts1, fgm, gim, tsm
         return i1.sum(), i1, im.sum(), im, fg1, gi1, ts1, fgm, gim, tsm
 
     @staticmethod
     def backward(ctx, d1, _i1, dm, *unused):
         grads = ctx.saved_tensors
-        if d1 is None and dm is None:
-            return (None,) * (6 + len(grads))
+        if (d1 is None and dm is None) or not grads:
+            return (None,) * (6 + ctx.nmaps)
         no = ctx.no
         z = torch.zeros((), dtype=torch.float32, device=grads[0].device)
         scale = torch.cat(((d1 if d1 is not None else z).float().reshape(1).expand(no), (dm if dm is not None else z).float().reshape(1).expand(no)))
@@ -391,7 +410,18 @@ class DDDetectionLoss:
             if h.distillation_loss not in CRITERIA:
                 raise RuntimeError(f"Unknown criterion function: {h.distillation_loss}")  # the reference's message, loss.py:1185
             self.dis = (float(h.distillation_temp), float(h.distillation_weight), CRITERIA[h.distillation_loss], bool(h.distillation_no_mixup))
+        self.item_w = None
 
+    def set_item_weights(self, table):
+        """`table`: 6 device floats (in the order of the loss items: box, cls, dep, o3d, s3d, hd) that weight this head set's items,
+        read by the loss kernel at every call - whoever owns the tensor may change its contents between calls (train.HtlWeights) - or
+        None: the calls of before.  With a table the loss is sum(table * items), NOT times the batch size (engine/trainer.py:398-400)."""
+        if table is not None:
+            if self.distillation:
+                raise NotImplementedError("item weights (htl) with distillation: the reference multiplies 12 weights into 14 items")
+            if not (torch.is_tensor(table) and table.is_cuda and table.dtype == torch.float32 and table.numel() == 6 and table.is_contiguous()):
+                raise Y3DError("set_item_weights: 6 contiguous fp32 values on a HIP device (no host path)")
+        self.item_w = table
     GT_KEYS = ("batch_idx", "cls", "bboxes", "center_2d", "size_2d", "center_3d", "size_3d", "depth", "heading_bin", "heading_res")
 
     def targets(self, batch, B, H, W, dev):
@@ -419,6 +449,8 @@ class DDDetectionLoss:
         with (_tap_scal() if self.distillation else contextlib.nullcontext()) as tap:
             total, items, fg, gt_idx, t_sc = Loss3dFn.apply(self.cfg(len(feats)), g, n_used, batch["calib"].to(dev), batch["mean_sizes"].to(dev), *maps)
         self._assignment = (fg, gt_idx, t_sc)
+        if self.item_w is not None:
+            return total, items
         if not self.distillation:
             return total * B, items
         if embeddings is None:
@@ -456,8 +488,12 @@ class DDDetectionLoss:
 
     def cfg(self, nl):
         h = self.hyp
-        return (self.stride[:nl], self.nc, self.topk, float(h.tal_alpha), float(h.tal_beta), float(h.tal_gamma),
-                (float(h.loss2d), float(h.cls), float(h.depth), float(h.offset3d), float(h.size3d), float(h.heading)), self.mode)
+        cfg = (self.stride[:nl], self.nc, self.topk, float(h.tal_alpha), float(h.tal_beta), float(h.tal_gamma),
+               (float(h.loss2d), float(h.cls), float(h.depth), float(h.offset3d), float(h.size3d), float(h.heading)), self.mode)
+        if self.item_w is None:
+            return cfg
+        # ... the table, and whether gradient rows are wanted (read HERE: inside an autograd Function's forward grad mode is always off)
+        return cfg + (self.item_w, torch.is_grad_enabled())
 
     @property
     def last_assignment(self):
@@ -473,6 +509,12 @@ class DetectLoss3d:
         self.one2many = DDDetectionLoss(model, tal_topk=model.args.tal_topk)
         self.one2one = DDDetectionLoss(model, tal_topk=1)
 
+    def set_item_weights(self, table):
+        """`table`: 12 device floats, the one-to-many set's six first (`loss_names`), or None; see DDDetectionLoss.set_item_weights"""
+        if table is not None and not (torch.is_tensor(table) and table.numel() == 12 and table.dim() == 1):
+            raise Y3DError("set_item_weights: a 1-D tensor of 12 values")
+        self.one2many.set_item_weights(None if table is None else table[0:6])
+        self.one2one.set_item_weights(None if table is None else table[6:12])
     @staticmethod
     def _shared_maps(maps, o2o, o2m, no):
         """`maps`: the head's own (B, 2*no, H, W) tensors (preds["_y3d_maps"], written by v10Detect3d.forward_train_fused), accepted
@@ -519,6 +561,8 @@ class DetectLoss3d:
                     t1, i1, tm, im, fg1, gi1, ts1, fgm, gim, tsm = DualLoss3dFn.apply(self.one2one.cfg(nl), self.one2many.cfg(nl), g, n_used, batch["calib"].to(dev),
                                                                                       batch["mean_sizes"].to(dev), *bases)
                 self.one2one._assignment, self.one2many._assignment = (fg1, gi1, ts1), (fgm, gim, tsm)
+                if self.one2one.item_w is not None:
+                    return tm + t1, torch.cat((im, i1))
                 if not dist:
                     return tm * B + t1 * B, torch.cat((im, i1))
                 e1, em = preds["o2o_embs"], preds["o2m_embs"]

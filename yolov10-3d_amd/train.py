@@ -32,7 +32,18 @@ accumulation window (`last_opt_step` comes from plan(), which always counts from
 reference restarts its window counter and keeps the previous epoch's factor for one epoch; a step with a non-finite gradient norm is
 skipped on the device and the EMA update with it (optim.FusedSGD.step); there is no GradScaler (bf16 needs none), no callbacks but one
 `on_epoch_end` hook, no
-plots of training samples, no time limit, no AutoBatch, no multi-GPU, no HTL (the loss kernels take host gains)."""
+plots of training samples, no time limit, no AutoBatch, no multi-GPU.
+
+Hierarchical task learning (`htl`, engine/trainer.py:349-358, 398-400, 498-512 + utils/htl.py): `HtlWeights` keeps the reference's
+`Hierarchical_Task_Learning` state on the device and `y3d_htl_update` restates `compute_weight` there; the criterion reads the 12 weights
+from that table (loss.DetectLoss3d.set_item_weights -> y3d_loss3d_weighted), so nothing about the weights crosses to the host but the
+epoch's one read-back.  Restated with its quirks: the e0 pass runs in train mode under no_grad (BatchNorm statistics move) and divides
+by the number of batches; from the second epoch on the weights come from the LAST micro-batch of the epoch before (:398); the loss is
+weights @ items without `* batch_size`; stat_epoch_nums = 5 and max_epochs = 200 whatever the run's `epochs`.  Where it differs, on
+purpose: a resumed run restores the state (and the last micro-batch's items) from the checkpoint's optional "htl" entry instead of
+repeating the e0 pass with a fresh `Hierarchical_Task_Learning`, and continues bit for bit; a non-finite weight raises Y3DError at the
+end of its epoch, naming the items (the reference dies with a KeyError inside its diagnostic print, htl.py:48-51), and the optimizer's
+device-side skip rule has kept that epoch's steps from being applied."""
 from __future__ import annotations
 
 import math
@@ -126,6 +137,55 @@ def preprocess_batch(batch):
     return batch
 
 
+HTL_STAT_EPOCHS, HTL_MAX_EPOCHS = 5, 200  # utils/htl.py:4, never overridden by engine/trainer.py:351
+
+
+def htl_time_value(epoch, max_epochs=HTL_MAX_EPOCHS):
+    """utils/htl.py:41, with its literal 5"""
+    return min((epoch - 5) / (max_epochs - 5), 1.0)
+
+
+class HtlWeights:
+    """utils/htl.py `Hierarchical_Task_Learning` as device state: the list of past losses (a ring of stat_epochs x 12 floats, oldest first,
+    and its fill count), `init_diff` and whether it exists, the 12 weights, and a status word whose bit 0 is set once a weight or their sum
+    was not finite.  `table` (12 floats) keeps its address for the life of the object: hand it to `criterion.set_item_weights` once.
+    `update(items, epoch)` is `compute_weight(items, epoch)`: one launch, nothing read back."""
+    PARTS = (("weights", 0, 12), ("init_diff", 12, 12), ("ring", 24, 96))  # floats of `buf`; int words: 120 count, 121 have_init, 122 status
+
+    def __init__(self, device, stat_epochs=HTL_STAT_EPOCHS, max_epochs=HTL_MAX_EPOCHS):
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise NotImplementedError("HtlWeights (htl): the weight table lives on a HIP device; there is no host path")
+        if not 3 <= int(stat_epochs) <= 8:
+            raise Y3DError(f"HtlWeights: stat_epochs = {stat_epochs}, 3..8")
+        self.stat_epochs, self.max_epochs = int(stat_epochs), int(max_epochs)
+        self.buf = torch.zeros(124, dtype=torch.float32, device=device)
+        self.table, self.init_diff, self.ring = (self.buf[o:o + n] for _, o, n in self.PARTS)
+        self.ints = self.buf[120:124].view(torch.int32)
+        self.status = self.ints[2:3]
+
+    def update(self, items, epoch):
+        if not (torch.is_tensor(items) and items.is_cuda and items.dtype == torch.float32 and items.numel() == 12 and items.is_contiguous()):
+            raise Y3DError("HtlWeights.update: the 12 loss items as contiguous fp32 on the HIP device")
+        i = self.ints
+        _loss.lib().htl_update(items.data_ptr(), float(htl_time_value(epoch, self.max_epochs)), self.stat_epochs, self.ring.data_ptr(),
+                               i[0:].data_ptr(), self.init_diff.data_ptr(), i[1:].data_ptr(), self.table.data_ptr(), i[2:].data_ptr(), ops.stream())
+        return self.table
+
+    def state_dict(self):
+        sd = {k: self.buf[o:o + n].cpu().clone() for k, o, n in self.PARTS}
+        ints = self.ints.cpu()
+        return {**sd, "count": int(ints[0]), "have_init": int(ints[1]), "status": int(ints[2]), "stat_epochs": self.stat_epochs,
+                "max_epochs": self.max_epochs}
+
+    def load_state_dict(self, sd):
+        if sd["stat_epochs"] != self.stat_epochs or sd["max_epochs"] != self.max_epochs:
+            raise Y3DError(f"HtlWeights: the state was kept for stat_epochs = {sd['stat_epochs']}, max_epochs = {sd['max_epochs']}")
+        for k, o, n in self.PARTS:
+            self.buf[o:o + n].copy_(sd[k])
+        self.ints.copy_(torch.tensor([sd["count"], sd["have_init"], sd["status"], 0], dtype=torch.int32))
+
+
 def load_optimizer(opt, sd):
     """a checkpoint's `optimizer` -> opt: torch's layout (groups' hyper-parameters, state buffers, Adam's step count), then the native
     counters behind it (steps applied / skipped, NAdam's mu_product) exactly as they were"""
@@ -143,15 +203,25 @@ class Trainer:
     train_split: anything with `__len__` and `epoch(batch, args, shuffle=, seed=)` that yields batch dicts on the model's device (the
     four resident splits).  validator: `model -> callable -> results dict with "fitness"`, called once with the EMA model.
     fit() seeds numpy, torch and random with `seed` (a resumed run restores their states instead); epoch e is drawn with seed + e.
-    After fit(): `history` (one dict per epoch: epoch, the loss items by name, lr/pg*, the validation results, fitness),
+    htl: hierarchical task learning (module docstring); None follows `model.args.htl`.  3D models only, not with distillation.
+    After fit(): `history` (one dict per epoch: epoch, the loss items by name, htl/<name> weights when htl is on, lr/pg*, the validation
+    results, fitness),
     `best_fitness`, `ema`, `opt`."""
 
     def __init__(self, model, train_split, validator=None, epochs=400, batch=32, nbs=64, optimizer="auto", lr0=0.001, lrf=0.01, momentum=0.937,
                  weight_decay=0.0005, warmup_epochs=3.0, warmup_momentum=0.8, warmup_bias_lr=0.1, cos_lr=False, close_mixup=0, close_mosaic=0,
-                 val_period=1, patience=150, save_dir=None, save_period=-1, seed=0, data_args=None, max_norm=10.0, resume=None):
-        if getattr(getattr(model, "args", None), "htl", False):
-            raise NotImplementedError("Trainer: htl (hierarchical task learning) weights the loss items per epoch; the loss kernels take "
-                                      "their gains from the host when the criterion is built")
+                 val_period=1, patience=150, save_dir=None, save_period=-1, seed=0, data_args=None, max_norm=10.0, resume=None, htl=None):
+        if htl is None:
+            htl = getattr(getattr(model, "args", None), "htl", False)
+        if htl:
+            if next(model.parameters()).device.type != "cuda":
+                raise NotImplementedError("Trainer: htl (hierarchical task learning) keeps its weight table on the device and weights the "
+                                          "items in the loss kernels: the model must live on a HIP device (no host path)")
+            from .tasks import YOLOv10_3DDetectionModel
+            if not isinstance(model, YOLOv10_3DDetectionModel):
+                raise NotImplementedError("Trainer: htl weights the 12 items of the 3D loss; a 2D model's reference items carry no graph")
+            if getattr(model.args, "distillation", False):
+                raise NotImplementedError("Trainer: htl with distillation: the reference multiplies 12 weights into 14 items")
         if int(batch) < 1 or int(epochs) < 1:
             raise Y3DError(f"Trainer: batch = {batch}, epochs = {epochs}")
         import torch.distributed as dist
@@ -212,6 +282,12 @@ class Trainer:
         self.start_epoch = 0
         self.validator = None
         self.on_epoch_end = None  # callable(history row): tools/train.py prints its line from it
+        self.htl, self._ei = None, None  # the weight state; the loss items the next update takes (engine/trainer.py:350, 398)
+        if htl:
+            self.htl = HtlWeights(dev)
+            if not hasattr(model, "criterion"):
+                model.criterion = model.init_criterion()
+            model.criterion.set_item_weights(self.htl.table)
         if self.ckpt is not None:
             self._resume(self.ckpt)
 
@@ -226,6 +302,11 @@ class Trainer:
         self.stopper.load_state_dict(ck["stopper"])
         self.start_epoch = ck["epoch"] + 1
         self.sched.epoch_end(ck["epoch"])  # the factor of the epoch the run continues with
+        if self.htl is not None:
+            if "htl" not in ck:
+                raise Y3DError("Trainer: htl is on and the checkpoint holds no htl state (it was written by a run without htl)")
+            self.htl.load_state_dict(ck["htl"]["state"])
+            self._ei = ck["htl"]["items"].to(self.device).float().contiguous()
         ops.bump_weight_epoch()
 
     def checkpoint(self, epoch):
@@ -235,11 +316,28 @@ class Trainer:
         cpu = lambda sd: {k: v.detach().cpu().clone() for k, v in sd.items()}
         rng = {"numpy": np.random.get_state(), "torch": torch.get_rng_state(), "torch_cuda": torch.cuda.get_rng_state(self.device),
                "random": random.getstate()}
-        return {"epoch": epoch, "best_fitness": self.best_fitness, "model": cpu(self.model.state_dict()),
-                "ema": {k: (v.float() if v.is_floating_point() else v) for k, v in cpu(self.ema.ema.state_dict()).items()},
-                "updates": self.ema.updates, "optimizer": opt_sd, "train_args": dict(self.train_args),
-                "train_metrics": {**self.metrics, "fitness": self.fitness}, "history": list(self.history), "rng": rng,
-                "stopper": self.stopper.state_dict(), "date": datetime.now().isoformat()}
+        ck = {"epoch": epoch, "best_fitness": self.best_fitness, "model": cpu(self.model.state_dict()),
+              "ema": {k: (v.float() if v.is_floating_point() else v) for k, v in cpu(self.ema.ema.state_dict()).items()},
+              "updates": self.ema.updates, "optimizer": opt_sd, "train_args": dict(self.train_args),
+              "train_metrics": {**self.metrics, "fitness": self.fitness}, "history": list(self.history), "rng": rng,
+              "stopper": self.stopper.state_dict(), "date": datetime.now().isoformat()}
+        if self.htl is not None:  # optional: CKPT_KEYS is what every checkpoint holds
+            ck["htl"] = {"state": self.htl.state_dict(), "items": self._ei.detach().cpu().clone()}
+        return ck
+
+    def _e0_loss(self):
+        """engine/trainer.py:498-512 compute_e0_loss: one pass over the training data in train mode under no_grad (BatchNorm running
+        statistics move), the 12 items summed and divided by the number of batches (a short last batch counts like any other)"""
+        self.model.train()
+        total, n = None, 0
+        with torch.no_grad():
+            # an order of its own, seed - 1 (epoch e draws seed + e); modulo 2^32: the splits seed a RandomState, which takes no -1
+            for batch in self.split.epoch(self.batch, self.data_args, shuffle=True, seed=(self.seed - 1) % (1 << 32)):
+                _, items = self.model(preprocess_batch(batch))
+                items = items.detach().float()
+                total = items.clone() if total is None else total + items
+                n += 1
+        return (total / n).contiguous()
 
     def _save(self, epoch):
         """engine/trainer.py:536-541"""
@@ -299,8 +397,12 @@ class Trainer:
         if self.make_validator is not None and self.validator is None:
             self.validator = self.make_validator(self.ema.ema)
         model, args = self.model, self.data_args
+        if self.htl is not None and self._ei is None:
+            self._ei = self._e0_loss()  # :349-350
         for epoch in range(self.start_epoch, self.epochs):
             self.epoch = epoch
+            if self.htl is not None:
+                self.htl.update(self._ei, epoch)  # :357-358
             model.train()
             if self.close_mosaic > 0 and epoch >= self.epochs - self.close_mosaic and hasattr(args, "mosaic"):
                 args.mosaic = 0.0
@@ -316,6 +418,8 @@ class Trainer:
                 self.sched.iteration(ni, epoch)
                 items = self._micro(batch).detach().float()
                 tloss = items.clone() if tloss is None else (tloss * i + items) / (i + 1)
+                if self.htl is not None:
+                    self._ei = items.contiguous()  # :398 the last micro-batch's items, not the epoch mean, feed the next update
                 if step:
                     self._optimizer_step()
             lr = {f"lr/pg{j}": g["lr"] for j, g in enumerate(self.opt.param_groups)}
@@ -325,11 +429,21 @@ class Trainer:
                 self.metrics = {k: float(v) for k, v in self.validator().items()}
                 self.fitness = self.metrics.pop("fitness", None)
                 self.best_fitness = better_fitness(self.best_fitness, self.fitness)
-            tloss = tloss.cpu()  # the epoch's one read-back of the loss items
+            hw = {}
+            if self.htl is not None:  # the weights and the status word ride on the same read-back
+                tloss = torch.cat((tloss, self.htl.table, self.htl.status.float())).cpu()
+                tloss, w, status = tloss[:-13], tloss[-13:-1], int(tloss[-1])
+                hw = {f"htl/{k}": float(v) for k, v in zip(self.names, w)}
+                if status & 1:
+                    bad = [k for k, v in zip(self.names, w) if not math.isfinite(float(v))]
+                    raise Y3DError(f"Trainer: htl weights not finite in epoch {epoch}: {', '.join(bad) or 'their sum'} "
+                                   f"(weights {[float(v) for v in w]}); the optimizer skipped the steps that saw them")
+            else:
+                tloss = tloss.cpu()  # the epoch's one read-back of the loss items
             names = self.names if len(self.names) == tloss.numel() else [f"loss_{j}" for j in range(tloss.numel())]  # (2D models)
             losses = dict(zip(names, (float(v) for v in tloss)))
-            row = {**{f"train/{k}": v for k, v in losses.items()}, **self.metrics, **lr}
-            self.history.append({"epoch": epoch, **losses, **lr, **self.metrics, "fitness": self.fitness})
+            row = {**{f"train/{k}": v for k, v in losses.items()}, **hw, **self.metrics, **lr}
+            self.history.append({"epoch": epoch, **losses, **hw, **lr, **self.metrics, "fitness": self.fitness})
             self.stop |= self.stopper(epoch + 1, self.fitness) or final
             if self.save_dir is not None:
                 self._save_metrics(epoch, row)
