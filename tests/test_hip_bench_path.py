@@ -1074,12 +1074,12 @@ def test_nonfinite_gradient_norm_skips_the_step_on_the_device():
         e0 = [v.clone() for v in ema.ema.state_dict().values()]
         for poison in (float("nan"), float("inf")):
             before = [p.detach().clone() for p in net.parameters()]
-            state = opts[0]._state["flat"].clone()
+            state = opts[0].state.flat.clone()
             run(net, opts[0], grads[1], poison)   # skipped
             ema.update(net, guard=opts[0].last_norm)
             assert float(opts[0].last_norm[2]) == 0.0
             assert all(torch.equal(a, b.detach()) for a, b in zip(before, net.parameters())), "a skipped step moved the parameters"
-            assert torch.equal(state, opts[0]._state["flat"]), "a skipped step moved the optimizer state"
+            assert torch.equal(state, opts[0].state.flat), "a skipped step moved the optimizer state"
             assert all(torch.equal(a, b) for a, b in zip(e0, ema.ema.state_dict().values())), "a guarded EMA update ran after a skipped step"
         run(net, opts[0], grads[2])
         run(twin, opts[1], grads[2])

@@ -313,7 +313,7 @@ def _one_step(prepare):
     loss.backward()
     opt.step(max_norm=10.0)
     torch.cuda.synchronize()
-    return ({k: v.detach().clone() for k, v in model.state_dict().items()}, opt._state["flat"].clone(), items.clone(), nodes, set(preds), head.distill)
+    return ({k: v.detach().clone() for k, v in model.state_dict().items()}, opt.state.flat.clone(), items.clone(), nodes, set(preds), head.distill)
 
 
 def test_distillation_off_leaves_the_step_as_it_was():
@@ -421,7 +421,7 @@ def test_graphed_train_step_with_teacher_map_replays_the_eager_step():
                 loss, it = step(b)
                 items.append(it.float().cpu().clone())
         torch.cuda.synchronize()
-        res[mode] = (items, {k: v.detach().float().cpu().clone() for k, v in model.state_dict().items()}, opt._state["flat"].cpu().clone())
+        res[mode] = (items, {k: v.detach().float().cpu().clone() for k, v in model.state_dict().items()}, opt.state.flat.cpu().clone())
         del loss
     for a, b in zip(res["eager"][0], res["graph"][0]):
         assert a.numel() == 14 and float(a[6]) > 0 and torch.equal(a, b), (a, b)
@@ -478,7 +478,7 @@ def test_graphed_train_step_with_registered_teacher_replays_the_eager_step():
                     assert len(calls) == n0 + 1, "the teacher runs once per replay, outside the graph"
                     items.append(it.float().cpu().clone())
             torch.cuda.synchronize()
-            res[mode] = (items, {k: v.detach().float().cpu().clone() for k, v in model.state_dict().items()}, opt._state["flat"].cpu().clone())
+            res[mode] = (items, {k: v.detach().float().cpu().clone() for k, v in model.state_dict().items()}, opt.state.flat.cpu().clone())
             del loss
         for a, b in zip(res["eager"][0], res["graph"][0]):
             assert a.numel() == 14 and float(a[6]) > 0 and torch.equal(a, b), (a, b)

@@ -376,7 +376,7 @@ def test_fp8_dgrad_graphed_train_step_matches_eager_steps():
                     loss, it = step(b)
                     items.append(it.float().cpu().clone())
             torch.cuda.synchronize()
-            res[mode] = (items, {k: v.detach().float().cpu().clone() for k, v in model.state_dict().items()}, opt._state["flat"].cpu().clone())
+            res[mode] = (items, {k: v.detach().float().cpu().clone() for k, v in model.state_dict().items()}, opt.state.flat.cpu().clone())
     finally:
         ops.TIMER = None
         y3d.set_fp8_conv(False)

@@ -182,7 +182,7 @@ def test_graphed_step_replays_a_crowded_image():
                 items.append(it.float().cpu().clone())
         torch.cuda.synchronize()
         PL.check_target_overflow(wait=True)
-        res[mode] = (items, {k: v.detach().float().cpu().clone() for k, v in model.state_dict().items()}, opt._state["flat"].cpu().clone())
+        res[mode] = (items, {k: v.detach().float().cpu().clone() for k, v in model.state_dict().items()}, opt.state.flat.cpu().clone())
     for a, b in zip(res["eager"][0], res["graph"][0]):
         assert torch.isfinite(a).all() and torch.equal(a, b), (a, b)
     for k, v in res["eager"][1].items():

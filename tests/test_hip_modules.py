@@ -1277,12 +1277,12 @@ def test_graphed_train_step_matches_eager_steps():
             # statistics and counters, momentum, step counts are where they were
             for k, v in model.state_dict().items():
                 assert torch.equal(v, state0[k]), f"GraphedTrainStep's constructor changed {k}"
-            assert float(opt._state["flat"].abs().max()) == 0 and float(opt._state["norm_clip"].abs().max()) == 0 and opt._steps == 0
+            assert float(opt.state.flat.abs().max()) == 0 and float(opt.state.norm_clip.abs().max()) == 0 and opt._steps == 0
             for b in batches:
                 loss, it = step(b)
                 items.append(it.float().cpu().clone())
         torch.cuda.synchronize()
-        res[mode] = (items, {k: v.detach().float().cpu().clone() for k, v in model.state_dict().items()}, opt._state["flat"].cpu().clone())
+        res[mode] = (items, {k: v.detach().float().cpu().clone() for k, v in model.state_dict().items()}, opt.state.flat.cpu().clone())
     for a, b in zip(res["eager"][0], res["graph"][0]):
         assert torch.equal(a, b), (a, b)
     for k, v in res["eager"][1].items():

@@ -276,18 +276,18 @@ def test_nonfinite_gradients_skip_the_step_on_the_device(kind):
         opt.step(max_norm=5.0)
     torch.cuda.synchronize()
     p0 = [p.detach().clone() for p in ps]
-    flat0, nc0 = opt._state["flat"].clone(), opt._state["norm_clip"].clone()
+    flat0, nc0 = opt.state.flat.clone(), opt.state.norm_clip.clone()
     assert nc0.numel() == 5 + opt.NSCAL and nc0[3:5].tolist() == [2.0, 0.0] and bool(flat0.any())
     if opt.NSCAL:
         assert float(nc0[5 + M.T]) == 2.0 and float(nc0[5 + M.BC1]) > 0
     _set_grads(ps, 50, nan=True)
     opt.step(max_norm=5.0)
     torch.cuda.synchronize()
-    nc1 = opt._state["norm_clip"]
+    nc1 = opt.state.norm_clip
     assert nc1[2:5].tolist() == [0.0, 2.0, 1.0] and opt.last_norm.numel() == 5
     if opt.NSCAL:
         assert_bits(nc1[5:], nc0[5:], f"{kind}: step scalars across a skipped step")
-    assert_bits(opt._state["flat"], flat0, f"{kind}: state across a skipped step")
+    assert_bits(opt.state.flat, flat0, f"{kind}: state across a skipped step")
     for t, (p, q) in enumerate(zip(ps, p0)):
         assert_bits(p.detach(), q, f"{kind}: parameter {t} across a skipped step")
 
@@ -315,7 +315,7 @@ def test_fused_sgd_device_momentum_follows_set_hyper_bit_for_bit():
             grp = opt.param_groups[0 if t < 2 else 1]
             p[t], b[t] = M.sgd_f32(p[t], g[t], b[t], grp["lr"], grp["weight_decay"], grp["momentum"], 1, 0)
         O.same_bits([x.detach().cpu().numpy().reshape(-1) for x in ps], p, f"device momentum step {s} p")
-        O.same_bits([x[0].cpu().numpy() for x in opt._state["bufs"]], b, f"device momentum step {s} buffer")
+        O.same_bits([x[0].cpu().numpy() for x in opt.state.bufs], b, f"device momentum step {s} buffer")
 
 
 @pytest.mark.gpu
@@ -338,7 +338,7 @@ def test_default_optimizers_make_the_parent_commits_library_calls(monkeypatch):
         opt.step(max_norm=10.0)
         torch.cuda.synchronize()
         assert calls == [("mt_sqnorm", 8), ("mt_clip_coef", 5), last], calls
-        assert opt._state["norm_clip"].numel() == 5 and opt.last_norm is opt._state["norm_clip"] and "mom" not in opt._state
+        assert opt.state.norm_clip.numel() == 5 and opt.last_norm is opt.state.norm_clip and opt.table.mom is None
         assert sorted(opt.state_dict()) == ["flat", "norm_clip", "steps"]
     ps = _params(4)
     opt = _make("SGD-table", ps)
@@ -346,6 +346,46 @@ def test_default_optimizers_make_the_parent_commits_library_calls(monkeypatch):
     _set_grads(ps, 70)
     opt.step(max_norm=10.0)
     assert [c[0] for c in calls] == ["mt_sqnorm", "mt_clip_coef", "mt_sgd_tab"]
+    # the other kinds, ModelEMA and GradAccumulator: the sequence and the argument counts they had before the launch tables moved to
+    # mt.py, written out.  A step over the same gradient tensors makes the same calls and uploads no gradient pointers; one replaced
+    # gradient tensor costs exactly one upload
+    from yolov10_3d_amd import optim as P
+    adam = [("mt_sqnorm", 8), ("mt_clip_coef", 5), ("mt_step_scalars", 6), ("mt_update", 19)]
+    for kind in CLASSES[1:]:
+        want = [("mt_sqnorm", 8), ("mt_clip_coef", 5), ("mt_update", 19)] if kind == "RMSprop" else adam
+        ps = _params(4)
+        opt = _make(kind, ps)
+        _set_grads(ps, 70)
+        for s in range(3):
+            if s == 2:
+                ps[1].grad = ps[1].grad.clone()
+            del calls[:]
+            opt.step(max_norm=10.0)
+            assert calls == want, (kind, s, calls)
+            col = opt.table.col["grads"]
+            if s == 0:
+                col0, key0 = col, col.key
+            assert col is col0 and col.uploads == (1 if s < 2 else 2) and (col.key is key0) == (s < 2), (kind, s, col.uploads)
+    torch.cuda.synchronize()
+    net = torch.nn.Sequential(torch.nn.Linear(5, 3), torch.nn.BatchNorm1d(3)).to(DEV)
+    ema = P.ModelEMA(net)
+    for s in range(2):
+        del calls[:]
+        ema.update(net)
+        assert calls == [("mt_ema", 12)], calls
+        assert [c.uploads for c in ema._tab.col.values()] == [1, 1]
+    ps = _params(4, idle=False)
+    acc = P.GradAccumulator(ps)
+    _set_grads(ps, 71)
+    grads = [p.grad for p in ps]
+    for s in range(3):
+        for p, g in zip(ps, grads):
+            p.grad = g.clone() if (s == 2 and p is ps[1]) else g
+        del calls[:]
+        acc.add()
+        assert calls == [("mt_grad_acc", 8)], calls
+        assert [tb.col["grads"].uploads for tb in acc._tabs.values()] == [1 if s < 2 else 2]
+    torch.cuda.synchronize()
 
 
 @pytest.mark.gpu
@@ -395,13 +435,13 @@ def test_state_moves_through_the_torch_format_bit_for_bit(kind):
         tag = f"{kind} resumed {'after' if i else 'before'} the first step"
         for t, (q, p) in enumerate(zip(qs, ps)):
             assert_bits(q.detach(), p.detach(), f"{tag}: parameter {t}")
-        assert_bits(o2._state["flat"], opt._state["flat"], f"{tag}: flat state")
+        assert_bits(o2.state.flat, opt.state.flat, f"{tag}: flat state")
         if has_step:
-            assert float(o2._state["norm_clip"][3]) == 3.0
+            assert float(o2.state.norm_clip[3]) == 3.0
             if opt.NSCAL:
                 # torch's dict carries mu_product for NAdam alone: for the other kinds the entries derived from it are not state
                 keep = [i for i in range(M.NSCAL) if kind == "NAdam" or i not in (M.MU_PROD, M.MU_PROD_NEXT, M.NADAM_G, M.NADAM_M)]
-                assert_bits(o2._state["norm_clip"][5:][keep], opt._state["norm_clip"][5:][keep], f"{tag}: step scalars")
+                assert_bits(o2.state.norm_clip[5:][keep], opt.state.norm_clip[5:][keep], f"{tag}: step scalars")
     # refusals reach the caller through load_state_dict, naming the parameter
     bad = opt.state_dict(torch_format=True)
     bad["state"][3][keys[0]] = torch.zeros(7, device=DEV)
@@ -480,7 +520,7 @@ def _run(name, mode, batches, hyper=None, device_momentum=False):
             opt.zero_grad()
             del loss
     torch.cuda.synchronize()
-    return ({k: v.detach().clone() for k, v in model.state_dict().items()}, opt._state["flat"].clone(), opt._state["norm_clip"].clone())
+    return ({k: v.detach().clone() for k, v in model.state_dict().items()}, opt.state.flat.clone(), opt.state.norm_clip.clone())
 
 
 def _same_run(a, b, what):

@@ -135,7 +135,7 @@ def new_model(seed=3):
 
 def snapshot(model, opt):
     torch.cuda.synchronize()
-    return {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}, opt._state["flat"].cpu().clone()
+    return {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}, opt.state.flat.cpu().clone()
 
 
 def same_state(a, b, what):
@@ -167,7 +167,7 @@ def arena_route(batches):
         assert acc.count == 2
         acc.bind()
         opt.step(max_norm=10.0)
-        out["gkeys"].append(list(opt._state["gkey"]))
+        out["gkeys"].append(list(opt.table.col["grads"].key))
         acc.reset()
         out["arena_zero"].append(float(acc.arena.abs().max()) == 0 and acc.count == 0 and all(p.grad is None for p in model.parameters()))
         out["after"].append(snapshot(model, opt))
@@ -292,7 +292,7 @@ def run_state(t):
     torch.cuda.synchronize()
     return {"model": {k: v.detach().cpu().clone() for k, v in t.model.state_dict().items()},
             "ema": {k: v.detach().cpu().clone() for k, v in t.ema.ema.state_dict().items()},
-            "opt": t.opt._state["flat"].cpu().clone(), "counters": t.opt._state["norm_clip"].cpu().clone(), "updates": t.ema.updates,
+            "opt": t.opt.state.flat.cpu().clone(), "counters": t.opt.state.norm_clip.cpu().clone(), "updates": t.ema.updates,
             "best_fitness": t.best_fitness, "history": [dict(h) for h in t.history]}
 
 
@@ -360,7 +360,7 @@ def test_fit_equals_the_loop_written_out(tree, straight):
         assert torch.equal(v.cpu(), got["model"][k]), f"model {k}"
     for k, v in ema.ema.state_dict().items():
         assert torch.equal(v.cpu(), got["ema"][k]), f"EMA {k}"
-    assert torch.equal(opt._state["flat"].cpu(), got["opt"]) and ema.updates == got["updates"] == 3
+    assert torch.equal(opt.state.flat.cpu(), got["opt"]) and ema.updates == got["updates"] == 3
     for h, g in zip(history, got["history"]):
         assert all(g[k] == v and np.isfinite(v) for k, v in h.items()), (h, g)
     assert [h["epoch"] for h in got["history"]] == [0, 1] and all("fitness" in h and "lr/pg0" in h and "metrics/3D" in h for h in got["history"])

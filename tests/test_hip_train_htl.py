@@ -70,7 +70,7 @@ def run_state(t):
     torch.cuda.synchronize()
     return {"model": {k: v.detach().cpu().clone() for k, v in t.model.state_dict().items()},
             "ema": {k: v.detach().cpu().clone() for k, v in t.ema.ema.state_dict().items()},
-            "opt": t.opt._state["flat"].cpu().clone(), "counters": t.opt._state["norm_clip"].cpu().clone(), "updates": t.ema.updates,
+            "opt": t.opt.state.flat.cpu().clone(), "counters": t.opt.state.norm_clip.cpu().clone(), "updates": t.ema.updates,
             "history": [dict(h) for h in t.history], "htl": t.htl.state_dict() if t.htl is not None else None}
 
 
@@ -155,7 +155,7 @@ def test_fit_equals_the_loop_written_out(tree, straight):
         assert torch.equal(v.cpu(), got["model"][k]), f"model {k}"
     for k, v in ema.ema.state_dict().items():
         assert torch.equal(v.cpu(), got["ema"][k]), f"EMA {k}"
-    assert torch.equal(opt._state["flat"].cpu(), got["opt"]) and ema.updates == got["updates"] == EPOCHS
+    assert torch.equal(opt.state.flat.cpu(), got["opt"]) and ema.updates == got["updates"] == EPOCHS
     for e, (h, g) in enumerate(zip(history, got["history"])):
         assert all(g[k] == v and np.isfinite(v) for k, v in h.items()), (e, h, g)
     sd = hw.state_dict()

@@ -141,3 +141,54 @@ def test_accumulator_tables():
     ps[0].grad = torch.ones(1)
     with pytest.raises(Y3DError, match="HIP device"):  # no host fallback
         acc.add()
+
+
+def test_one_chunk_map_and_one_chunk_size():
+    """mt.chunk_map against the double loop written out; every module's CHUNK is mt's"""
+    from yolov10_3d_amd import ddp, mt, ops
+    assert optim.chunk_map is mt.chunk_map
+    assert ddp.FlatGradReducer.CHUNK == ops._PackRegistry.CHUNK == optim.CHUNK == mt.CHUNK == 16384
+    for chunk in (256, 16384):
+        for sizes in ([0], [1], [chunk - 1, chunk, chunk + 1], [3 * chunk + 5, 0, 2]):
+            ct, co = [], []
+            for t, n in enumerate(sizes):
+                for c in range((n + chunk - 1) // chunk):
+                    ct.append(t)
+                    co.append(c)
+            assert mt.chunk_map(sizes, chunk) == (ct, co), (sizes, chunk)
+        assert mt.chunk_map([0], chunk) == ([], []) and mt.chunk_map([3 * chunk + 5, 0, 2], chunk) == ([0, 0, 0, 0, 2], [0, 1, 2, 3, 0])
+    assert mt.chunk_map([16385, 1]) == ([0, 0, 1], [0, 1, 0])  # the default chunk
+
+
+def test_a_checkpoints_optimizer_entry_loads_and_writes_back_without_a_device():
+    """the `optimizer` entry of a trainer checkpoint, put together by hand as the trainer writes it (torch's layout + "native": the host
+    step count and the counters array on the CPU), into a fresh FusedAdam over CPU parameters and out again: nothing is built before the
+    first step, so no device is needed"""
+    g = torch.Generator().manual_seed(11)
+    shapes = [(3, 4), (5,), (2, 3)]
+    ps = [torch.nn.Parameter(torch.randn(s, generator=g)) for s in shapes]
+    groups = [{"lr": 0.004, "weight_decay": 5e-4, "betas": (0.85, 0.99), "eps": 1e-7, "initial_lr": 0.01, "params": [0, 1]},
+              {"lr": 0.002, "weight_decay": 0.0, "betas": (0.85, 0.99), "eps": 1e-7, "initial_lr": 0.005, "params": [2]}]
+    state = {i: {"step": torch.tensor(7.0), "exp_avg": torch.randn(s, generator=g), "exp_avg_sq": torch.rand(s, generator=g)}
+             for i, s in enumerate(shapes)}
+    norm_clip = torch.arange(21, dtype=torch.float32) * 0.5  # [norm, coefficient, finite, applied, skipped] + 16 step scalars
+    norm_clip[3], norm_clip[4] = 7.0, 2.0
+    sd = {"state": state, "param_groups": groups, "native": {"steps": 9, "norm_clip": norm_clip.clone()}}
+    opt = optim.FusedAdam([{"params": ps[:2]}, {"params": ps[2:]}], lr=0.1)
+    opt.load_state_dict(sd)
+    assert opt.state is None and opt.table is None
+    out = opt.state_dict(torch_format=True, native=True)
+    assert set(out) == {"state", "param_groups", "native"} and sorted(out["state"]) == [0, 1, 2]
+    for i, e in state.items():
+        assert sorted(out["state"][i]) == ["exp_avg", "exp_avg_sq", "step"]
+        assert all(torch.equal(out["state"][i][k], v) and out["state"][i][k].dtype == v.dtype for k, v in e.items())
+    assert out["param_groups"] == groups
+    assert out["native"]["steps"] == 9 and torch.equal(out["native"]["norm_clip"], norm_clip)
+    assert out["native"]["norm_clip"].device.type == "cpu"
+    assert set(opt.state_dict(torch_format=True)) == {"state", "param_groups"}  # the entry is opt-in
+    # without the entry, torch's layout alone: the same state, the step count from torch's `step`, no counters yet
+    plain = optim.FusedAdam([{"params": ps[:2]}, {"params": ps[2:]}], lr=0.1)
+    plain.load_state_dict({"state": state, "param_groups": groups})
+    out = plain.state_dict(torch_format=True, native=True)
+    assert all(torch.equal(out["state"][i][k], v) for i, e in state.items() for k, v in e.items())
+    assert out["native"] == {"steps": 0, "norm_clip": None}

@@ -28,7 +28,7 @@ state = {k: v.clone() for k, v in model.state_dict().items()}
 print('eager reducer step ...', flush=True)
 loss, _ = model(b[0]); loss.backward(); red.finish(); opt.step(max_norm=10.0); opt.zero_grad(); torch.cuda.synchronize()
 del loss, _  # an autograd graph kept alive keeps its AccumulateGrad nodes (made on the NULL stream) alive: the capture would have to touch that stream
-model.load_state_dict(state); opt._state['flat'].zero_()
+model.load_state_dict(state); opt.state.flat.zero_()
 print('capture ...', flush=True)
 try:
     step = GraphedTrainStep(model, opt, b[0], reducer=None if os.environ.get('Y3D_PROBE_NORED') else red)
@@ -37,7 +37,7 @@ try:
         step(x)
     torch.cuda.synchronize()
     g_state = {k: v.clone() for k, v in model.state_dict().items()}
-    model.load_state_dict(state); opt._state["flat"].zero_(); opt.zero_grad()
+    model.load_state_dict(state); opt.state.flat.zero_(); opt.zero_grad()
     for x in b:
         loss, _ = model(x); loss.backward(); red.finish(); opt.step(max_norm=10.0); opt.zero_grad()
     torch.cuda.synchronize()

@@ -30,12 +30,12 @@ maps = kept["maps"]
 n_used = step.counts[0][0]
 
 def snap():
-    return [t.detach().clone() for t in tens], opt._state["flat"].clone(), opt._state["norm_clip"].clone()
+    return [t.detach().clone() for t in tens], opt.state.flat.clone(), opt.state.norm_clip.clone()
 def restore(s):
     with torch.no_grad():
         for t, v in zip(tens, s[0]):
             t.copy_(v)
-        opt._state["flat"].copy_(s[1]); opt._state["norm_clip"].copy_(s[2])
+        opt.state.flat.copy_(s[1]); opt.state.norm_clip.copy_(s[2])
     ops.bump_weight_epoch()
 s0 = snap()
 outs = []

@@ -54,7 +54,7 @@ def kernel(a):
         acc.add()  # builds the tables and uploads the gradient pointers; the timed loop repeats its launch without the host work around it
         tb = acc._tabs[next(iter(acc._tabs))]
         L, st = y3d.lib(), torch.cuda.current_stream().cuda_stream
-        args = (tb["aptr"].data_ptr(), tb["gptr"].data_ptr(), tb["sizes"].data_ptr(), tb["ct"].data_ptr(), tb["co"].data_ptr(), tb["n"], optim.CHUNK, st)
+        args = (tb.ptr["arena"].data_ptr(), tb.col["grads"].dev.data_ptr(), tb.sizes.data_ptr(), *tb.chunks, st)
 
         def add():
             L.mt_grad_acc(*args)
@@ -73,7 +73,7 @@ def kernel(a):
             torch.cuda.synchronize()
             spans.append(e0.elapsed_time(e1) / a.launches)
         ms = median(spans)
-        print(f"kernel {name}: {len(ps)} tensors, {n / 1e6:.2f} M elements, {tb['n']} workgroups; "
+        print(f"kernel {name}: {len(ps)} tensors, {n / 1e6:.2f} M elements, {tb.nchunks} workgroups; "
               f"{1e3 * ms:.1f} us per launch (median of {a.repeats} x {a.launches} back-to-back launches, min {1e3 * min(spans):.1f}, "
               f"max {1e3 * max(spans):.1f}); {12 * n / (ms * 1e-3) / 1e12:.2f} TB/s at 12 B per element", flush=True)
         del model, acc, grads

@@ -7,14 +7,28 @@
 
 namespace {
 
+// the chunk of workgroup blockIdx.x: tensor t and its n elements from element off on (tables: mt.chunk_map)
+struct Chunk {
+  int t;
+  long off, n;
+};
+
+__device__ __forceinline__ Chunk mt_chunk(const long* __restrict__ sizes, const int* __restrict__ ctensor, const int* __restrict__ coff, int chunk) {
+  Chunk ck;
+  ck.t = ctensor[blockIdx.x];
+  ck.off = (long)coff[blockIdx.x] * chunk;
+  ck.n = sizes[ck.t] - ck.off;
+  if (ck.n > chunk) ck.n = chunk;
+  return ck;
+}
+
 __global__ __launch_bounds__(256) void mt_sqnorm_kernel(const long* __restrict__ gptr, const long* __restrict__ sizes, const int* __restrict__ ctensor,
                                                         const int* __restrict__ coff, int chunk, float* __restrict__ partials) {
   __shared__ float sh[256];
-  const int t = ctensor[blockIdx.x];
-  const long off = (long)coff[blockIdx.x] * chunk;
+  const Chunk ck = mt_chunk(sizes, ctensor, coff, chunk);
+  const int t = ck.t;
+  const long off = ck.off, n = ck.n;
   const float* g = (const float*)gptr[t] + off;
-  long n = sizes[t] - off;
-  if (n > chunk) n = chunk;
   float s = 0.f;
   if ((((uintptr_t)g) & 15) == 0) {
     long n4 = n >> 2;
@@ -60,39 +74,40 @@ __global__ __launch_bounds__(256) void mt_clip_kernel(const float* __restrict__ 
   }
 }
 
+// one element of torch.optim.SGD (dampening 0), for mt_sgd_kernel and mt_sgd_tab_kernel
+__device__ __forceinline__ void upd_sgd(float& p, const float g, float& b, float c, float l, float w, float momentum, int nesterov, int first) {
+  const float pv = p;
+  float gv = g * c;
+  if (w != 0.f) gv += w * pv;
+  const float bv = first ? gv : momentum * b + gv;
+  b = bv;
+  const float step = nesterov ? gv + momentum * bv : bv;
+  p = pv - l * step;
+}
+
 __global__ __launch_bounds__(256) void mt_sgd_kernel(const long* __restrict__ pptr, const long* __restrict__ gptr, const long* __restrict__ bptr,
                                                      const long* __restrict__ sizes, const float* __restrict__ lr, const float* __restrict__ wd,
                                                      const int* __restrict__ ctensor, const int* __restrict__ coff, int chunk, float momentum,
                                                      int nesterov, int first, const float* __restrict__ clip) {
-  const int t = ctensor[blockIdx.x];
-  const long off = (long)coff[blockIdx.x] * chunk;
+  const Chunk ck = mt_chunk(sizes, ctensor, coff, chunk);
+  const int t = ck.t;
+  const long off = ck.off, n = ck.n;
   float* p = (float*)pptr[t] + off;
   const float* g = (const float*)gptr[t] + off;
   float* b = (float*)bptr[t] + off;
-  long n = sizes[t] - off;
-  if (n > chunk) n = chunk;
   if (clip && clip[2] == 0.f) return;  // non-finite gradient norm: this step is skipped on every rank (the norm is that of the reduced buffer)
   const float c = clip ? clip[1] : 1.f, l = lr[t], w = wd[t];
-  for (long i = threadIdx.x; i < n; i += 256) {
-    float pv = p[i];
-    float gv = g[i] * c;
-    if (w != 0.f) gv += w * pv;
-    float bv = first ? gv : momentum * b[i] + gv;
-    b[i] = bv;
-    float step = nesterov ? gv + momentum * bv : bv;
-    p[i] = pv - l * step;
-  }
+  for (long i = threadIdx.x; i < n; i += 256) upd_sgd(p[i], g[i], b[i], c, l, w, momentum, nesterov, first);
 }
 
 // dst_t[i] = src_t[i] * scale for every tensor t of the table: gathers the step's gradient tensors into the flat all-reduce buffer
 __global__ __launch_bounds__(256) void mt_copy_kernel(const long* __restrict__ sptr, const long* __restrict__ dptr, const long* __restrict__ sizes,
                                                       const int* __restrict__ ctensor, const int* __restrict__ coff, int chunk, float scale) {
-  const int t = ctensor[blockIdx.x];
-  const long off = (long)coff[blockIdx.x] * chunk;
+  const Chunk ck = mt_chunk(sizes, ctensor, coff, chunk);
+  const int t = ck.t;
+  const long off = ck.off, n = ck.n;
   const float* s = (const float*)sptr[t] + off;
   float* d = (float*)dptr[t] + off;
-  long n = sizes[t] - off;
-  if (n > chunk) n = chunk;
   if (((((uintptr_t)s) | ((uintptr_t)d)) & 15) == 0) {
     const long n4 = n >> 2;
     for (long i = threadIdx.x; i < n4; i += 256) {
@@ -112,14 +127,13 @@ __global__ __launch_bounds__(256) void mt_adamw_kernel(const long* __restrict__ 
                                                        const float* __restrict__ wd, const int* __restrict__ ctensor, const int* __restrict__ coff,
                                                        int chunk, float beta1, float beta2, float eps, float bc1, float bc2s,
                                                        const float* __restrict__ clip) {
-  const int t = ctensor[blockIdx.x];
-  const long off = (long)coff[blockIdx.x] * chunk;
+  const Chunk ck = mt_chunk(sizes, ctensor, coff, chunk);
+  const int t = ck.t;
+  const long off = ck.off, n = ck.n;
   float* p = (float*)pptr[t] + off;
   const float* g = (const float*)gptr[t] + off;
   float* m = (float*)mptr[t] + off;
   float* v = (float*)vptr[t] + off;
-  long n = sizes[t] - off;
-  if (n > chunk) n = chunk;
   if (clip) {
     if (clip[2] == 0.f) return;  // skipped step (non-finite gradient norm): state and step count stay
     // the step count of the bias corrections is the number of APPLIED steps, which only the device knows
@@ -236,14 +250,13 @@ __global__ __launch_bounds__(256) void mt_update_kernel(const long* __restrict__
                                                         const float* __restrict__ wd, const float* __restrict__ mom, const int* __restrict__ ctensor,
                                                         const int* __restrict__ coff, int chunk, float beta1, float beta2, float eps,
                                                         const float* __restrict__ scal, const float* __restrict__ clip) {
-  const int t = ctensor[blockIdx.x];
-  const long off = (long)coff[blockIdx.x] * chunk;
+  const Chunk ck = mt_chunk(sizes, ctensor, coff, chunk);
+  const int t = ck.t;
+  const long off = ck.off, n = ck.n;
   float* p = (float*)pptr[t] + off;
   const float* g = (const float*)gptr[t] + off;
   float* a = (float*)aptr[t] + off;
   float* b = (float*)bptr[t] + off;
-  long n = sizes[t] - off;
-  if (n > chunk) n = chunk;
   if (clip && clip[2] == 0.f) return;  // skipped step (non-finite gradient norm): parameters and state stay
   UpdCoef k;
   k.c = clip ? clip[1] : 1.f;
@@ -294,27 +307,16 @@ __global__ __launch_bounds__(256) void mt_update_kernel(const long* __restrict__
 
 // mt_sgd_kernel with the momentum read from a per-tensor device table next to lr / wd: a captured step follows a momentum schedule
 // (warm-up, engine/trainer.py:392-393) through in-place writes of the table
-__device__ __forceinline__ void upd_sgd(float& p, const float g, float& b, float c, float l, float w, float momentum, int nesterov, int first) {
-  const float pv = p;
-  float gv = g * c;
-  if (w != 0.f) gv += w * pv;
-  const float bv = first ? gv : momentum * b + gv;
-  b = bv;
-  const float step = nesterov ? gv + momentum * bv : bv;
-  p = pv - l * step;
-}
-
 __global__ __launch_bounds__(256) void mt_sgd_tab_kernel(const long* __restrict__ pptr, const long* __restrict__ gptr, const long* __restrict__ bptr,
                                                          const long* __restrict__ sizes, const float* __restrict__ lr, const float* __restrict__ wd,
                                                          const float* __restrict__ mom, const int* __restrict__ ctensor, const int* __restrict__ coff,
                                                          int chunk, int nesterov, int first, const float* __restrict__ clip) {
-  const int t = ctensor[blockIdx.x];
-  const long off = (long)coff[blockIdx.x] * chunk;
+  const Chunk ck = mt_chunk(sizes, ctensor, coff, chunk);
+  const int t = ck.t;
+  const long off = ck.off, n = ck.n;
   float* p = (float*)pptr[t] + off;
   const float* g = (const float*)gptr[t] + off;
   float* b = (float*)bptr[t] + off;
-  long n = sizes[t] - off;
-  if (n > chunk) n = chunk;
   if (clip && clip[2] == 0.f) return;
   const float c = clip ? clip[1] : 1.f, l = lr[t], w = wd[t], m = mom[t];
   if (((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)b)) & 15) == 0) {
@@ -341,12 +343,11 @@ __global__ __launch_bounds__(256) void mt_ema_kernel(const long* __restrict__ ep
                                                      const int* __restrict__ reps, const int* __restrict__ ctensor, const int* __restrict__ coff,
                                                      int chunk, float d, float omd, const float* __restrict__ guard) {
   if (guard && guard[2] == 0.f) return;  // the optimizer step this update follows was skipped: the model did not move
-  const int t = ctensor[blockIdx.x];
-  const long off = (long)coff[blockIdx.x] * chunk;
+  const Chunk ck = mt_chunk(sizes, ctensor, coff, chunk);
+  const int t = ck.t;
+  const long off = ck.off, n = ck.n;
   float* e = (float*)eptr[t] + off;
   const float* m = (const float*)mptr[t] + off;
-  long n = sizes[t] - off;
-  if (n > chunk) n = chunk;
   const int r = reps[t];
   for (long i = threadIdx.x; i < n; i += 256) {
     float ev = e[i];
@@ -361,12 +362,11 @@ __global__ __launch_bounds__(256) void mt_ema_kernel(const long* __restrict__ ep
 // engine/trainer.py:384-386, 411-413).  Tables and chunking of mt_copy_kernel; 8 B read + 4 B written per element.
 __global__ __launch_bounds__(256) void mt_grad_acc_kernel(const long* __restrict__ aptr, const long* __restrict__ gptr, const long* __restrict__ sizes,
                                                           const int* __restrict__ ctensor, const int* __restrict__ coff, int chunk) {
-  const int t = ctensor[blockIdx.x];
-  const long off = (long)coff[blockIdx.x] * chunk;
+  const Chunk ck = mt_chunk(sizes, ctensor, coff, chunk);
+  const int t = ck.t;
+  const long off = ck.off, n = ck.n;
   float* a = (float*)aptr[t] + off;
   const float* g = (const float*)gptr[t] + off;
-  long n = sizes[t] - off;
-  if (n > chunk) n = chunk;
   if (((((uintptr_t)a) | ((uintptr_t)g)) & 15) == 0) {
     const long n4 = n >> 2;
     for (long i = threadIdx.x; i < n4; i += 256) {

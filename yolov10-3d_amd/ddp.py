@@ -20,6 +20,8 @@ import os
 import torch
 import torch.distributed as dist
 
+from . import mt
+
 # keys of the collated batch dict (reference data/datasets/kitti.py:421-442, collate_fn :579-599)
 PER_BOX_KEYS = ("cls", "bboxes", "center_2d", "size_2d", "center_3d", "size_3d", "depth", "heading_bin", "heading_res")
 # per-image entries: stacked tensors (`depth_map` is a (B, 1) placeholder unless depth maps are loaded, kitti.py:409-420) and the
@@ -110,7 +112,7 @@ class FlatGradReducer:
     its slot ZEROED before the collective, whatever an earlier step left there (another rank may own a gradient for it) - and after
     `finish()` EVERY rank holds the reduced sum in `p.grad` for every parameter that has a gradient on some rank."""
 
-    CHUNK = 16384
+    CHUNK = mt.CHUNK
     MASK_EVERY = 256
 
     def __init__(self, params, bucket_mb: float = 32.0, overlap: bool | None = None, timing: bool = False):
@@ -219,21 +221,12 @@ class FlatGradReducer:
         key = tuple(idx)
         tb = self._tabs.get(key)
         if tb is None:
-            sizes = [self.sizes[i] for i in idx]
-            ct, co = [], []
-            for t, n in enumerate(sizes):
-                for c in range((n + self.CHUNK - 1) // self.CHUNK):
-                    ct.append(t)
-                    co.append(c)
-            from .optim import PtrUploader
-            tb = {"sizes": torch.tensor(sizes, dtype=torch.int64, device=dev), "ct": torch.tensor(ct, dtype=torch.int32, device=dev),
-                  "co": torch.tensor(co, dtype=torch.int32, device=dev), "n": len(ct),
-                  "dst": torch.tensor([self.views[i].data_ptr() for i in idx], dtype=torch.int64, device=dev),
-                  "up": PtrUploader(len(idx), dev)}
-            self._tabs[key] = tb
-        src = tb["up"].upload([g.data_ptr() for g in grads])  # non-blocking: the host must not wait for the backward to drain
-        lib().mt_copy(src.data_ptr(), tb["dst"].data_ptr(), tb["sizes"].data_ptr(), tb["ct"].data_ptr(), tb["co"].data_ptr(), tb["n"], self.CHUNK,
-                      1.0, ops.stream())
+            tb = self._tabs[key] = mt.Table([self.sizes[i] for i in idx], dev, dst=[self.views[i].data_ptr() for i in idx])
+            tb.column("src", now=True)
+        # pinned and non-blocking: the host must not wait for the backward to drain; every gather uploads (force), as it is launched on the
+        # side stream or recorded into a hipGraph
+        src = tb.col["src"].refresh([g.data_ptr() for g in grads], force=True)
+        lib().mt_copy(src.data_ptr(), tb.ptr["dst"].data_ptr(), tb.sizes.data_ptr(), *tb.chunks, 1.0, ops.stream())
 
     def _launch(self, b):
         a, e = self.buckets[b]
@@ -251,10 +244,9 @@ class FlatGradReducer:
                 raise RuntimeError("FlatGradReducer: a gradient was accumulated into its already all-reduced slot - clear gradients "
                                    "with zero_grad(set_to_none=True) after every finish(), and run the non-final micro-steps of "
                                    "gradient accumulation under reducer.no_sync()")
-            if g.dtype != torch.float32 or not g.is_contiguous():
-                g = g.float().contiguous()
             idx.append(i)
             grads.append(g)
+        grads = mt.Table.fp32_contiguous(grads)
         lo = self.offs[a]
         hi = self.offs[e - 1] + self.sizes[e - 1]
         multi = dist.is_initialized() and (dist.get_world_size() > 1 or self.always_collective)

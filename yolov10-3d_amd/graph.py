@@ -72,7 +72,8 @@ class GraphedTrainStep:
     For the small models the step is bound by the host (N-3D: ~900 launches enqueued in 17 ms for ~12 ms of kernels); replayed from a
     graph the host cost is one call.  What makes the step capturable: the library never synchronises or allocates; target padding
     keeps its count on the device (loss.pad_targets); the optimizer's skip of non-finite steps and AdamW's step count live on the
-    device (csrc/optim.hip); pointer tables travel through pinned buffers (optim.PtrUploader).
+    device (csrc/optim.hip); pointer tables travel through pinned buffers (mt.PtrUploader).  What the graph keeps alive of the optimizer,
+    what set_hyper() reaches and what an eager step rebuilds afterwards: DESIGN.md §3.29.
 
     N > 1: pass the `ddp.FlatGradReducer` - its bucket gathers and RCCL all-reduces are recorded into the graph (on the capturing stream:
     no side stream is forked inside a capture), every rank captures and replays the same sequence of collectives.
@@ -98,7 +99,6 @@ class GraphedTrainStep:
         from . import loss as _loss
         from .ddp import PER_BOX_KEYS
         from .modules import Conv
-        from .optim import PtrUploader
         self.model, self.opt, self.max_norm, self.reducer = model, opt, max_norm, reducer
         self.box_keys = tuple(k for k in (("batch_idx",) + PER_BOX_KEYS) if k in batch)
         B = batch["img"].shape[0]
@@ -141,9 +141,7 @@ class GraphedTrainStep:
                     tensors.append(t)
             snap = [t.detach().clone() for t in tensors]
         nbt = [m._nbt_pending for m in self.convs]
-        had_state = opt._state is not None
-        opt_snap = (opt._state["flat"].clone(), opt._state["norm_clip"].clone()) if had_state else None
-        steps0 = opt._steps
+        opt_snap = opt.snapshot()
         if reducer is not None:
             # the reducer's gather tables (source pointers through rotating pinned buffers): the warm-up below builds fresh ones, the capture
             # bakes their addresses in, and they are then set aside for the graph alone (eager steps build their own) - as the optimizer's
@@ -158,13 +156,7 @@ class GraphedTrainStep:
             with torch.no_grad():
                 for t, v in zip(tensors, snap):
                     t.copy_(v)
-                if had_state:
-                    opt._state["flat"].copy_(opt_snap[0])
-                    opt._state["norm_clip"].copy_(opt_snap[1])
-                else:
-                    opt._state["flat"].zero_()
-                    opt._state["norm_clip"].zero_()
-        opt._steps = steps0
+                opt.restore(opt_snap)
         for m, n in zip(self.convs, nbt):
             m._nbt_pending = n
         cur.wait_stream(side)
@@ -173,20 +165,17 @@ class GraphedTrainStep:
         # the gradient pointer table of the captured optimizer launches must not live in the optimizer's ROTATING pinned buffers: a few
         # eager opt.step() calls later (a fallback for an over-capacity batch) would overwrite them and the next replay would read those
         # pointers (round-3 advisor finding).  The graph gets an uploader of its own; the optimizer builds a new one when it next needs it.
-        st = opt._state
-        st["gup"], st["gkey"] = PtrUploader(len(st["active"]), st["dev"], depth=1), None
+        opt.begin_capture()
         _loss._CAPTURED_COUNTS.clear()
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
             self.loss, self.items = self._body()
         if reducer is not None:
             self._red_tabs, reducer._tabs = reducer._tabs, {}  # kept alive for the replays; eager steps build new ones
-        self._gup = st["gup"]  # kept alive: the graph's memcpy node reads its pinned buffer at every replay
-        st["gup"], st["gkey"] = None, None
-        # every device table the captured optimizer launches read (sizes, chunk maps, lr / wd, parameter and state pointers): the optimizer
-        # REPLACES them when its active set or a parameter address changes (an eager step in between); the graph keeps reading these
-        self._opt_tables = dict(st)
-        opt._steps = steps0  # the captured Python counted a step that has not run
+        # every device table the captured optimizer launches read (sizes, chunk maps, lr / wd, parameter and state pointers) and the
+        # uploader whose pinned buffer the graph's memcpy node reads at every replay: the optimizer REPLACES them when its active set or a
+        # parameter address changes (an eager step in between); the graph keeps reading these
+        self._opt_tables = opt.end_capture()
         # the device words [min(count, cap), true largest per-image count] of the captured pad_targets launches: graph-private static
         # memory, rewritten by every replay; read back after each one so that an image with more boxes than the kernels take is
         # reported as in the eager loop, not trained on silently truncated targets (round-3 advisor finding)

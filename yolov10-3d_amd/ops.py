@@ -13,6 +13,7 @@ from collections import namedtuple
 
 import torch
 
+from . import mt
 from ._lib import BF16, F32, Y3DError, lib
 
 _COMPUTE_DTYPE = torch.bfloat16
@@ -317,7 +318,7 @@ class _PackRegistry(_WeightRegistry):
 
     DW = 2
 
-    CHUNK = 16384
+    CHUNK = mt.CHUNK
 
     def __init__(self, mode):
         super().__init__()
@@ -341,14 +342,12 @@ class _PackRegistry(_WeightRegistry):
         dev = ents[0]["dst"].device
         key = tuple(id(e) for e in ents)
         if self.tables is None or self.tables[0] != (key, dt):
-            desc, ct, co = [], [], []
-            for t, e in enumerate(ents):
+            desc, sizes = [], []
+            for e in ents:
                 a, b, c, taps, kpad, _ = e["geo"]
-                n = a * kpad if e["mode"] == 0 else a * c * kpad
+                sizes.append(a * kpad if e["mode"] == 0 else a * c * kpad)
                 desc += [e["src"], e["dst"].data_ptr(), a, b, c, taps, kpad, e["mode"]]
-                for j in range((n + self.CHUNK - 1) // self.CHUNK):
-                    ct.append(t)
-                    co.append(j)
+            ct, co = mt.chunk_map(sizes, self.CHUNK)
             self.tables = ((key, dt), torch.tensor(desc, dtype=torch.int64, device=dev), torch.tensor(ct, dtype=torch.int32, device=dev),
                            torch.tensor(co, dtype=torch.int32, device=dev), len(ct))
         _, desc, ct, co, n = self.tables

@@ -20,35 +20,13 @@ import math
 import numpy as np
 import torch
 
-from . import ops
+from . import mt, ops
 from ._lib import Y3DError, lib
+from .mt import CHUNK, PtrUploader, chunk_map  # noqa: F401  (their home is mt.py; tests and tools import them from here)
 
-CHUNK = 16384
 # indices into the step-scalar array (include/y3d.h, y3d_mt_step_scalars) and y3d_mt_update's kinds
 S_BC1, S_BC2, S_BC1_SQRT, S_BC2_SQRT, S_MU, S_MU_NEXT, S_MU_PROD, S_MU_PROD_NEXT, S_RHO, S_RECT_ON, S_RECT, S_T, S_NADAM_G, S_NADAM_M = range(14)
 OPT_ADAM, OPT_ADAMAX, OPT_NADAM, OPT_RADAM, OPT_RMSPROP = range(5)
-
-
-class PtrUploader:
-    """Pointer tables that change every step (the step's gradient tensors) go to the device through rotating PINNED host buffers
-    with a non-blocking copy: `torch.tensor(list, device=...)` stages through pageable memory and holds the host until the stream
-    has drained, which leaves the GPU idle while the rest of the optimizer's host code runs (measured ~1 ms per step)."""
-
-    def __init__(self, n, device, depth=4):
-        import numpy as np
-        self.host = [torch.empty(n, dtype=torch.int64).pin_memory() for _ in range(depth)]
-        self.np = [h.numpy() for h in self.host]
-        self.dev = [torch.empty(n, dtype=torch.int64, device=device) for _ in range(depth)]
-        self.i, self.n = 0, n
-        self._np = np
-
-    def upload(self, ptrs):
-        assert len(ptrs) == self.n
-        k = self.i
-        self.i = (self.i + 1) % len(self.host)
-        self.np[k][:] = self._np.asarray(ptrs, dtype=self._np.int64)
-        self.dev[k].copy_(self.host[k], non_blocking=True)
-        return self.dev[k]
 
 
 # ---- torch-format optimizer state <-> the flat state buffers: pure functions, no device needed --------------------------------------------
@@ -126,114 +104,116 @@ def torch_state_to_flat(kind, state, shapes, dtype=torch.float32):
     return flat, step, mu, present
 
 
-class FusedSGD:
-    NSTATE = 1  # flat zero-initialised state buffers per parameter (SGD: momentum)
-    NSCAL = 0   # floats behind the five counters of `norm_clip`: the step scalars of y3d_mt_step_scalars (none for SGD / AdamW)
-    TORCH_NAME = "SGD"
+# ---- the optimizers: DESIGN.md §3.29 for the two lifetimes of their device state and the capture contract ----------------------------------
+class OptState:
+    """What lives as long as the optimizer, created on its first step in one allocation each: `flat` (NSTATE, sum of numel) zero-
+    initialised state rows, `bufs[i]` the (NSTATE, numel) view of parameter i, `norm_clip` the device counters [norm, clip coefficient,
+    finite flag, steps applied, steps skipped] followed by the NSCAL step scalars, of which `scal` is the view (None for NSCAL = 0)"""
 
-    def __init__(self, param_groups, lr=0.01, momentum=0.937, nesterov=True, weight_decay=0.0, device_momentum=False):
-        """device_momentum: the groups carry a "momentum" key (as torch's do: the reference's warm-up finds it, engine/trainer.py:392),
-        a per-tensor device table holds it next to lr / wd, set_hyper() rewrites it in place and the table-reading kernel
-        (y3d_mt_sgd_tab) is launched - so a captured step follows a momentum schedule.  False: momentum is a launch constant."""
-        self.device_momentum = bool(device_momentum)
+    def __init__(self, sizes, nstate, nscal, dev):
+        self.flat = torch.zeros(nstate, sum(sizes), dtype=torch.float32, device=dev)
+        self.bufs, off = [], 0
+        for n in sizes:
+            self.bufs.append(self.flat[:, off:off + n])
+            off += n
+        self.norm_clip = torch.zeros(5 + nscal, dtype=torch.float32, device=dev)
+        self.scal = self.norm_clip[5:] if nscal else None
+
+
+class OptTable(mt.Table):
+    """The launch table over the `active` parameters (those that carry a gradient), valid while that list and the group layout `hkey`
+    stay: mt.Table's chunk map, the fixed columns ptr["state0"] / ["state1"] into OptState.flat, the refreshable columns col["params"]
+    (plain upload) and col["grads"] (pinned), the per-tensor `lr` / `wd` / `mom` (None unless the momentum is a device table) that
+    set_hyper() rewrites in place, and `partials` of the norm launch"""
+
+    def __init__(self, state, active, sizes, hkey, hyper):
+        dev = state.flat.device
+        super().__init__(sizes, dev, **{f"state{r}": [state.bufs[i][r].data_ptr() for i in active] for r in range(state.flat.shape[0])})
+        self.active, self.hkey = list(active), hkey
+        self.partials = torch.empty(self.nchunks, dtype=torch.float32, device=dev)
+        self.lr, self.wd, self.mom = (None if v is None else torch.tensor(v, dtype=torch.float32, device=dev) for v in hyper)
+        self.column("params", pinned=False)
+        self.column("grads")
+
+
+class FusedOptimizer:
+    """What the fused optimizers share: parameter groups, OptState and OptTable, the clipping launches, step(), zero_grad(), set_hyper(),
+    both checkpoint layouts.  A kind sets NSTATE / NSCAL / TORCH_NAME and has its own constructor arguments, `_update(L, tb, clip, s)` (its
+    launches), `_torch_group_hyper()` (what torch keeps per group beside lr / weight_decay) and `_take_group_hyper(groups)` (the same,
+    taken from a torch dict's groups).  `device_momentum` (class or instance): the groups carry a "momentum" key and a per-
+    tensor device column holds it next to lr / weight_decay - read in one place, `_hyper`."""
+    NSTATE = 1  # flat zero-initialised state buffers per parameter
+    NSCAL = 0   # floats behind the five counters of `norm_clip`: the step scalars of y3d_mt_step_scalars
+    TORCH_NAME = None
+    ALWAYS_CLIP = False  # the update reads the device's count of applied steps, which the clipping launch keeps
+    device_momentum = False
+    momentum = None
+
+    def __init__(self, param_groups, lr, weight_decay):
         if isinstance(param_groups, (list, tuple)) and param_groups and not isinstance(param_groups[0], dict):
             param_groups = [{"params": list(param_groups)}]
-        self.param_groups = []
+        self.param_groups, self.params = [], []
         for g in param_groups:
-            g = dict(g)
-            g.setdefault("lr", lr)
-            g.setdefault("weight_decay", weight_decay)
-            if self.device_momentum:
-                g.setdefault("momentum", float(momentum))
-            g["params"] = [p for p in g["params"] if p.requires_grad]
-            self.param_groups.append(g)
-        self.momentum, self.nesterov = float(momentum), bool(nesterov)
-        self.params = [p for g in self.param_groups for p in g["params"]]
+            self._append_group(g, lr, weight_decay)
         if not self.params:
             raise ValueError("FusedSGD: no parameters")
-        self._state = None
+        self.state = self.table = None
         self._steps = 0
         self.last_norm = None
         self._pending_load = None
         self._seen = set()  # parameters that have carried a gradient (or loaded state): the ones torch would hold state for
         self.auto = None    # build_optimizer(name="auto"): what was chosen
 
-    def add_param_group(self, g):
+    @property
+    def _hyper(self):
+        """(group key, OptTable attribute) of the per-tensor hyper-parameter columns"""
+        return (("lr", "lr"), ("weight_decay", "wd"), ("momentum", "mom"))[:3 if self.device_momentum else 2]
+
+    def _append_group(self, g, lr, weight_decay):
         g = dict(g)
-        g.setdefault("lr", self.param_groups[0]["lr"])
-        g.setdefault("weight_decay", 0.0)
-        if self.device_momentum:
-            g.setdefault("momentum", self.momentum)
+        for (key, _), v in zip(self._hyper, (lr, weight_decay, self.momentum)):
+            g.setdefault(key, v)
         g["params"] = [p for p in g["params"] if p.requires_grad]
         self.param_groups.append(g)
         self.params = [p for gg in self.param_groups for p in gg["params"]]
-        self._state = None
+
+    def add_param_group(self, g):
+        self._append_group(g, self.param_groups[0]["lr"], 0.0)
+        self.state = self.table = None
+
+    def _hkey(self):
+        return [tuple(g[key] for key, _ in self._hyper) + (len(g["params"]),) for g in self.param_groups]
+
+    def _per_tensor(self, key, active):
+        row = [g[key] for g in self.param_groups for _ in g["params"]]
+        return [row[i] for i in active]
 
     def _build(self, active):
-        """tables over the parameters that carry a gradient (torch.optim.SGD and clip_grad_norm_ skip the others, e.g. the neck
-        blocks behind a detect level that `num_scales: 2` leaves unused); momentum buffers are zero-initialised, so the first
-        update `buf = momentum*0 + g` equals torch's `buf = clone(g)` exactly."""
+        """the table over the parameters that carry a gradient (torch.optim.SGD and clip_grad_norm_ skip the others, e.g. the neck
+        blocks behind a detect level that `num_scales: 2` leaves unused); on the first call the state: its buffers are zero-
+        initialised, so the first update `buf = momentum*0 + g` equals torch's `buf = clone(g)` exactly."""
         dev = self.params[0].device
         if dev.type != "cuda":
             raise Y3DError("FusedSGD needs parameters on a HIP device")
         for p in self.params:
             if p.dtype != torch.float32 or not p.is_contiguous():
                 raise Y3DError("FusedSGD: parameters must be contiguous fp32 tensors")
-        old = self._state
-        if old is None:
-            sizes_all = [p.numel() for p in self.params]
-            flat = torch.zeros(self.NSTATE, sum(sizes_all), dtype=torch.float32, device=dev)  # state buffers, one allocation
-            bufs, off = [], 0
-            for n in sizes_all:
-                bufs.append(flat[:, off:off + n])
-                off += n
-        else:
-            flat, bufs = old["flat"], old["bufs"]
-        sizes = [self.params[i].numel() for i in active]
-        ct, co = [], []
-        for t, n in enumerate(sizes):
-            for c in range((n + CHUNK - 1) // CHUNK):
-                ct.append(t)
-                co.append(c)
-        i64 = lambda v: torch.tensor(v, dtype=torch.int64, device=dev)
-        lr_all = [g["lr"] for g in self.param_groups for _ in g["params"]]
-        wd_all = [g["weight_decay"] for g in self.param_groups for _ in g["params"]]
-        st = {
-            "dev": dev, "flat": flat, "bufs": bufs, "nchunks": len(ct), "active": list(active),
-            "sizes": i64(sizes), "ctensor": torch.tensor(ct, dtype=torch.int32, device=dev), "coff": torch.tensor(co, dtype=torch.int32, device=dev),
-            "bptr": i64([bufs[i][0].data_ptr() for i in active]),
-            "bptr2": i64([bufs[i][1].data_ptr() for i in active]) if self.NSTATE > 1 else None, "partials": torch.empty(len(ct), dtype=torch.float32, device=dev),
-            "norm_clip": old["norm_clip"] if old is not None else torch.zeros(5 + self.NSCAL, dtype=torch.float32, device=dev), "pkey": None, "gkey": None,
-            "lr": torch.tensor([lr_all[i] for i in active], dtype=torch.float32, device=dev),
-            "wd": torch.tensor([wd_all[i] for i in active], dtype=torch.float32, device=dev),
-            "hkey": self._hkey(),
-        }
-        if self.device_momentum:
-            mom_all = [g["momentum"] for g in self.param_groups for _ in g["params"]]
-            st["mom"] = torch.tensor([mom_all[i] for i in active], dtype=torch.float32, device=dev)
-        if self.NSCAL:
-            st["scal"] = st["norm_clip"][5:]  # one allocation with the counters: checkpointed and restored with them
+        fresh = self.state is None
+        if fresh:
+            self.state = OptState([p.numel() for p in self.params], self.NSTATE, self.NSCAL, dev)
+        hyper = ([self._per_tensor(key, active) for key, _ in self._hyper] + [None])[:3]
+        self.table = OptTable(self.state, active, [self.params[i].numel() for i in active], self._hkey(), hyper)
         self._seen.update(active)
-        self._state = st
-        if self._pending_load is not None:  # load_state_dict() before the first step
+        if fresh and self._pending_load is not None:  # load_state_dict() before the first step
             sd, self._pending_load = self._pending_load, None
             if "torch" in sd:
                 self._apply_torch(*sd["torch"])
             else:
                 self.load_state_dict(sd)
-        return st
+        return self.table
 
-    def _hkey(self):
-        if self.device_momentum:
-            return [(g["lr"], g["weight_decay"], len(g["params"]), g["momentum"]) for g in self.param_groups]
-        return [(g["lr"], g["weight_decay"], len(g["params"])) for g in self.param_groups]
-
-    def _torch_group_hyper(self):
-        """the hyper-parameters torch keeps per group, beside lr / weight_decay"""
-        return {"momentum": self.momentum, "nesterov": self.nesterov}
-
-    def _take_group_hyper(self, groups):
-        """load_state_dict(torch dict): momentum is one launch constant unless device_momentum keeps it per group"""
+    def _take_group_momentum(self, groups):
+        """momentum is one launch constant unless device_momentum keeps it per group"""
         moms = {float(g["momentum"]) for g in groups if "momentum" in g}
         if self.device_momentum:
             for g, src in zip(self.param_groups, groups):
@@ -244,18 +224,30 @@ class FusedSGD:
         if len(moms) == 1:
             self.momentum = moms.pop()
 
-    def state_dict(self, torch_format=False):
+    def _held(self):
+        """(flat, norm_clip) as they are now: the state's, or those of a native dict loaded before the first step, or None"""
+        if self.state is not None:
+            return self.state.flat, self.state.norm_clip
+        pl = self._pending_load
+        if pl is not None and pl.get("flat") is not None and pl.get("norm_clip") is not None:
+            return pl["flat"], pl["norm_clip"]
+        return None
+
+    def state_dict(self, torch_format=False, native=False):
         """optimizer state for checkpoint / resume (the reference saves `optimizer.state_dict()`, engine/trainer.py:470-486): the flat
         state buffers in parameter order (SGD: momentum; AdamW: exp_avg, exp_avg_sq) and the device-side counters [norm, clip
         coefficient, finite flag, steps APPLIED, steps skipped] - `steps applied` is AdamW's bias-correction step count.
 
         torch_format: torch.optim's layout instead, as the reference's checkpoints hold it - `state[i]` with torch's keys for this
         optimizer (TORCH_STATE) for every parameter that has been active, `param_groups` with lr, weight_decay, momentum / betas,
-        initial_lr when set and `params` indices in group order"""
-        st = self._state
+        initial_lr when set and `params` indices in group order.  native (with torch_format): a third entry "native" = {"steps",
+        "norm_clip" on the CPU or None} - the counters torch's layout has no place for (steps skipped, the step scalars), which
+        load_state_dict takes back; train.Trainer's checkpoints hold it"""
+        held = self._held()
         if not torch_format:
-            return {"steps": self._steps, "flat": None if st is None else st["flat"].detach().clone(),
-                    "norm_clip": None if st is None else st["norm_clip"].detach().clone()}
+            st = self.state
+            return {"steps": self._steps, "flat": None if st is None else st.flat.detach().clone(),
+                    "norm_clip": None if st is None else st.norm_clip.detach().clone()}
         groups, k = [], 0
         for g in self.param_groups:
             d = {"lr": g["lr"], "weight_decay": g["weight_decay"]}
@@ -268,14 +260,17 @@ class FusedSGD:
             groups.append(d)
         shapes = [tuple(p.shape) for p in self.params]
         state = {}
-        if st is not None:
-            nc = st["norm_clip"].detach().cpu()
+        if held is not None:
+            nc = held[1].detach().cpu()
             mu = float(nc[5 + S_MU_PROD]) if self.TORCH_NAME == "NAdam" and float(nc[3]) > 0 else None
-            state = flat_to_torch_state(self.TORCH_NAME, st["flat"], shapes, sorted(self._seen), step=float(nc[3]), mu_product=mu)
+            state = flat_to_torch_state(self.TORCH_NAME, held[0], shapes, sorted(self._seen), step=float(nc[3]), mu_product=mu)
         elif self._pending_load is not None and "torch" in self._pending_load:  # loaded, not stepped yet
             flat, step, mu, present = self._pending_load["torch"]
             state = flat_to_torch_state(self.TORCH_NAME, flat, shapes, present, step=step, mu_product=mu)
-        return {"state": state, "param_groups": groups}
+        sd = {"state": state, "param_groups": groups}
+        if native:
+            sd["native"] = {"steps": self._steps, "norm_clip": None if held is None else held[1].detach().cpu().clone()}
+        return sd
 
     def _convert_torch(self, sd):
         """a torch.optim state dict -> (flat, step, mu_product, indices present), validated against these parameters; nothing is changed"""
@@ -292,19 +287,22 @@ class FusedSGD:
         return torch_state_to_flat(self.TORCH_NAME, state, [tuple(p.shape) for p in self.params])
 
     def _apply_torch(self, flat, step, mu, present):
-        st = self._state
-        st["flat"].copy_(flat)
+        st = self.state
+        st.flat.copy_(flat)
         self._seen.update(present)
         if step is not None:  # (torch's SGD keeps no step count: the device counters stay)
             self._steps = int(step)
-            nc = st["norm_clip"].detach().cpu()
+            nc = st.norm_clip.detach().cpu()
             nc[3] = step
             if mu is not None:
                 nc[5 + S_MU_PROD] = mu
-            st["norm_clip"].copy_(nc)
+            st.norm_clip.copy_(nc)
 
     def load_state_dict(self, sd):
-        """inverse of state_dict(), either format; before the first step the state is kept and applied when the tables are built"""
+        """inverse of state_dict(), either format; before the first step the state is kept and applied when the state is created.
+        A torch-format dict with a "native" entry (state_dict(native=True)) restores the counters behind torch's layout exactly as
+        they were (steps applied / skipped, NAdam's mu_product) - but only into an optimizer that has not stepped yet: one whose
+        state exists takes the torch entries alone."""
         if is_torch_format(sd):  # torch.optim's layout (a reference checkpoint's `ckpt["optimizer"]`)
             conv = self._convert_torch(sd)  # raises before anything is taken over
             for g, src in zip(self.param_groups, sd["param_groups"]):
@@ -312,94 +310,81 @@ class FusedSGD:
                     if key in src:
                         g[key] = float(src[key])
             self._take_group_hyper(sd["param_groups"])
-            if self._state is None:
-                self._pending_load = {"torch": conv}
-                return
-            self._apply_torch(*conv)
-            return self.set_hyper()
-        if self._state is None:
-            self._pending_load = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in sd.items()}
-            self._steps = int(sd["steps"])
+            if self.state is not None:
+                self._apply_torch(*conv)
+                return self.set_hyper()
+            self._pending_load = {"torch": conv}
+            native = sd.get("native")
+            if native is not None and native["norm_clip"] is not None:
+                self._seen.update(conv[3])
+                self.load_state_dict({"steps": native["steps"], "flat": conv[0], "norm_clip": native["norm_clip"]})
             return
-        st = self._state
         self._steps = int(sd["steps"])
+        if self.state is None:
+            self._pending_load = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in sd.items()}
+            return
+        st = self.state
         if sd.get("flat") is not None:
-            if sd["flat"].shape != st["flat"].shape:
-                raise Y3DError(f"optimizer state of shape {tuple(sd['flat'].shape)} does not fit these parameters {tuple(st['flat'].shape)}")
-            st["flat"].copy_(sd["flat"])
-            st["norm_clip"].copy_(sd["norm_clip"])
+            if sd["flat"].shape != st.flat.shape:
+                raise Y3DError(f"optimizer state of shape {tuple(sd['flat'].shape)} does not fit these parameters {tuple(st.flat.shape)}")
+            st.flat.copy_(sd["flat"])
+            st.norm_clip.copy_(sd["norm_clip"])
 
     def set_hyper(self):
-        """write the groups' current lr / weight_decay (and momentum, with device_momentum) into the EXISTING device tables (in place: a captured hipGraph of the step keeps
-        reading them, graph.GraphedTrainStep) - what a scheduler's `param_group["lr"] = ...` needs before the next replay"""
-        st = self._state
-        if st is None:
+        """write the groups' current lr / weight_decay (and momentum, with device_momentum) into the EXISTING device columns (in place: a
+        captured hipGraph of the step keeps reading them, graph.GraphedTrainStep) - what a scheduler's `param_group["lr"] = ...` needs
+        before the next replay"""
+        tb = self.table
+        if tb is None:
             return
-        lr_all = [g["lr"] for g in self.param_groups for _ in g["params"]]
-        wd_all = [g["weight_decay"] for g in self.param_groups for _ in g["params"]]
-        st["lr"].copy_(torch.tensor([lr_all[i] for i in st["active"]], dtype=torch.float32), non_blocking=False)
-        st["wd"].copy_(torch.tensor([wd_all[i] for i in st["active"]], dtype=torch.float32), non_blocking=False)
-        if self.device_momentum:
-            mom_all = [g["momentum"] for g in self.param_groups for _ in g["params"]]
-            st["mom"].copy_(torch.tensor([mom_all[i] for i in st["active"]], dtype=torch.float32), non_blocking=False)
-        st["hkey"] = self._hkey()
+        for key, attr in self._hyper:
+            getattr(tb, attr).copy_(torch.tensor(self._per_tensor(key, tb.active), dtype=torch.float32), non_blocking=False)
+        tb.hkey = self._hkey()
 
     def _tables(self):
         active = [i for i, p in enumerate(self.params) if p.grad is not None]
         if not active:
             raise Y3DError("FusedSGD.step: no parameter has a gradient")
-        st = self._state
+        tb = self.table
         hkey = self._hkey()
-        if st is not None and st["active"] == active and st["hkey"] != hkey and [h[2] for h in st["hkey"]] == [h[2] for h in hkey]:
+        if tb is not None and tb.active == active and tb.hkey != hkey and [h[-1] for h in tb.hkey] == [h[-1] for h in hkey]:
             self.set_hyper()  # only the values moved (a scheduler): same tables, new contents
-        if st is None or st["active"] != active or st["hkey"] != hkey:
-            st = self._build(active)
-        pkey = [self.params[i].data_ptr() for i in active]
-        if pkey != st["pkey"]:  # parameters re-pointed (e.g. sibling-branch stacking, .to()): refresh
-            st["pptr"] = torch.tensor(pkey, dtype=torch.int64, device=st["dev"])
-            st["pkey"] = pkey
-        gkey = []
-        for i in active:
-            p = self.params[i]
-            g = p.grad
-            if g.dtype != torch.float32 or not g.is_contiguous():
-                g = p.grad = g.float().contiguous()
-            gkey.append(g.data_ptr())
-        if gkey != st["gkey"]:
-            if st.get("gup") is None or st["gup"].n != len(gkey):
-                st["gup"] = PtrUploader(len(gkey), st["dev"])
-            st["gptr"] = st["gup"].upload(gkey)
-            st["gkey"] = gkey
-        return st
+        if tb is None or tb.active != active or tb.hkey != hkey:
+            tb = self._build(active)
+        ps = [self.params[i] for i in active]
+        tb.col["params"].refresh([p.data_ptr() for p in ps])  # parameters re-pointed (e.g. sibling-branch stacking, .to()): refresh
+        grads = tb.fp32_contiguous([p.grad for p in ps])
+        for p, g in zip(ps, grads):
+            if g is not p.grad:
+                p.grad = g
+        tb.col["grads"].refresh([g.data_ptr() for g in grads])
+        return tb
 
     @torch.no_grad()
     def step(self, max_norm: float | None = 10.0):
         """clip (when max_norm is given) + update; self.last_norm holds the device tensor [total_norm, clip_coef, finite flag, steps
         applied, steps skipped].  A step whose gradient norm is inf / NaN is skipped ON THE DEVICE (no host synchronisation): parameters,
         momentum / Adam state and AdamW's bias-correction step count stay - torch.cuda.amp.GradScaler.step's rule, engine/trainer.py:
-        567-572.  Under ddp.FlatGradReducer the norm is that of the all-reduced buffer, so every rank takes the same decision."""
-        st = self._tables()
+        567-572.  Under ddp.FlatGradReducer the norm is that of the all-reduced buffer, so every rank takes the same decision.
+
+        The Adam family (ALWAYS_CLIP) runs the clipping launch without a `max_norm` too (with an infinite bound: coefficient 1), because
+        the bias corrections read the number of APPLIED steps from its device-side counter - ONE source for the step count, whether or
+        not the step is clipped, eager or replayed from a hipGraph, fresh or resumed.  Side effect: a step with a non-finite gradient
+        norm is skipped in that case too."""
+        if max_norm is None and self.ALWAYS_CLIP:
+            max_norm = float("inf")
+        tb = self._tables()
         L, s = lib(), ops.stream()
         clip = None
         if max_norm is not None:
-            L.mt_sqnorm(st["gptr"].data_ptr(), st["sizes"].data_ptr(), st["ctensor"].data_ptr(), st["coff"].data_ptr(), st["nchunks"], CHUNK,
-                        st["partials"].data_ptr(), s)
-            L.mt_clip_coef(st["partials"].data_ptr(), st["nchunks"], float(max_norm), st["norm_clip"].data_ptr(), s)
-            clip = st["norm_clip"].data_ptr()
-            self.last_norm = st["norm_clip"][:5] if self.NSCAL else st["norm_clip"]
+            nc = self.state.norm_clip
+            L.mt_sqnorm(tb.col["grads"].dev.data_ptr(), tb.sizes.data_ptr(), *tb.chunks, tb.partials.data_ptr(), s)
+            L.mt_clip_coef(tb.partials.data_ptr(), tb.nchunks, float(max_norm), nc.data_ptr(), s)
+            clip = nc.data_ptr()
+            self.last_norm = nc[:5] if self.NSCAL else nc
         self._steps += 1
-        self._update(L, st, clip, s)
+        self._update(L, tb, clip, s)
         ops.bump_weight_epoch()  # the parameters changed behind torch's version counters
-
-    def _update(self, L, st, clip, s):
-        if self.device_momentum:
-            L.mt_sgd_tab(st["pptr"].data_ptr(), st["gptr"].data_ptr(), st["bptr"].data_ptr(), st["sizes"].data_ptr(), st["lr"].data_ptr(),
-                         st["wd"].data_ptr(), st["mom"].data_ptr(), st["ctensor"].data_ptr(), st["coff"].data_ptr(), st["nchunks"], CHUNK,
-                         int(self.nesterov), 0, clip, s)
-            return
-        L.mt_sgd(st["pptr"].data_ptr(), st["gptr"].data_ptr(), st["bptr"].data_ptr(), st["sizes"].data_ptr(), st["lr"].data_ptr(),
-                 st["wd"].data_ptr(), st["ctensor"].data_ptr(), st["coff"].data_ptr(), st["nchunks"], CHUNK, self.momentum, int(self.nesterov),
-                 0, clip, s)
 
     def zero_grad(self, set_to_none: bool = True):
         for p in self.params:
@@ -408,15 +393,75 @@ class FusedSGD:
             elif p.grad is not None:
                 p.grad.zero_()
 
+    # ---- what graph.GraphedTrainStep needs: undoing its warm-up steps, and a capture of step() ------------------------------------------
+    def snapshot(self):
+        """-> (host step count, clones of flat and norm_clip, or None when there is no state yet) for restore()"""
+        st = self.state
+        return self._steps, None if st is None else (st.flat.clone(), st.norm_clip.clone())
 
-class FusedAdamW(FusedSGD):
-    """torch.optim.AdamW(betas, eps, weight_decay per group), amsgrad off; same tables and clipping as FusedSGD"""
-    NSTATE = 2  # exp_avg, exp_avg_sq
-    TORCH_NAME = "AdamW"
+    def restore(self, snap):
+        """put a snapshot() back IN PLACE (every address stays); state that did not exist at the snapshot is zeroed"""
+        self._steps, held = snap
+        st = self.state
+        if st is not None and held is None:
+            st.flat.zero_()
+            st.norm_clip.zero_()
+        elif st is not None:
+            st.flat.copy_(held[0])
+            st.norm_clip.copy_(held[1])
 
-    def __init__(self, param_groups, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
-        super().__init__(param_groups, lr=lr, momentum=betas[0], nesterov=False, weight_decay=weight_decay)
+    def begin_capture(self):
+        """before step() is recorded into a hipGraph: the gradient column gets an uploader of its own, of depth 1, and no key (the
+        recorded step uploads).  The optimizer's rotating pinned buffers would be overwritten a few eager steps later, and the replays
+        would read those pointers."""
+        self.table.column("grads", depth=1, now=True)
+        self._steps_at_capture = self._steps
+
+    def end_capture(self):
+        """after the capture -> what the graph must keep alive: the table as captured (chunk maps, state / parameter / gradient pointer
+        columns, the depth-1 uploader whose pinned buffer the graph's copy node reads, lr / wd / mom).  The optimizer keeps the SAME
+        table, so set_hyper() reaches the replays, with a fresh gradient column: its next eager step builds an uploader and uploads.
+        The step the recorded Python counted has not run: the host step count is put back."""
+        held = self.table.held()
+        self.table.column("grads")
+        self._steps = self._steps_at_capture
+        return held
+
+
+class FusedSGD(FusedOptimizer):
+    """torch.optim.SGD (dampening 0) with Nesterov momentum"""
+    TORCH_NAME = "SGD"
+
+    def __init__(self, param_groups, lr=0.01, momentum=0.937, nesterov=True, weight_decay=0.0, device_momentum=False):
+        """device_momentum: the groups carry a "momentum" key (as torch's do: the reference's warm-up finds it, engine/trainer.py:392),
+        a per-tensor device table holds it next to lr / wd, set_hyper() rewrites it in place and the table-reading kernel
+        (y3d_mt_sgd_tab) is launched - so a captured step follows a momentum schedule.  False: momentum is a launch constant."""
+        self.device_momentum = bool(device_momentum)
+        self.momentum, self.nesterov = float(momentum), bool(nesterov)
+        super().__init__(param_groups, lr, weight_decay)
+
+    def _torch_group_hyper(self):
+        return {"momentum": self.momentum, "nesterov": self.nesterov}
+
+    _take_group_hyper = FusedOptimizer._take_group_momentum
+
+    def _update(self, L, tb, clip, s):
+        head = (tb.col["params"].dev.data_ptr(), tb.col["grads"].dev.data_ptr(), tb.ptr["state0"].data_ptr(), tb.sizes.data_ptr(),
+                tb.lr.data_ptr(), tb.wd.data_ptr())
+        if self.device_momentum:
+            L.mt_sgd_tab(*head, tb.mom.data_ptr(), *tb.chunks, int(self.nesterov), 0, clip, s)
+        else:
+            L.mt_sgd(*head, *tb.chunks, self.momentum, int(self.nesterov), 0, clip, s)
+
+
+class _Betas(FusedOptimizer):
+    """the Adam family: betas and eps as launch constants, two state rows, the clipping launch always"""
+    NSTATE = 2  # exp_avg, exp_avg_sq (Adamax: exp_inf)
+    ALWAYS_CLIP = True
+
+    def __init__(self, param_groups, lr, betas, eps, weight_decay):
         self.betas, self.eps = (float(betas[0]), float(betas[1])), float(eps)
+        super().__init__(param_groups, lr, weight_decay)
 
     def _torch_group_hyper(self):
         return {"betas": self.betas, "eps": self.eps}
@@ -432,23 +477,25 @@ class FusedAdamW(FusedSGD):
         if len(eps) == 1:
             self.eps = eps.pop()
 
-    def step(self, max_norm: float | None = 10.0):
-        """as FusedSGD.step; without a `max_norm` the clipping launch still runs (with an infinite bound: coefficient 1), because the
-        bias corrections read the number of APPLIED steps from its device-side counter - ONE source for the step count, whether or not
-        the step is clipped, eager or replayed from a hipGraph, fresh or resumed (round-3 advisor finding).  Side effect: a step with a
-        non-finite gradient norm is skipped in that case too."""
-        return super().step(max_norm=float("inf") if max_norm is None else max_norm)
-
-    def _update(self, L, st, clip, s):
-        b1, b2 = self.betas
-        bc1 = 1.0 - b1 ** max(self._steps, 1)  # (placeholders: the kernel recomputes both from the device-side step count)
-        bc2s = math.sqrt(1.0 - b2 ** max(self._steps, 1))
-        L.mt_adamw(st["pptr"].data_ptr(), st["gptr"].data_ptr(), st["bptr"].data_ptr(), st["bptr2"].data_ptr(), st["sizes"].data_ptr(),
-                   st["lr"].data_ptr(), st["wd"].data_ptr(), st["ctensor"].data_ptr(), st["coff"].data_ptr(), st["nchunks"], CHUNK, b1, b2,
-                   self.eps, bc1, bc2s, clip, s)
+    def _pointers(self, tb):
+        return (tb.col["params"].dev.data_ptr(), tb.col["grads"].dev.data_ptr(), tb.ptr["state0"].data_ptr(), tb.ptr["state1"].data_ptr(),
+                tb.sizes.data_ptr(), tb.lr.data_ptr(), tb.wd.data_ptr())
 
 
-class FusedAdam(FusedAdamW):
+class FusedAdamW(_Betas):
+    """torch.optim.AdamW(betas, eps, weight_decay per group), amsgrad off"""
+    TORCH_NAME = "AdamW"
+
+    def __init__(self, param_groups, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
+        super().__init__(param_groups, lr, betas, eps, weight_decay)
+
+    def _update(self, L, tb, clip, s):
+        # bias_corr1 / bias_corr2_sqrt: the launcher wants them positive; the kernel recomputes both from the device's count of applied
+        # steps whenever norm_clip is given, which ALWAYS_CLIP makes every step of this class
+        L.mt_adamw(*self._pointers(tb), *tb.chunks, *self.betas, self.eps, 1.0, 1.0, clip, s)
+
+
+class FusedAdam(_Betas):
     """torch.optim.Adam: coupled L2 decay `g += wd*p` (amsgrad off).  Two launches after the clipping pair: y3d_mt_step_scalars turns
     the device's count of APPLIED steps into the bias corrections (and NAdam's / RAdam's scalars), y3d_mt_update applies them - one
     device-side source for everything that depends on the step, eager or replayed, as FusedAdamW's bias corrections"""
@@ -458,64 +505,59 @@ class FusedAdam(FusedAdamW):
     MOMENTUM_DECAY = 4e-3  # torch.optim.NAdam's default (read by y3d_mt_step_scalars for every kind; used by NAdam)
 
     def __init__(self, param_groups, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
-        super().__init__(param_groups, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+        super().__init__(param_groups, lr, betas, eps, weight_decay)
 
-    def _update(self, L, st, clip, s):
-        b1, b2 = self.betas
-        scal = st["scal"].data_ptr()
-        L.mt_step_scalars(clip, b1, b2, self.MOMENTUM_DECAY, scal, s)
-        L.mt_update(self.KIND, st["pptr"].data_ptr(), st["gptr"].data_ptr(), st["bptr"].data_ptr(), st["bptr2"].data_ptr(), st["sizes"].data_ptr(),
-                    st["lr"].data_ptr(), st["wd"].data_ptr(), None, st["ctensor"].data_ptr(), st["coff"].data_ptr(), st["nchunks"], CHUNK, b1, b2,
-                    self.eps, scal, clip, s)
+    def _update(self, L, tb, clip, s):
+        scal = self.state.scal.data_ptr()
+        L.mt_step_scalars(clip, *self.betas, self.MOMENTUM_DECAY, scal, s)
+        L.mt_update(self.KIND, *self._pointers(tb), None, *tb.chunks, *self.betas, self.eps, scal, clip, s)
 
 
 class FusedAdamax(FusedAdam):
     """torch.optim.Adamax: exp_inf = max(beta2*exp_inf, |g| + eps); p -= lr/(1-beta1^t) * exp_avg / exp_inf"""
-    KIND = OPT_ADAMAX
-    TORCH_NAME = "Adamax"
+    KIND, TORCH_NAME = OPT_ADAMAX, "Adamax"
 
     def __init__(self, param_groups, lr=2e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
-        super().__init__(param_groups, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+        super().__init__(param_groups, lr, betas, eps, weight_decay)
 
 
 class FusedNAdam(FusedAdam):
     """torch.optim.NAdam (momentum_decay 4e-3, coupled decay); mu_product is the one piece of state among the step scalars"""
-    KIND = OPT_NADAM
-    TORCH_NAME = "NAdam"
+    KIND, TORCH_NAME = OPT_NADAM, "NAdam"
 
     def __init__(self, param_groups, lr=2e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
-        super().__init__(param_groups, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+        super().__init__(param_groups, lr, betas, eps, weight_decay)
 
 
 class FusedRAdam(FusedAdam):
     """torch.optim.RAdam (coupled decay): the unrectified arm while rho_t <= 5, the rectified one after"""
-    KIND = OPT_RADAM
-    TORCH_NAME = "RAdam"
+    KIND, TORCH_NAME = OPT_RADAM, "RAdam"
 
 
-class FusedRMSprop(FusedSGD):
+class FusedRMSprop(FusedOptimizer):
     """torch.optim.RMSprop(alpha, eps, momentum), not centered; the momentum always comes from the per-tensor device table"""
     NSTATE = 2  # square_avg, momentum_buffer
     TORCH_NAME = "RMSprop"
+    device_momentum = True
 
     def __init__(self, param_groups, lr=1e-2, alpha=0.99, eps=1e-8, weight_decay=0.0, momentum=0.0):
-        super().__init__(param_groups, lr=lr, momentum=momentum, nesterov=False, weight_decay=weight_decay, device_momentum=True)
-        self.alpha, self.eps = float(alpha), float(eps)
+        self.momentum, self.alpha, self.eps = float(momentum), float(alpha), float(eps)
+        super().__init__(param_groups, lr, weight_decay)
 
     def _torch_group_hyper(self):
         return {"alpha": self.alpha, "eps": self.eps}
 
     def _take_group_hyper(self, groups):
-        super()._take_group_hyper(groups)
+        self._take_group_momentum(groups)
         for key in ("alpha", "eps"):
             vals = {float(g[key]) for g in groups if key in g}
             if len(vals) == 1:
                 setattr(self, key, vals.pop())
 
-    def _update(self, L, st, clip, s):
-        L.mt_update(OPT_RMSPROP, st["pptr"].data_ptr(), st["gptr"].data_ptr(), st["bptr"].data_ptr(), st["bptr2"].data_ptr(),
-                    st["sizes"].data_ptr(), st["lr"].data_ptr(), st["wd"].data_ptr(), st["mom"].data_ptr(), st["ctensor"].data_ptr(),
-                    st["coff"].data_ptr(), st["nchunks"], CHUNK, 0.0, self.alpha, self.eps, None, clip, s)
+    def _update(self, L, tb, clip, s):
+        L.mt_update(OPT_RMSPROP, tb.col["params"].dev.data_ptr(), tb.col["grads"].dev.data_ptr(), tb.ptr["state0"].data_ptr(),
+                    tb.ptr["state1"].data_ptr(), tb.sizes.data_ptr(), tb.lr.data_ptr(), tb.wd.data_ptr(), tb.mom.data_ptr(), *tb.chunks,
+                    0.0, self.alpha, self.eps, None, clip, s)
 
 
 class Schedule:
@@ -607,16 +649,12 @@ class ModelEMA:
         dev = pairs[0][0].device
         if dev.type != "cuda":
             raise Y3DError("ModelEMA needs the models on a HIP device")
-        ct, co = [], []
-        for t, (v, _, _) in enumerate(pairs):
-            for c in range((v.numel() + CHUNK - 1) // CHUNK):
-                ct.append(t)
-                co.append(c)
-        i64 = lambda x: torch.tensor(x, dtype=torch.int64, device=dev)
-        i32 = lambda x: torch.tensor(x, dtype=torch.int32, device=dev)
-        self._tab = {"pairs": pairs, "n": len(ct), "sizes": i64([v.numel() for v, _, _ in pairs]), "reps": i32([r for _, _, r in pairs]),
-                     "ct": i32(ct), "co": i32(co), "ekey": None, "mkey": None, "model": model}
-        return self._tab
+        tb = self._tab = mt.Table([v.numel() for v, _, _ in pairs], dev)
+        tb.column("ema", pinned=False)  # plain uploads: the addresses move when storage is re-pointed, not from step to step
+        tb.column("model", pinned=False)
+        self._pairs, self._model = pairs, model
+        self._reps = torch.tensor([r for _, _, r in pairs], dtype=torch.int32, device=dev)
+        return tb
 
     @torch.no_grad()
     def update(self, model, guard=None):
@@ -628,22 +666,17 @@ class ModelEMA:
         self.updates += 1
         d = self.decay(self.updates)
         tb = self._tab
-        if tb is None or tb["model"] is not model:
+        if tb is None or self._model is not model:
             tb = self._tables(model)
-        ekey = [v.data_ptr() for v, _, _ in tb["pairs"]]
-        mkey = [m.data_ptr() for _, m, _ in tb["pairs"]]
+        ekey = [v.data_ptr() for v, _, _ in self._pairs]
         if len(set(ekey)) != len(ekey):  # storage re-pointed so that entries merged or split: rebuild the multiplicities
             tb = self._tables(model)
-            ekey = [v.data_ptr() for v, _, _ in tb["pairs"]]
-            mkey = [m.data_ptr() for _, m, _ in tb["pairs"]]
-        dev = tb["sizes"].device
-        if ekey != tb["ekey"]:
-            tb["eptr"], tb["ekey"] = torch.tensor(ekey, dtype=torch.int64, device=dev), ekey
-        if mkey != tb["mkey"]:
-            tb["mptr"], tb["mkey"] = torch.tensor(mkey, dtype=torch.int64, device=dev), mkey
+            ekey = [v.data_ptr() for v, _, _ in self._pairs]
+        eptr = tb.col["ema"].refresh(ekey)
+        mptr = tb.col["model"].refresh([m.data_ptr() for _, m, _ in self._pairs])
         ops.bump_param_epoch()
-        lib().mt_ema(tb["eptr"].data_ptr(), tb["mptr"].data_ptr(), tb["sizes"].data_ptr(), tb["reps"].data_ptr(), tb["ct"].data_ptr(),
-                     tb["co"].data_ptr(), tb["n"], CHUNK, float(d), float(1 - d), guard.data_ptr() if guard is not None else None, ops.stream())
+        lib().mt_ema(eptr.data_ptr(), mptr.data_ptr(), tb.sizes.data_ptr(), self._reps.data_ptr(), *tb.chunks, float(d), float(1 - d),
+                     guard.data_ptr() if guard is not None else None, ops.stream())
 
     def update_attr(self, model, include=(), exclude=("process_group", "reducer")):
         """utils/torch_utils.py:445-448 / copy_attr :342-349"""
@@ -665,17 +698,6 @@ def accum_layout(sizes, chunk=CHUNK, align=ACC_ALIGN):
         offs.append(pos)
         pos += (int(n) + align - 1) // align * align
     return offs, pos
-
-
-def chunk_map(sizes, chunk=CHUNK):
-    """Host only: the (chunk_tensor, chunk_off) tables of the multi-tensor launches: workgroup c handles elements
-    [chunk_off[c] * chunk, + chunk) of tensor chunk_tensor[c]"""
-    ct, co = [], []
-    for t, n in enumerate(sizes):
-        for c in range((int(n) + chunk - 1) // chunk):
-            ct.append(t)
-            co.append(c)
-    return ct, co
 
 
 class GradAccumulator:
@@ -717,13 +739,8 @@ class GradAccumulator:
         tb = self._tabs.get(key)
         if tb is None:
             dev = self._ensure().device
-            sizes = [self.sizes[i] for i in active]
-            ct, co = chunk_map(sizes)
-            tb = {"n": len(ct), "host_sizes": sizes, "sizes": torch.tensor(sizes, dtype=torch.int64, device=dev),
-                  "ct": torch.tensor(ct, dtype=torch.int32, device=dev), "co": torch.tensor(co, dtype=torch.int32, device=dev),
-                  "aptr": torch.tensor([self.views[i].data_ptr() for i in active], dtype=torch.int64, device=dev), "up": None, "gkey": None,
-                  "gptr": None}
-            self._tabs[key] = tb
+            tb = self._tabs[key] = mt.Table([self.sizes[i] for i in active], dev, arena=[self.views[i].data_ptr() for i in active])
+            tb.column("grads")
         return tb
 
     @torch.no_grad()
@@ -740,16 +757,10 @@ class GradAccumulator:
             raise Y3DError(f"GradAccumulator.add: {len(active)} parameters carry a gradient, the window began with {len(self._active)} "
                            "(the active set may not change between reset() calls)")
         tb = self._table(active)
-        grads = []
-        for i in active:
-            p = self.params[i]
-            g = p.grad
-            if g.dtype != torch.float32 or not g.is_contiguous():
-                g = p.grad = g.float().contiguous()
-            grads.append(g)
-        if len(tb["host_sizes"]) != len(grads):
-            raise Y3DError(f"GradAccumulator.add: a table of {len(tb['host_sizes'])} tensors for {len(grads)} gradients")
-        for i, g, n in zip(active, grads, tb["host_sizes"]):
+        grads = tb.fp32_contiguous([self.params[i].grad for i in active])
+        if len(tb.host_sizes) != len(grads):
+            raise Y3DError(f"GradAccumulator.add: a table of {len(tb.host_sizes)} tensors for {len(grads)} gradients")
+        for i, g, n in zip(active, grads, tb.host_sizes):
             if not (n == self.params[i].numel() == g.numel()):
                 raise Y3DError(f"GradAccumulator.add: parameter {i} has {self.params[i].numel()} elements, its gradient {g.numel()}, "
                                f"the table {n}")
@@ -759,13 +770,8 @@ class GradAccumulator:
                 raise Y3DError(f"GradAccumulator.add: the uploader holds {uploader.n} pointers, {len(gkey)} gradients")
             gptr = uploader.upload(gkey)
         else:
-            if gkey != tb["gkey"]:
-                if tb["up"] is None:
-                    tb["up"] = PtrUploader(len(gkey), self.arena.device)
-                tb["gptr"], tb["gkey"] = tb["up"].upload(gkey), gkey
-            gptr = tb["gptr"]
-        lib().mt_grad_acc(tb["aptr"].data_ptr(), gptr.data_ptr(), tb["sizes"].data_ptr(), tb["ct"].data_ptr(), tb["co"].data_ptr(), tb["n"],
-                          CHUNK, ops.stream())
+            gptr = tb.col["grads"].refresh(gkey)
+        lib().mt_grad_acc(tb.ptr["arena"].data_ptr(), gptr.data_ptr(), tb.sizes.data_ptr(), *tb.chunks, ops.stream())
         for i in active:
             self.params[i].grad = None
         self._active = active

@@ -186,17 +186,6 @@ class HtlWeights:
         self.ints.copy_(torch.tensor([sd["count"], sd["have_init"], sd["status"], 0], dtype=torch.int32))
 
 
-def load_optimizer(opt, sd):
-    """a checkpoint's `optimizer` -> opt: torch's layout (groups' hyper-parameters, state buffers, Adam's step count), then the native
-    counters behind it (steps applied / skipped, NAdam's mu_product) exactly as they were"""
-    opt.load_state_dict(sd)
-    native = sd.get("native")
-    if native is not None and opt._state is None:
-        flat, _, _, present = opt._convert_torch(sd)
-        opt._seen.update(present)
-        opt.load_state_dict({"steps": native["steps"], "flat": flat, "norm_clip": native["norm_clip"]})
-
-
 class Trainer:
     """`Trainer(model, train_split, validator).fit()`; see the module docstring.  Defaults: the reference's cfg/default.yaml.
 
@@ -297,7 +286,7 @@ class Trainer:
         self.model.load_state_dict(ck["model"])
         self.ema.ema.load_state_dict(ck["ema"])
         self.ema.updates = ck["updates"]
-        load_optimizer(self.opt, ck["optimizer"])
+        self.opt.load_state_dict(ck["optimizer"])  # torch's layout, then the native counters behind it
         self.best_fitness, self.history = ck["best_fitness"], list(ck["history"])
         self.stopper.load_state_dict(ck["stopper"])
         self.start_epoch = ck["epoch"] + 1
@@ -310,9 +299,7 @@ class Trainer:
         ops.bump_weight_epoch()
 
     def checkpoint(self, epoch):
-        opt_sd = self.opt.state_dict(torch_format=True)
-        st = self.opt._state
-        opt_sd["native"] = {"steps": self.opt._steps, "norm_clip": None if st is None else st["norm_clip"].detach().cpu().clone()}
+        opt_sd = self.opt.state_dict(torch_format=True, native=True)
         cpu = lambda sd: {k: v.detach().cpu().clone() for k, v in sd.items()}
         rng = {"numpy": np.random.get_state(), "torch": torch.get_rng_state(), "torch_cuda": torch.cuda.get_rng_state(self.device),
                "random": random.getstate()}
