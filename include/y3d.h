@@ -154,6 +154,10 @@ int y3d_get_tile_kernels(void);
 /* same for the row-wide workgroup slabs of the BatchNorm forward / backward-apply passes on bf16 tensors with >= 512 channels
  * (bn_act.hip: slab_width) */
 int y3d_set_bn_wide_slabs(int enable);
+/* same for the zero-skip of y3d_proj_group_bn_bwd (mode 0) and y3d_proj_group_bwd_weight_bn_mfma (proj_bn_mfma.hip): on (the default),
+ * pixel chunks whose `dout` rows of a branch are all +0 skip that branch's dz / activation / MFMA work; off, every chunk takes the
+ * dense path.  The results are bit-identical for finite inputs (the header of proj_bn_mfma.hip has the argument and the one difference) */
+int y3d_set_proj_zero_skip(int enable);
 /* grad_oihw (+)= dL/dw.  Cin may be channel-padded (stem): only the first Cin_real channels are written. */
 int y3d_conv2d_bwd_weight(int dtype, const void* x, int64_t xsb, int64_t xsh, int64_t xsw, int B, int H, int W, int Cin,
                           int Cin_real, const void* dy, int64_t dsw, int Ho, int Wo, int Cout, int groups, int kh, int kw,
