@@ -403,6 +403,21 @@ int y3d_distill_loss(int dtype, int nl, const void* const* embs, const int64_t* 
 int y3d_distill_scatter(int dtype, const void* rows, const int* idx, const int* nrows, const float* scale, int cap, int C, void* grad,
                         int64_t sb, int64_t sh, int64_t sw, int a0, int H, int W, void* stream);
 
+/* Foreground depth map loss, utils/loss.py:1225-1365 ForegroundDepthMapLoss (focal_loss / one_hot :1399-1522), fgdm_loss.hip.
+ * logits: (B, num_bins + 1, h, w) of `dtype` with element strides (sb, sc, sh, sw): contiguous and channels_last are both just strides.
+ * depth_map: dense (B, H, W) float32 (map_f64 == 0) or float64 (map_f64 != 0); (h, w) must be (H / 16, W / 16).  Cell (b, i, j) samples
+ * the map at ATen's nearest-exact index, bins the depth with the LID rule in float64 (class num_bins for out-of-range, non-finite and
+ * background depths), and takes sum_c (delta_ct + 1e-6) * -alpha (1 - p_c)^gamma log p_c, weighted fg_weight where the depth is > 0,
+ * else bg_weight.  loss[0] = sum of the weighted cell losses / (B h w); dlogits (the logits' dtype and strides) = d loss / d logits.
+ * partials: y3d_fgdm_loss_blocks(B, h, w) floats, folded in a fixed order (no float atomics: the same bits on every run).
+ * targets: NULL, or B*h*w ints that receive every cell's class (a debug output).  num_bins <= 255; gamma == 0 or gamma >= 1. */
+int y3d_fgdm_loss_blocks(int B, int h, int w);
+int y3d_fgdm_loss(int dtype, const void* logits, int64_t sb, int64_t sc, int64_t sh, int64_t sw, int map_f64, const void* depth_map, int B,
+                  int H, int W, int h, int w, int num_bins, double dmin, double dmax, float alpha, float gamma, float fg_weight,
+                  float bg_weight, void* dlogits, float* partials, float* loss, int* targets, void* stream);
+/* dst[i] = src[i] * scale[0] for n elements of `dtype` (16-byte aligned, dense, not overlapping); scale: device fp32 */
+int y3d_fgdm_scale(int dtype, const void* src, const float* scale, void* dst, int64_t n, void* stream);
+
 /* 2D counterparts (tal_loss2d.hip): TaskAlignedAssigner utils/tal.py:45-94 and v8DetectionLoss utils/loss.py:206-257 (+BboxLoss :82-113,
  * DFL block.py:59-62).  maps[l]: (B, H, W, 64 + nc) with channel order [4 x 16 DFL bins | nc class logits]; gt: (B, n, 5) = cls | box xyxy px.
  * scratch as y3d_tal3d_scratch_floats.  items[3] = (box, cls, dfl) incl. gains; partials: 3 * ceil(B*A/256) floats */
@@ -494,6 +509,30 @@ int y3d_kitti_encode_labels(const double* rec, const int* img_i, const double* i
                             double* bboxes, float* center_2d, float* size_2d, double* center_3d, double* size_3d, double* depth,
                             int64_t* heading_bin, double* heading_res, float* batch_idx, int* counts, double* calib, double* ratio_pad,
                             void* stream);
+/* y3d_kitti_encode_labels (the same kernel, the same outputs bit for bit) that also writes the per-line depth table of the foreground
+ * depth map: line_depth (B, 2, 64) float32, [b][0][i] = the depth label line i of image b's own file paints (the float32 rounding of
+ * pos z * crop scale, never the camera distance), [b][1][i] = the same for the mixup partner's line i; +inf for a line that is
+ * dropped by the filter chain, lies behind the max_objs cut or does not exist. */
+int y3d_kitti_encode_labels_depths(const double* rec, const int* img_i, const double* img_f, int B, int out_w, int out_h, double min_depth,
+                                   double max_depth, int use_camera_dis, const double* mean_size, int n_cls, int max_objs, int64_t* cls,
+                                   double* bboxes, float* center_2d, float* size_2d, double* center_3d, double* size_3d, double* depth,
+                                   int64_t* heading_bin, double* heading_res, float* batch_idx, int* counts, double* calib,
+                                   double* ratio_pad, float* line_depth, void* stream);
+/* Foreground depth maps, `load_depth_maps` of KITTIDataset.__getitem__ (data/datasets/kitti.py:143-145, 170-201, 286-287, 384-385,
+ * 409-417), kitti_depth_map.hip.  A mask is (h, w) uint8, a pixel = the label-file line index of its object (ids above 255 stored as
+ * 255).  Masks either as per-image device pointers `mask` / `mask2` (B each; the partner's entry NULL for an unmixed image, mask2 NULL
+ * when no image is mixed) with arena == NULL, or as one `arena` with mask_off (N) int64 byte offsets and the device draw table
+ * `draws` (B, draw_w) float64 whose columns 0 / 1 hold the position and the partner (-1: none); then mask == mask2 == NULL.  wide: NULL,
+ * or uint8 flags of the masks that came from 16-bit files (Pillow warps an I;16 image by a path of its own): (B, 2) own | partner
+ * with mask pointers, (N) per frame with an arena.  hw (B, 2) int32 (h, w) of the masks, flip (B) int32, trans_inv (B, 6) float64: the tables of y3d_kitti_image_aug; max_side: the largest mask
+ * side (refused from 32768).  out (B, out_h, out_w) float32: per pixel the source pixel of Pillow's Image.transform(AFFINE, NEAREST,
+ * fillcolor=51) over the mirrored mask - its scale path (a[1] == a[3] == 0: running double sums) or its 16.16 fixed-point path for an
+ * 8-bit mask, its generic double-precision path for a 16-bit one - then min(line_depth[b][0][id], line_depth[b][1][partner id]) (ids >= 64 match nothing), 0 where that exceeds max_depth or
+ * nothing matches.  xy: B * (out_w + out_h) ints of workspace (the scale path's column / row tables, made by a launch of B blocks). */
+int y3d_kitti_depth_map(const unsigned char* const* mask, const unsigned char* const* mask2, const unsigned char* arena, const int64_t* mask_off,
+                        const double* draws, int draw_w, const unsigned char* wide, const int* hw, const int* flip, const double* trans_inv,
+                        const float* line_depth, int B, int out_h, int out_w, int max_side, double max_depth, int* xy, float* out,
+                        void* stream);
 /* Batch plan over a KITTI split held on the device (kitti_cache.hip, kitti.DeviceSplit), one thread per image: the per-image tables of
  * y3d_kitti_image_aug and y3d_kitti_encode_labels from the split's frame tables and one table of draws.  Frame tables, on the device,
  * indexed by dataset position (N frames): img_off (N) int64 byte offsets into arena (every frame (H, W, 3) uint8 RGB); frame_hw (N, 2)

@@ -17,7 +17,7 @@ import torch
 
 from . import ops
 from ._lib import Y3DError, lib
-from .resident import DrawRing, ResidentSplit, check_plan, epoch_indices, fill_arena, span_table, upload  # noqa: F401  (re-exported)
+from .resident import ALIGN, DrawRing, ResidentSplit, check_plan, epoch_indices, fill_arena, span_table, upload  # noqa: F401  (re-exported)
 
 # (h, w, l) per class, kitti.py:38-41
 CLS_MEAN_SIZE = ((1.52563191462, 1.62856739989, 3.88311640418), (1.76255119, 0.66068622, 0.84422524), (1.73698127, 0.59706367, 1.76282397))
@@ -377,6 +377,82 @@ def data_args(**over):
     return SimpleNamespace(**dict(DATA_ARGS, **over))
 
 
+# ------------------------------------------------------------------------------------------------------------------------------
+# foreground depth maps (`load_depth_maps`, data/datasets/kitti.py:54-56, 87-90, 143-145, 170-201, 286-287, 384-385, 409-417)
+# ------------------------------------------------------------------------------------------------------------------------------
+LINE_SLOTS = 64  # label lines per source in the per-line depth table (max_objs <= 64)
+
+
+def seg_path(data_dir, idx):
+    """the instance segmentation mask of frame `idx` of the split directory `data_dir` (<root>/training): under
+    <root>/deepseg/training/image_2 when that directory exists, else next to the images (kitti.py:54-56)"""
+    import os
+    deep = os.path.join(os.path.dirname(os.path.abspath(data_dir)), "deepseg", "training", "image_2")
+    return os.path.join(deep if os.path.exists(deep) else os.path.join(data_dir, "image_2"), f"{int(idx):06d}_seg.png")
+
+
+def read_seg(path, with_wide=False):
+    """A segmentation mask file -> (H, W) uint8: a pixel is the label-file line index of its object.  The file is read unchanged
+    (kitti.py:87-90, cv2.imread(..., -1)) and must hold a single channel of 8 or 16 bits; ids above 255 are stored as 255 (only ids
+    below max_objs can match a label line).  with_wide: -> (mask, whether the file holds 16 bits): Pillow warps a 16-bit image by
+    another code path than an 8-bit one, so the depth map kernel needs to know."""
+    import numpy as np
+    from PIL import Image
+    with Image.open(path) as im:
+        if im.mode not in ("L", "I;16", "I;16L", "I;16B"):
+            raise Y3DError(f"read_seg: {path} is a {im.mode} image; a mask has a single channel of 8 or 16 bits")
+        px = np.array(im)
+    if px.ndim != 2:
+        raise Y3DError(f"read_seg: {path} decodes to {px.shape}; a mask has a single channel")
+    px, wide = np.minimum(px, 255).astype(np.uint8), px.dtype.itemsize == 2
+    return (px, wide) if with_wide else px
+
+
+def _depth_map_launch(B, out_wh, max_depth, max_side, dev, **tables):
+    """the launch of `y3d_kitti_depth_map` shared by augment_depth_maps (mask pointers) and DeviceSplit (the mask arena)"""
+    W, H = int(out_wh[0]), int(out_wh[1])
+    out = torch.empty(B, H, W, dtype=torch.float32, device=dev)
+    xy = torch.empty(B, W + H, dtype=torch.int32, device=dev)
+    ptr = lambda k: tables[k].data_ptr() if tables.get(k) is not None else None
+    lib().kitti_depth_map(ptr("mask"), ptr("mask2"), ptr("arena"), ptr("mask_off"), ptr("draws"), int(tables.get("draw_w", 0)), ptr("wide"),
+                          ptr("hw"), ptr("flip"), ptr("trans_inv"), ptr("line_depth"), B, H, W, int(max_side), float(max_depth), xy.data_ptr(),
+                          out.data_ptr(), ops.stream())
+    return out
+
+
+def augment_depth_maps(masks, partners, flips, trans_inv, line_depth, out_wh=RESOLUTION, max_depth=120.0, wide=None):
+    """The foreground depth maps of a batch on the device (csrc/kitti_depth_map.hip), the counterpart of augment_images: `masks[b]` an
+    (h, w) uint8 device tensor (read_seg), `partners[b]` the mixup partner's or None, `flips[b]`, `trans_inv[b]` the (2, 3) crop matrix
+    of the image, `line_depth` (B, 2, 64) float32 on the device (encode_labels(..., depths=True): the depth each own / partner label
+    line paints, +inf for none).  Every mask is mirrored and warped as Pillow's Image.transform(AFFINE, NEAREST, fillcolor=51) does,
+    bit for bit; a pixel takes the smaller depth of its two objects, 0 where there is none or it exceeds max_depth.  wide: None (every
+    mask came from an 8-bit file) or per image (own, partner) flags of the masks read from 16-bit files (read_seg(..., with_wide=True)):
+    Pillow warps those by its generic double-precision path.  -> (B, H, W) float32 at out_wh = (W, H)."""
+    import numpy as np
+    B = len(masks)
+    if B == 0 or any((not t.is_cuda) or t.dtype != torch.uint8 or t.dim() != 2 for t in masks):
+        raise Y3DError("augment_depth_maps: masks must be (h, w) uint8 tensors on a HIP device")
+    dev = masks[0].device
+    masks = [t.contiguous() for t in masks]
+    parts = [None if q is None else q.contiguous() for q in partners]
+    for t, q in zip(masks, parts):
+        if q is not None and (q.shape != t.shape or q.dtype != torch.uint8 or not q.is_cuda):
+            raise Y3DError("augment_depth_maps: a mixup partner's mask must match its image's mask")
+    if not (torch.is_tensor(line_depth) and line_depth.is_cuda and line_depth.dtype == torch.float32
+            and tuple(line_depth.shape) == (B, 2, LINE_SLOTS) and line_depth.is_contiguous()):
+        raise Y3DError(f"augment_depth_maps: line_depth must be a contiguous ({B}, 2, {LINE_SLOTS}) float32 tensor on a HIP device")
+    if len(parts) != B or len(flips) != B or len(trans_inv) != B or (wide is not None and len(wide) != B):
+        raise Y3DError("augment_depth_maps: partners, flips, trans_inv and wide need one entry per mask")
+    wd = None if wide is None else torch.tensor([[int(bool(a)), int(bool(b))] for a, b in wide], dtype=torch.uint8).to(dev)
+    mask = torch.tensor([t.data_ptr() for t in masks], dtype=torch.int64).to(dev)
+    mask2 = torch.tensor([0 if q is None else q.data_ptr() for q in parts], dtype=torch.int64).to(dev) if any(q is not None for q in parts) else None
+    hw = torch.tensor([[t.shape[0], t.shape[1]] for t in masks], dtype=torch.int32).to(dev)
+    fl = torch.tensor([int(bool(f)) for f in flips], dtype=torch.int32).to(dev)
+    ti = torch.tensor(np.stack([np.asarray(t, np.float64).reshape(6) for t in trans_inv]), dtype=torch.float64).to(dev)
+    return _depth_map_launch(B, out_wh, max_depth, max(max(t.shape) for t in masks), dev, mask=mask, mask2=mask2, hw=hw, flip=fl, trans_inv=ti,
+                             line_depth=line_depth, wide=wd)
+
+
 def _level(box, trunc, occ):
     """kitti_utils.py Object3d.get_obj_level, from the label's own box"""
     height = float(box[3]) - float(box[1]) + 1
@@ -541,21 +617,26 @@ def _label_outputs(B, max_objs, dev):
             "ratio_pad": e(B, 2, 2, dt=torch.float64)}
 
 
-def encode_labels(packed, out_wh=RESOLUTION, min_depth=1.0, max_depth=120.0, use_camera_dis=False, max_objs=MAX_OBJS):
+def encode_labels(packed, out_wh=RESOLUTION, min_depth=1.0, max_depth=120.0, use_camera_dis=False, max_objs=MAX_OBJS, depths=False):
     """The label encoding of `KITTIDataset.__getitem__` + `collate_fn` for a packed batch (pack_labels), one HIP launch, no host
     synchronisation (capturable).  -> dict of the per-box keys in a static layout: image b owns rows [b * max_objs, b * max_objs + count);
     unused rows have batch_idx = -1 (skipped by pad_targets) and zeros elsewhere; plus `counts` (B,) int32, `calib` (B, 6) float64,
-    `ratio_pad` (B, 2, 2) float64."""
+    `ratio_pad` (B, 2, 2) float64.  depths: the same launch also writes `line_depth` (B, 2, 64) float32, the depth every own /
+    partner label line paints into the foreground depth map (+inf: dropped or absent), what `augment_depth_maps` takes."""
     img_i = packed["img_i"]
     if not img_i.is_cuda or any(not packed[k].is_cuda for k in ("rec", "img_f", "mean_size")):
         raise Y3DError("encode_labels: the packed labels must live on a HIP device (no host fallback)")
     B = img_i.shape[0]
     o = _label_outputs(B, max_objs, img_i.device)
     ms = packed["mean_size"]
-    lib().kitti_encode_labels(packed["rec"].data_ptr(), img_i.data_ptr(), packed["img_f"].data_ptr(), B, int(out_wh[0]), int(out_wh[1]),
-                              float(min_depth), float(max_depth), int(bool(use_camera_dis)), ms.data_ptr(), ms.shape[0], int(max_objs),
-                              *[o[k].data_ptr() for k in PER_BOX], o["counts"].data_ptr(), o["calib"].data_ptr(), o["ratio_pad"].data_ptr(),
-                              ops.stream())
+    a = (packed["rec"].data_ptr(), img_i.data_ptr(), packed["img_f"].data_ptr(), B, int(out_wh[0]), int(out_wh[1]), float(min_depth),
+         float(max_depth), int(bool(use_camera_dis)), ms.data_ptr(), ms.shape[0], int(max_objs), *[o[k].data_ptr() for k in PER_BOX],
+         o["counts"].data_ptr(), o["calib"].data_ptr(), o["ratio_pad"].data_ptr())
+    if depths:
+        o["line_depth"] = torch.empty(B, 2, LINE_SLOTS, dtype=torch.float32, device=img_i.device)
+        lib().kitti_encode_labels_depths(*a, o["line_depth"].data_ptr(), ops.stream())
+    else:
+        lib().kitti_encode_labels(*a, ops.stream())
     return o
 
 
@@ -608,9 +689,10 @@ def _split(root_or_split_file, mode):
     return data, ids
 
 
-def _batch(img, lab, ids, sizes, draws, mean_size, mixed, compact):
+def _batch(img, lab, ids, sizes, draws, mean_size, mixed, compact, depth_map=None):
     """The dictionary every 3D builder returns (json3d's too): the images, encode_labels' `lab`, and per image its id, its original
-    (W, H) and its draws.  compact: false for the per-box keys in the static layout, or counts (host ints) -> the ragged ones."""
+    (W, H) and its draws.  compact: false for the per-box keys in the static layout, or counts (host ints) -> the ragged ones.
+    depth_map: the KITTI builders' (B, H, W) float32 foreground depth maps under `load_depth_maps` (no key without)."""
     import numpy as np
     batch = {"img": img, "calib": lab["calib"],
              "info": [{"img_id": i, "img_size": np.array(s), "trans_inv": d["trans_inv"]} for i, s, d in zip(ids, sizes, draws)],
@@ -621,6 +703,8 @@ def _batch(img, lab, ids, sizes, draws, mean_size, mixed, compact):
         del batch["counts"]
     else:
         batch.update({k: lab[k] for k in PER_BOX})
+    if depth_map is not None:
+        batch["depth_map"] = depth_map
     return batch
 
 
@@ -635,8 +719,9 @@ def _resident_tail(split, plan, args, cam_dis, img_mode, resolution, encode, **p
         img = torch.empty(B, H, W, 3, dtype=torch.uint8, device=split.device)
     lib().kitti_image_aug(plan["src"].data_ptr(), plan["src2"].data_ptr(), plan["hw"].data_ptr(), plan["flip"].data_ptr(),
                           plan["trans_inv"].data_ptr(), B, H, W, 0 if img_mode == "float" else 1, img.data_ptr(), ops.stream())
+    encode_kw = packed.pop("encode_kw", {})
     packed = dict(rec=split.rec, img_i=plan["img_i"], img_f=plan["img_f"], mean_size=split.mean_size, **packed)
-    return img, encode(packed, resolution, args.min_depth_threshold, args.max_depth_threshold, cam_dis, MAX_OBJS)
+    return img, encode(packed, resolution, args.min_depth_threshold, args.max_depth_threshold, cam_dis, MAX_OBJS, **encode_kw)
 
 
 def build_batch(root_or_split_file, indices, args, device, mode="train", compact=False, img_mode="uint8", resolution=RESOLUTION):
@@ -653,14 +738,17 @@ def build_batch(root_or_split_file, indices, args, device, mode="train", compact
     if isinstance(root_or_split_file, DeviceSplit):  # the split is resident on the device: no file is touched
         root_or_split_file.check_device(device)
         return root_or_split_file.build_batch(indices, args, mode=mode, compact=compact, img_mode=img_mode, resolution=resolution)
-    if getattr(args, "load_depth_maps", False):
-        raise Y3DError("build_batch: depth maps (load_depth_maps) are not supported")
+    depth = bool(getattr(args, "load_depth_maps", False))
     if torch.device(device).type != "cuda":
         raise Y3DError("build_batch: the batch is built on a HIP device (no host fallback)")
     if mode == "test":
         raise Y3DError("build_batch: the test split has no labels")
     data, ids = _split(root_or_split_file, mode)
     path = lambda sub, i, ext: os.path.join(data, sub, f"{i:06d}.{ext}")
+    if depth:  # the batch's own masks before anything is decoded (a partner's once it is drawn)
+        for pos in indices:
+            if not os.path.exists(seg_path(data, ids[pos])):
+                raise Y3DError(f"build_batch: load_depth_maps: frame {ids[pos]:06d} has no segmentation mask ({seg_path(data, ids[pos])})")
     calib_cache, label_cache = {}, {}
 
     def calib(i):
@@ -699,10 +787,27 @@ def build_batch(root_or_split_file, indices, args, device, mode="train", compact
         partners.append(label(ids[d["partner"]]) if d["mixed"] else None)
     packed = pack_labels(labels, partners, P2s, [d["trans"] for d in draws], [d["flip"] for d in draws], [d["scale"] for d in draws],
                          [im.size for im in frames], device)
-    lab = encode_labels(packed, resolution, args.min_depth_threshold, args.max_depth_threshold, bool(args.cam_dis), MAX_OBJS)
+    lab = encode_labels(packed, resolution, args.min_depth_threshold, args.max_depth_threshold, bool(args.cam_dis), MAX_OBJS, depths=depth)
     mixed = torch.tensor([int(d["mixed"]) for d in draws], dtype=torch.uint8).to(device)
+    depth_map = None
+    if depth:  # the masks of the frames and of their partners (kitti.py:125-126, 170-171), warped with the images' matrices
+        def mask(pos, size):
+            f = seg_path(data, ids[pos])
+            if not os.path.exists(f):
+                raise Y3DError(f"build_batch: load_depth_maps: frame {ids[pos]:06d} has no segmentation mask ({f})")
+            px, wide = read_seg(f, with_wide=True)
+            if px.shape != (size[1], size[0]):
+                raise Y3DError(f"build_batch: load_depth_maps: the mask of frame {ids[pos]:06d} is {px.shape[1]} x {px.shape[0]}, "
+                               f"its image {size[0]} x {size[1]}")
+            return torch.from_numpy(px).to(device), wide
+
+        masks = [mask(pos, im.size) for pos, im in zip(indices, frames)]
+        pmasks = [mask(d["partner"], im.size) if d["mixed"] else (None, False) for d, im in zip(draws, frames)]
+        depth_map = augment_depth_maps([m for m, _ in masks], [m for m, _ in pmasks], [d["flip"] for d in draws],
+                                       [d["trans_inv"] for d in draws], lab["line_depth"], resolution, args.max_depth_threshold,
+                                       wide=[(a[1], b[1]) for a, b in zip(masks, pmasks)])
     return _batch(img, lab, [ids[p] for p in indices], [im.size for im in frames], draws, packed["mean_size"], mixed,
-                  compact and (lambda counts: compact_labels(lab, counts, [d["crop"] for d in draws], bool(args.cam_dis))))
+                  compact and (lambda counts: compact_labels(lab, counts, [d["crop"] for d in draws], bool(args.cam_dis))), depth_map)
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
@@ -751,7 +856,7 @@ class DeviceSplit(ResidentSplit):
     `frame_info` knows every frame's true size, as the reference's dataset does; the path-based builder knows those of the batch's own
     frames only, so the two draw the same mixup partners when frames that share a calibration share a size."""
 
-    def __init__(self, root_or_split_file, mode="train", device="cuda", max_bytes=None, workers=8):
+    def __init__(self, root_or_split_file, mode="train", device="cuda", max_bytes=None, workers=8, load_depth_maps=False):
         import os
         import numpy as np
         from concurrent.futures import ThreadPoolExecutor
@@ -760,7 +865,23 @@ class DeviceSplit(ResidentSplit):
         self.data, self.ids = _split(root_or_split_file, mode)
         path = lambda sub, i, ext: os.path.join(self.data, sub, f"{i:06d}.{ext}")
         # sizes from the PNG headers, the budget before anything is decoded or allocated
-        self._layout(dev, self._sizes([path("image_2", i, "png") for i in self.ids]), max_bytes)
+        hw = self._sizes([path("image_2", i, "png") for i in self.ids])
+        self.load_depth_maps = bool(load_depth_maps)
+        if self.load_depth_maps:  # a second arena, one byte per pixel of every frame's mask: both arenas share the budget
+            px = np.asarray(hw, np.int64).reshape(-1, 2).prod(1)
+            self._mask_padded = (px + ALIGN - 1) // ALIGN * ALIGN
+            self.mask_offsets = np.concatenate(([0], np.cumsum(self._mask_padded)[:-1])).astype(np.int64)
+            self.mask_nbytes = int(self._mask_padded.sum())
+            frames = int(((px * 3 + ALIGN - 1) // ALIGN * ALIGN).sum())
+            allowed = int(max_bytes) if max_bytes is not None else torch.cuda.mem_get_info(dev)[0] // 2
+            if frames + self.mask_nbytes > allowed:
+                raise Y3DError(f"DeviceSplit: the {len(hw)} decoded frames and their masks need {frames} + {self.mask_nbytes} bytes, "
+                               f"{allowed} bytes are allowed (max_bytes)")
+            missing = [i for i in self.ids if not os.path.exists(seg_path(self.data, i))]
+            if missing:
+                raise Y3DError(f"DeviceSplit: load_depth_maps: frame {missing[0]:06d} has no segmentation mask "
+                               f"({seg_path(self.data, missing[0])}); {len(missing)} of {len(self.ids)} frames lack one")
+        self._layout(dev, hw, max_bytes)
 
         # labels and calibrations, both projections of every frame
         def tables(pos):
@@ -781,6 +902,30 @@ class DeviceSplit(ResidentSplit):
                 return np.array(im.convert("RGB"))
 
         self._fill(span_table(self.n_lines), decode, lambda pos: f"frame {self.ids[pos]:06d}", workers, _DRAW_W)
+        if self.load_depth_maps:
+            self._fill_masks(workers)
+
+    def _fill_masks(self, workers):
+        """every frame's mask (read_seg) into `mask_arena`, one byte per pixel at `mask_offsets` (multiples of 16), `mask_off`, the
+        offsets on the device, and `mask_wide` (N) uint8, the frames whose mask file holds 16 bits; a mask of another size than its
+        frame is refused"""
+        import numpy as np
+        from concurrent.futures import ThreadPoolExecutor
+        wide = np.zeros(len(self.ids), np.uint8)
+
+        def decode(pos):
+            px, wide[pos] = read_seg(seg_path(self.data, self.ids[pos]), with_wide=True)
+            h, w = int(self._hw[pos][0]), int(self._hw[pos][1])
+            if px.shape != (h, w):
+                raise Y3DError(f"DeviceSplit: load_depth_maps: the mask of frame {self.ids[pos]:06d} is {px.shape[1]} x {px.shape[0]}, "
+                               f"its image {w} x {h}")
+            return px
+
+        self.mask_arena = torch.empty(self.mask_nbytes, dtype=torch.uint8, device=self.device)
+        self.mask_off = upload(self.mask_offsets, self.device, torch.int64)
+        with ThreadPoolExecutor(max_workers=min(int(workers), 16)) as pool:
+            fill_arena(self.mask_arena, self.mask_offsets, self._mask_padded, decode, pool, self.CHUNK)
+        self.mask_wide = upload(wide, self.device, torch.uint8)
 
     def __len__(self):
         return len(self.ids)
@@ -792,8 +937,10 @@ class DeviceSplit(ResidentSplit):
     def build_batch(self, indices, args, mode="train", compact=False, img_mode="uint8", resolution=RESOLUTION):
         """`build_batch(path, indices, args, device, ...)` from the resident split: the same dictionary, bit for bit.  With compact=False
         nothing here waits for the device (but a ring buffer still in flight) and no file is opened."""
-        if getattr(args, "load_depth_maps", False):
-            raise Y3DError("build_batch: depth maps (load_depth_maps) are not supported")
+        depth = bool(getattr(args, "load_depth_maps", False))
+        if depth and not self.load_depth_maps:
+            raise Y3DError("build_batch: depth maps (load_depth_maps): this resident split holds no segmentation masks; build it with "
+                           "DeviceSplit(..., load_depth_maps=True)")
         if mode == "test":
             raise Y3DError("build_batch: the test split has no labels")
         indices = [int(i) for i in indices]
@@ -808,9 +955,15 @@ class DeviceSplit(ResidentSplit):
         with torch.cuda.device(self.device):
             host, dev = self._ring.upload(draw_table(indices, draws))
             plan = plan_batch(self, host, dev)
-            img, lab = _resident_tail(self, plan, args, cam_dis, img_mode, resolution, encode_labels)
+            img, lab = _resident_tail(self, plan, args, cam_dis, img_mode, resolution, encode_labels,
+                                      **({"encode_kw": {"depths": True}} if depth else {}))
+            depth_map = None
+            if depth:  # the masks' addresses come from the arena offsets and the draw table's position / partner columns
+                depth_map = _depth_map_launch(B, resolution, args.max_depth_threshold, int(self._hw.max()), self.device, arena=self.mask_arena,
+                                              mask_off=self.mask_off, wide=self.mask_wide, draws=dev, draw_w=_DRAW_W, hw=plan["hw"], flip=plan["flip"],
+                                              trans_inv=plan["trans_inv"], line_depth=lab["line_depth"])
         return _batch(img, lab, [self.ids[p] for p in indices], [self.wh[p] for p in indices], draws, self.mean_size, plan["mixed"],
-                      compact and (lambda counts: compact_labels(lab, counts, [d["crop"] for d in draws], cam_dis)))
+                      compact and (lambda counts: compact_labels(lab, counts, [d["crop"] for d in draws], cam_dis)), depth_map)
 
 
 def save_results(results, output_dir="./outputs", class_name=("Car", "Pedestrian", "Cyclist")):

@@ -255,6 +255,92 @@ class DistillFn(torch.autograd.Function):
         return (None, *grads)
 
 
+class FgdmLossFn(torch.autograd.Function):
+    """utils/loss.py:1299-1324 on the HIP kernel of csrc/fgdm_loss.hip.  apply(logits, depth_maps, cfg) -> loss (0-dim fp32);
+    cfg = (num_bins, dmin, dmax, alpha, gamma, fg_weight, bg_weight).  The forward launch also writes d loss / d logits in the logits'
+    dtype and layout (no softmax tensor is kept); the backward multiplies it by the incoming scalar on the device.  After a forward
+    `FgdmLossFn.last_targets` holds the (B, h, w) int32 class of every cell (for tests and tools)."""
+
+    last_targets = None
+
+    @staticmethod
+    def forward(ctx, logits, depth_maps, cfg):
+        num_bins, dmin, dmax, alpha, gamma, fgw, bgw = cfg
+        if not (torch.is_tensor(logits) and logits.dim() == 4 and torch.is_tensor(depth_maps) and depth_maps.dim() == 3):
+            raise ValueError("ForegroundDepthMapLoss: depth_logits must be (B, num_bins + 1, h, w) and depth_maps (B, H, W)")
+        if not logits.is_cuda:
+            raise Y3DError("ForegroundDepthMapLoss runs on the HIP kernel of fgdm_loss.hip: the logits must live on a HIP device (no CPU fallback)")
+        if logits.dtype not in (torch.float32, torch.bfloat16):
+            raise Y3DError(f"ForegroundDepthMapLoss: logits must be float32 or bfloat16 (got {logits.dtype})")
+        if not depth_maps.is_floating_point():
+            raise ValueError(f"ForegroundDepthMapLoss: depth_maps must be a floating-point tensor (got {depth_maps.dtype})")
+        B, C, h, w = logits.shape
+        if C != num_bins + 1:
+            raise ValueError(f"ForegroundDepthMapLoss: the logits have {C} channels, num_bins + 1 = {num_bins + 1} are needed")
+        H, W = depth_maps.shape[1:]
+        if depth_maps.shape[0] != B or (h, w) != (H // 16, W // 16) or h < 1 or w < 1:
+            raise ValueError(f"ForegroundDepthMapLoss: logits of {B} x {h} x {w} cells do not match depth maps {tuple(depth_maps.shape)}: "
+                             "the grid must be (H // 16, W // 16)")
+        if depth_maps.device != logits.device:
+            raise ValueError(f"ForegroundDepthMapLoss: the depth maps live on {depth_maps.device}, the logits on {logits.device}")
+        z = logits.detach()
+        if not (z.is_contiguous() or z.is_contiguous(memory_format=torch.channels_last)):
+            z = z.contiguous()
+        dm = depth_maps.detach()
+        if dm.dtype not in (torch.float32, torch.float64):
+            dm = dm.float()  # half and bfloat16 values are float32 values
+        dm = dm.contiguous()
+        dev = z.device
+        L = lib()
+        grad = torch.empty_like(z)  # dense: the logits' strides
+        part = torch.empty(L.fgdm_loss_blocks(B, h, w), dtype=torch.float32, device=dev)
+        item = torch.empty(1, dtype=torch.float32, device=dev)
+        tgt = torch.empty(B, h, w, dtype=torch.int32, device=dev)
+        L.fgdm_loss(ops.code(z.dtype), z.data_ptr(), *z.stride(), int(dm.dtype == torch.float64), dm.data_ptr(), B, H, W, h, w, num_bins,
+                    float(dmin), float(dmax), float(alpha), float(gamma), float(fgw), float(bgw), grad.data_ptr(), part.data_ptr(),
+                    item.data_ptr(), tgt.data_ptr(), ops.stream())
+        FgdmLossFn.last_targets = tgt
+        ctx.grad = grad
+        return item.reshape(())
+
+    @staticmethod
+    def backward(ctx, d):
+        if d is None:
+            return None, None, None
+        g = ctx.grad
+        scale = d.detach().float().reshape(1).contiguous()
+        out = torch.empty_like(g)
+        lib().fgdm_scale(ops.code(g.dtype), g.data_ptr(), scale.data_ptr(), out.data_ptr(), g.numel(), ops.stream())
+        return out, None, None
+
+
+class ForegroundDepthMapLoss:
+    """utils/loss.py:1225-1324: focal classification of depth logits (B, num_bins + 1, H // 16, W // 16) against the LID bins of the
+    foreground depth maps (B, H, W) (`batch["depth_map"]` of the KITTI builders under `load_depth_maps`), foreground cells weighted
+    `fg_weight`, background cells `bg_weight`, mean over cells.  `model_or_args`: a model (its `.args`) or the args themselves;
+    `min_depth_threshold` / `max_depth_threshold` are the bin range.  The logits are supplied by the caller: the DepthPredictor that
+    makes them in the reference and the `fgdm_loss_weight` / loss_names wiring are not part of this package yet."""
+
+    def __init__(self, model_or_args, alpha=0.25, gamma=2.0, fg_weight=13, bg_weight=1, num_bins=80):
+        args = getattr(model_or_args, "args", model_or_args)
+        self.args = args
+        self.num_bins = int(num_bins)
+        if not 1 <= self.num_bins <= 255:
+            raise ValueError(f"ForegroundDepthMapLoss: num_bins must be in 1..255 (got {num_bins})")
+        self.alpha, self.gamma, self.fg_weight, self.bg_weight = float(alpha), float(gamma), float(fg_weight), float(bg_weight)
+        if not (self.gamma == 0.0 or self.gamma >= 1.0):
+            raise ValueError(f"ForegroundDepthMapLoss: gamma must be 0 or >= 1 (got {gamma})")
+        self.dmin, self.dmax = float(args.min_depth_threshold), float(args.max_depth_threshold)
+        if not self.dmax > self.dmin:
+            raise ValueError("ForegroundDepthMapLoss: max_depth_threshold must exceed min_depth_threshold")
+
+    def __call__(self, depth_logits, depth_maps):
+        cfg = (self.num_bins, self.dmin, self.dmax, self.alpha, self.gamma, self.fg_weight, self.bg_weight)
+        return FgdmLossFn.apply(depth_logits, depth_maps, cfg)
+
+    forward = __call__
+
+
 def loss_names(args):
     """models/yolov10_3D/train.py:33-39: names of the loss items DetectLoss3d returns, one-to-many set first"""
     om = ["box_om", "cls_om", "dep_om", "o3d_om", "s3d_om", "hd_om"]
