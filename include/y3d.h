@@ -854,6 +854,45 @@ int y3d_mt_sgd_tab(const int64_t* param_ptrs, const int64_t* grad_ptrs, const in
 int y3d_mt_ema(const int64_t* ema_ptrs, const int64_t* model_ptrs, const int64_t* sizes, const int* reps, const int* chunk_tensor,
                const int* chunk_off, int nchunks, int chunk, float decay, float one_minus_decay, const float* guard, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Depth predictor of the 3D head (nn/modules/head.py:978-1042 DepthPredictor), group_norm.hip / resize.hip
+ * ---------------------------------------------------------------------------------------------- */
+/* nn.GroupNorm(32, 128) over a conv's raw output y (written WITHOUT the conv bias): x = y + bconv[c], xhat = (x - mean[b,g]) * rstd[b,g],
+ * z = xhat * gamma[c] + beta[c]; out = act(scale * sum_{i < nsrc} z_i), nsrc 1 or 3 (head.py:1027: the three-branch average), relu 0 / 1.
+ * Only C = 128, G = 32 is built.  y / ysw / bconv / gamma / beta / dy / dysw: HOST arrays of nsrc device pointers / pixel strides; every
+ * map is B * HW pixels at its pixel stride (elements), 16-byte aligned.  A chunk is 256 pixels of one sample:
+ *   y3d_gn_stats      partials [nsrc][B][y3d_gn_chunks(HW)][G][2] = (mean, M2) of every chunk, two passes over it
+ *   y3d_gn_apply      folds them per sample in chunk order (Chan's merge) in its prologue, writes out and stats [nsrc][B][G][2] = (mean, rstd)
+ *   y3d_gn_bwd_reduce partials [B][chunks][2 nsrc + 1][C] = per channel sum dzh xhat_i | sum xhat_i | sum dzh, dzh = dz * scale * mask (the
+ *                     ReLU mask recomputed from y, bconv and stats)
+ *   y3d_gn_bwd_apply  dy_i = rstd (dzh gamma - (s1 + xhat s2) / n) in `dtype`, and dgamma / dbeta / dbconv [nsrc][C] (fp32) folded over
+ *                     samples and chunks in a fixed order.  No float atomics anywhere: the same bits on every run. */
+int y3d_gn_chunks(int HW);
+int y3d_gn_stats(int dtype, int nsrc, const void* const* y, const int64_t* ysw, const float* const* bconv, int B, int HW, int C, int G,
+                 float* partials, void* stream);
+int y3d_gn_apply(int dtype, int nsrc, const void* const* y, const int64_t* ysw, const float* const* bconv, const float* const* gamma,
+                 const float* const* beta, const float* partials, float eps, float scale, int relu, void* out, int64_t osw, float* stats, int B,
+                 int HW, int C, int G, void* stream);
+int y3d_gn_bwd_reduce(int dtype, int nsrc, const void* const* y, const int64_t* ysw, const float* const* bconv, const float* const* gamma,
+                      const float* const* beta, const float* stats, float scale, int relu, const void* dz, int64_t dsw, float* partials, int B,
+                      int HW, int C, int G, void* stream);
+int y3d_gn_bwd_apply(int dtype, int nsrc, const void* const* y, const int64_t* ysw, const float* const* bconv, const float* const* gamma,
+                     const float* const* beta, const float* stats, float scale, int relu, const void* dz, int64_t dsw, const float* partials,
+                     void* const* dy, const int64_t* dysw, float* dgamma, float* dbeta, float* dbconv, int B, int HW, int C, int G, void* stream);
+/* F.interpolate(x, size=(Ho, Wo), mode="bilinear", align_corners=False) over an NHWC map and its adjoint (a gather in a fixed order, no
+ * atomics); C % 8 == 0; y, dy and dx are pixel-dense at their pixel strides */
+int y3d_resize_bilinear_fwd(int dtype, const void* x, int64_t xsb, int64_t xsh, int64_t xsw, void* y, int64_t ysw, int B, int H, int W, int Ho,
+                            int Wo, int C, void* stream);
+int y3d_resize_bilinear_bwd(int dtype, const void* dy, int64_t dsw, void* dx, int64_t xsw, int B, int H, int W, int Ho, int Wo, int C,
+                            void* stream);
+/* out[c] = sum over M pixels of x[p][c] (fp32), C <= 256 in whole 16-byte chunks: per-block partials [y3d_colsum_blocks(M)][C], then one
+ * fold in block order (the depth classifier's bias gradient) */
+int y3d_colsum_blocks(int64_t M);
+int y3d_colsum(int dtype, const void* x, int64_t xsw, int64_t M, int C, float* partials, float* out, void* stream);
+/* out[cell] = sum_c softmax(logits[cell])_c * bins[c] (head.py:1036-1037 weighted_depth), fp32, one thread per cell; the logits' rows
+ * (pixel stride sw) hold the C channels in whole 16-byte chunks */
+int y3d_depth_expect(int dtype, const void* logits, int64_t sw, int64_t M, int C, const float* bins, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

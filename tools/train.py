@@ -52,6 +52,8 @@ def parser():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--max-norm", type=float, default=10.0)
     ap.add_argument("--htl", action="store_true", help="3D models: hierarchical task learning (cfg/default.yaml:121), weights kept on the device")
+    ap.add_argument("--fgdm", action="store_true", help="3D KITTI models: train the head's depth predictor on the foreground depth maps "
+                    "(sets fgdm_predictor, fgdm_loss and load_depth_maps; the split needs its segmentation masks)")
     ap.add_argument("--resume", help="a last.pt of this trainer: continue at its epoch + 1")
     return ap
 
@@ -61,6 +63,10 @@ def main(argv=None):
     y3d.set_compute_dtype(torch.bfloat16 if a.dtype == "bf16" else torch.float32)
     cfg = y3d.yaml_model_load(a.model)
     is3d = any(row[2] == "v10Detect3d" for row in cfg["head"])
+    if a.fgdm:
+        if not is3d or a.dataset != "kitti":
+            raise SystemExit("--fgdm: the foreground depth maps exist for 3D models on KITTI only")
+        cfg["fgdm_predictor"] = True
     torch.manual_seed(a.seed)
     model = (y3d.YOLOv10_3DDetectionModel if is3d else y3d.YOLOv10DetectionModel)(cfg, nc=a.nc)
     if a.weights:
@@ -70,10 +76,13 @@ def main(argv=None):
         got, own = model.load(ck)
         print(f"loaded {got} of {own} tensors from {a.weights}")
     model = model.to("cuda").train()
+    if a.fgdm:
+        model.args.fgdm_loss = True
     validator = None
     if is3d:
         if a.dataset == "kitti":
-            split, data_args = kitti.DeviceSplit(a.data, mode="train"), kitti.data_args()
+            split = kitti.DeviceSplit(a.data, mode="train", load_depth_maps=a.fgdm)
+            data_args = kitti.data_args(load_depth_maps=True) if a.fgdm else kitti.data_args()
             vsrc = a.val or (a.data if os.path.isdir(a.data) else None)
             vsplit = kitti.DeviceSplit(vsrc, mode="val") if vsrc else None
         else:

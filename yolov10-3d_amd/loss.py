@@ -284,15 +284,19 @@ class FgdmLossFn(torch.autograd.Function):
         if depth_maps.device != logits.device:
             raise ValueError(f"ForegroundDepthMapLoss: the depth maps live on {depth_maps.device}, the logits on {logits.device}")
         z = logits.detach()
-        if not (z.is_contiguous() or z.is_contiguous(memory_format=torch.channels_last)):
-            z = z.contiguous()
+        dense = z.is_contiguous() or z.is_contiguous(memory_format=torch.channels_last)
+        # a channel slice of a wider pixel-dense NHWC buffer (the depth classifier's 81 of 88 columns) is read where it lies
+        sliced = not dense and ops.is_nhwc(z) and ops.px_dense(z) and z.data_ptr() % 16 == 0
+        if not (dense or sliced):
+            z, dense = z.contiguous(), True
         dm = depth_maps.detach()
         if dm.dtype not in (torch.float32, torch.float64):
             dm = dm.float()  # half and bfloat16 values are float32 values
         dm = dm.contiguous()
         dev = z.device
         L = lib()
-        grad = torch.empty_like(z)  # dense: the logits' strides
+        # the logits' strides (the kernel writes the gradient where it read the logit); a slice's gaps are never read
+        grad = torch.empty_like(z) if dense else torch.empty_strided(z.shape, z.stride(), dtype=z.dtype, device=dev)
         part = torch.empty(L.fgdm_loss_blocks(B, h, w), dtype=torch.float32, device=dev)
         item = torch.empty(1, dtype=torch.float32, device=dev)
         tgt = torch.empty(B, h, w, dtype=torch.int32, device=dev)
@@ -309,8 +313,12 @@ class FgdmLossFn(torch.autograd.Function):
             return None, None, None
         g = ctx.grad
         scale = d.detach().float().reshape(1).contiguous()
-        out = torch.empty_like(g)
-        lib().fgdm_scale(ops.code(g.dtype), g.data_ptr(), scale.data_ptr(), out.data_ptr(), g.numel(), ops.stream())
+        if g.is_contiguous() or g.is_contiguous(memory_format=torch.channels_last):
+            out, n = torch.empty_like(g), g.numel()
+        else:  # a slice's layout: every element from the first to the last, the gaps with them
+            out = torch.empty_strided(g.shape, g.stride(), dtype=g.dtype, device=g.device)
+            n = sum((s - 1) * st for s, st in zip(g.shape, g.stride())) + 1
+        lib().fgdm_scale(ops.code(g.dtype), g.data_ptr(), scale.data_ptr(), out.data_ptr(), n, ops.stream())
         return out, None, None
 
 
@@ -319,7 +327,8 @@ class ForegroundDepthMapLoss:
     foreground depth maps (B, H, W) (`batch["depth_map"]` of the KITTI builders under `load_depth_maps`), foreground cells weighted
     `fg_weight`, background cells `bg_weight`, mean over cells.  `model_or_args`: a model (its `.args`) or the args themselves;
     `min_depth_threshold` / `max_depth_threshold` are the bin range.  The logits are supplied by the caller: the DepthPredictor that
-    makes them in the reference and the `fgdm_loss_weight` / loss_names wiring are not part of this package yet."""
+    makes them is modules.DepthPredictor (`v10Detect3d(fgdm_predictor=True)`), and DetectLoss3d adds this loss times `fgdm_loss_weight`
+    as its 13th item under `fgdm_loss`."""
 
     def __init__(self, model_or_args, alpha=0.25, gamma=2.0, fg_weight=13, bg_weight=1, num_bins=80):
         args = getattr(model_or_args, "args", model_or_args)
@@ -347,7 +356,10 @@ def loss_names(args):
     oo = ["box_oo", "cls_oo", "dep_oo", "o3d_oo", "s3d_oo", "hd_oo"]
     if getattr(args, "distillation", False):
         om, oo = om + ["dis_om"], oo + ["dis_oo"]
-    return om + oo
+    names = om + oo
+    if getattr(args, "fgdm_loss", False):
+        names = names + ["fgdm"]  # models/yolov10_3D/train.py:41-42
+    return names
 
 
 def _loss3d_set(cfg, gt, n_used, calib, mean_sizes, map_ptrs, psw, grad_ptrs, gsw, Hs, Ws, B, dtype, dev):
@@ -594,9 +606,47 @@ class DetectLoss3d:
     def __init__(self, model):
         self.one2many = DDDetectionLoss(model, tal_topk=model.args.tal_topk)
         self.one2one = DDDetectionLoss(model, tal_topk=1)
+        # auxiliary depth supervision (loss.py:745-748, 757-767): ForegroundDepthMapLoss over the head's DepthPredictor logits
+        args = model.args
+        if getattr(args, "fgdm_supervision", False):
+            raise NotImplementedError("fgdm_supervision: SupervisionLoss.forward_fgdm needs the DINOv2 teacher, which is not part of this "
+                                      "package; set fgdm_supervision: False (fgdm_loss alone trains the depth predictor)")
+        self.fgdm = None
+        if getattr(args, "fgdm_loss", False):
+            if not getattr(model.model[-1], "fgdm_pred", False):
+                raise Y3DError("fgdm_loss: the head has no depth predictor; build the model with `fgdm_predictor: True` in the head's yaml "
+                               "arguments (v10Detect3d(fgdm_predictor=True)) or set fgdm_loss: False")
+            if not hasattr(args, "min_depth_threshold"):
+                args.min_depth_threshold, args.max_depth_threshold = 1, 120  # cfg/default.yaml:123-124
+            self.fgdm = ForegroundDepthMapLoss(model)
+            self.fgdm_weight = float(getattr(args, "fgdm_loss_weight", 2))
+
+    def _depth_pair(self, preds, batch):
+        """(depth logits, depth maps) of a step under fgdm_loss, checked before any launch"""
+        if "depth_map" not in batch:
+            raise Y3DError('fgdm_loss: the batch has no "depth_map"; build it with load_depth_maps=True in the data args (kitti.data_args) '
+                           "and, for a resident split, DeviceSplit(..., load_depth_maps=True)")
+        dm = preds.get("depth_maps")
+        if not isinstance(dm, (tuple, list)):
+            raise Y3DError("fgdm_loss: the head returned no depth logits; build it with fgdm_predictor=True")
+        return dm[0], batch["depth_map"].to(dm[0].device)
+
+    def __call__(self, preds, batch):
+        """loss.py:750-771: the two head sets, and under fgdm_loss the depth predictor's loss times fgdm_loss_weight - NOT times the batch
+        size, unlike the two head-set totals - appended as the last item"""
+        if self.fgdm is None:
+            return self._head_sets(preds, batch)
+        pair = self._depth_pair(preds, batch) if preds.get("one2many", None) else None
+        total, items = self._head_sets(preds, batch)
+        if pair is None:
+            return total, items
+        f = self.fgdm(*pair) * self.fgdm_weight
+        return total + f, torch.cat((items, f.detach().reshape(1)))
 
     def set_item_weights(self, table):
         """`table`: 12 device floats, the one-to-many set's six first (`loss_names`), or None; see DDDetectionLoss.set_item_weights"""
+        if table is not None and self.fgdm is not None:
+            raise NotImplementedError("item weights (htl) with fgdm_loss: 12 weights for 13 items")
         if table is not None and not (torch.is_tensor(table) and table.numel() == 12 and table.dim() == 1):
             raise Y3DError("set_item_weights: a 1-D tensor of 12 values")
         self.one2many.set_item_weights(None if table is None else table[0:6])
@@ -627,7 +677,7 @@ class DetectLoss3d:
                 return None
         return slots
 
-    def __call__(self, preds, batch):
+    def _head_sets(self, preds, batch):
         o2o = preds["one2one"][1] if isinstance(preds["one2one"], tuple) else preds["one2one"]
         dev = o2o[0].device
         B, (H, W) = o2o[0].shape[0], o2o[0].shape[2:]

@@ -479,13 +479,85 @@ class HeadLevelPlan(NamedTuple):
             yield part.stack
 
 
+class DepthPredictor(nn.Module):
+    """reference head.py:978-1042 (adapted there from MonoDETR): the auxiliary depth-bin predictor of the `fgdm` switch.  Reads the
+    three neck maps (P3, P4, P5) and predicts 80 LID depth bins + 1 per stride-16 cell:
+      downsample  Conv2d(ch[0], 128, 3, s 2, p 1) + GroupNorm(32, 128) on P3
+      proj        Conv2d(ch[1], 128, 1)           + GroupNorm(32, 128) on P4
+      upsample    Conv2d(ch[2], 128, 1)           + GroupNorm(32, 128) on P5 brought to P4's size bilinearly
+      src = mean of the three; depth_head = 2 x [Conv2d(128, 128, 3, p 1), GroupNorm, ReLU]; depth_classifier = Conv2d(128, 81, 1).
+    Same attribute names, parameter order, state_dict keys and initialisation draws as the reference: its checkpoints load strictly.
+    The forward is five autograd functions over the HIP kernels of csrc/group_norm.hip / resize.hip and the conv entry points
+    (ops.ConvGroupNormFn x 3, ops.DepthClassifierFn, ops.depth_expect); the `upsample` branch runs its 1x1 conv at P5's size and resizes
+    the 128-channel result (conv and resize commute, the bilinear weights sum to 1).  HIP device only: host tensors raise Y3DError.
+    `weighted_depth` carries no gradient: nothing in the reference consumes one (the fgdm loss reads the logits)."""
+
+    hidden_dim = 128
+
+    def __init__(self, ch=()):
+        super().__init__()
+        self.depth_min, self.depth_max, self.depth_bins = 1, 70, 80
+        bin_size = 2 * (self.depth_max - self.depth_min) / (self.depth_bins * (1 + self.depth_bins))
+        bin_indice = torch.linspace(0, self.depth_bins - 1, self.depth_bins)
+        bin_value = (bin_indice + 0.5).pow(2) * bin_size / 2 - bin_size / 8 + self.depth_min
+        self.depth_bin_values = nn.Parameter(torch.cat([bin_value, torch.tensor([self.depth_max])], dim=0), requires_grad=False)
+        hd = self.hidden_dim
+        self.downsample = nn.Sequential(nn.Conv2d(ch[0], hd, kernel_size=(3, 3), stride=(2, 2), padding=1), nn.GroupNorm(32, hd))
+        self.proj = nn.Sequential(nn.Conv2d(ch[1], hd, kernel_size=(1, 1)), nn.GroupNorm(32, hd))
+        self.upsample = nn.Sequential(nn.Conv2d(ch[2], hd, kernel_size=(1, 1)), nn.GroupNorm(32, hd))
+        self.depth_head = nn.Sequential(nn.Conv2d(hd, hd, kernel_size=(3, 3), padding=1), nn.GroupNorm(32, num_channels=hd), nn.ReLU(),
+                                        nn.Conv2d(hd, hd, kernel_size=(3, 3), padding=1), nn.GroupNorm(32, num_channels=hd), nn.ReLU())
+        self.depth_classifier = nn.Conv2d(hd, self.depth_bins + 1, kernel_size=(1, 1))
+        self.register_load_state_dict_post_hook(_bump_epoch_on_load)
+
+    @staticmethod
+    def _branch(conv, gn):
+        return (conv.kernel_size[0], conv.stride[0], conv.padding[0]), (conv.weight, conv.bias, gn.weight, gn.bias)
+
+    def _pads(self, dev):
+        """the classifier's persistent zero-padded fp32 weight / bias (88 rows: ops.DepthClassifierFn), one pair per device"""
+        cache = self.__dict__.setdefault("_cls_pad", {})
+        if dev not in cache:
+            cp = -(-(self.depth_bins + 1) // ops.CLS_PAD) * ops.CLS_PAD
+            cache[dev] = (torch.zeros(cp, self.hidden_dim, 1, 1, device=dev), torch.zeros(cp, device=dev))
+        return cache[dev]
+
+    def forward(self, feature, return_embeddings=False):
+        assert len(feature) == 3
+        if _host(feature):
+            raise Y3DError("DepthPredictor runs on the HIP kernels of group_norm.hip / resize.hip: the neck maps must live on a HIP device "
+                           "(no CPU fallback)")
+        size = tuple(feature[1].shape[2:])  # P4's: the stride-16 grid of the fgdm loss
+        eps = self.proj[1].eps
+        geo, args = [], []
+        for seq, x in zip((self.downsample, self.proj, self.upsample), feature):
+            g, params = self._branch(seq[0], seq[1])
+            geo.append(g)
+            args += [x, *params]
+        src = ops.ConvGroupNormFn.apply((tuple(geo), eps, 1.0 / 3.0, False, size), *args)
+        features = None
+        for conv, gn in ((self.depth_head[0], self.depth_head[1]), (self.depth_head[3], self.depth_head[4])):
+            g, params = self._branch(conv, gn)
+            src = ops.ConvGroupNormFn.apply(((g,), gn.eps, 1.0, True, size), src, *params)
+            if features is None:
+                features = src
+        depth_logits = ops.DepthClassifierFn.apply(src, self.depth_classifier.weight, self.depth_classifier.bias, *self._pads(src.device))
+        with torch.no_grad():
+            weighted_depth = ops.depth_expect(depth_logits, self.depth_bin_values)
+        if return_embeddings:
+            return depth_logits, weighted_depth, features
+        return depth_logits, weighted_depth
+
+
 class v10Detect3d(nn.Module):
     """reference head.py:545-975.  The shipped yamls leave every constructor switch off; with `dsconv`, `half_channels` or
     `use_predecessors` on, the head is built and run branch by branch (head.py:629-650, 718-743) on the same HIP ops - the
     sibling-branch fusion of the default head does not apply.  Not available, with the reference's own state of these switches:
     `common_head` (its training forward fails in the reference, head.py:745-746: three layers asserted, `build_small_head` makes two),
     `use_predecessors` in eval mode (the reference's patch path, head.py:709, hands the branches bare feature patches: channel
-    mismatch), `deform` / `fgdm_predictor` (DCN / depth-predictor code outside the YOLOv10 path)."""
+    mismatch), `deform` (DCN code outside the YOLOv10 path).  `fgdm_predictor=True` builds `self.fgdm_predictor`
+    (DepthPredictor, head.py:631-632) after the head sets; the training forward runs it on the undetached level maps and returns
+    `depth_maps = (depth_logits, weighted_depth, features)` (head.py:804-805); the eval forward, `fuse()` and the predictors never touch it."""
 
     max_det = 50
     dynamic = False
@@ -494,6 +566,7 @@ class v10Detect3d(nn.Module):
     fused = True  # sibling-branch fusion of the training forward (set False for the per-branch reference form)
     fuse_bn_proj = True  # second layer of 64-multiple width: BatchNorm + SiLU applied inside the projections (set False for the separate passes)
     distill = False  # set by loss.DDDetectionLoss under `distillation: True`: the fused forward opens the sparse gradient path into z1
+    fgdm_pred = False  # set by the constructor's `fgdm_predictor`: the training forward also runs self.fgdm_predictor (DepthPredictor)
     eval_one2many = False  # the eval forward also returns "one2many": the dense one-to-many head (the validator's use_o2m_depth reads it)
     PREDECESSORS = {"cls": (), "o2d": (), "s2d": (), "o3d": ("cls",), "s3d": ("cls",), "hd": ("cls",), "dep": ("cls", "s3d"),
                     "dep_un": ("cls", "s3d", "dep")}  # head.py:585-594
@@ -503,9 +576,8 @@ class v10Detect3d(nn.Module):
                  kernel_size_1=3, kernel_size_2=3):
         super().__init__()
         assert channels is not None
-        for name, flag in (("deform", deform), ("fgdm_predictor", fgdm_predictor)):
-            if flag:
-                raise NotImplementedError(f"{name}=True is not used by any shipped v10-3D yaml")
+        if deform:
+            raise NotImplementedError("deform=True is not used by any shipped v10-3D yaml")
         if common_head:
             raise NotImplementedError("common_head=True: the reference's own training forward fails on it (head.py:745-746 asserts three "
                                       "layers per branch, build_small_head makes two); there is no behaviour to reproduce")
@@ -531,6 +603,11 @@ class v10Detect3d(nn.Module):
             setattr(self, name, self.build_head([c + extra for c in ch], channels[name + "_c"], out))
         self.o2o_heads = nn.ModuleList([self.cls, self.o2d, self.s2d, self.o3d, self.s3d, self.hd, self.dep, self.dep_un])
         self.o2m_heads = copy.deepcopy(self.o2o_heads)
+        self.fgdm_pred = bool(fgdm_predictor)
+        if self.fgdm_pred:
+            if self.nl != 3:
+                raise ValueError(f"fgdm_predictor: the depth predictor reads three level maps (num_scales = {self.nl})")
+            self.fgdm_predictor = DepthPredictor(ch)
         self.register_load_state_dict_post_hook(_bump_epoch_on_load)
 
     def build_head(self, in_channels, mid, out):
@@ -833,7 +910,11 @@ class v10Detect3d(nn.Module):
             return out
         embs = [_meta(xi.shape[0], self.dep[i][0].conv.out_channels if isinstance(self.dep[i][0], Conv) else self.dep[i][0][-1].conv.out_channels,
                       *xi.shape[2:]) for i, xi in enumerate(x)]
-        return {"one2many": maps, "one2one": list(maps), "o2m_embs": embs, "o2o_embs": list(embs), "depth_maps": torch.empty(1)}
+        depth_maps = torch.empty(1)
+        if self.fgdm_pred:
+            p, (B, h, w) = self.fgdm_predictor, (x[1].shape[0], *x[1].shape[2:])
+            depth_maps = (_meta(B, p.depth_bins + 1, h, w), torch.empty(int(B), int(h), int(w), device="meta"), _meta(B, p.hidden_dim, h, w))
+        return {"one2many": maps, "one2one": list(maps), "o2m_embs": embs, "o2o_embs": list(embs), "depth_maps": depth_maps}
 
     def forward(self, x):
         x = list(x[: self.nl])
@@ -851,7 +932,8 @@ class v10Detect3d(nn.Module):
         else:
             one2one, o2o_embs = self.forward_feat([xi.detach() for xi in x], self.o2o_heads)
             one2many, o2m_embs = self.forward_feat(x, self.o2m_heads)
-        out = {"one2many": one2many, "one2one": one2one, "o2m_embs": o2m_embs, "o2o_embs": o2o_embs, "depth_maps": torch.empty(1)}
+        depth_maps = self.fgdm_predictor(x, return_embeddings=True) if self.fgdm_pred else torch.empty(1)  # head.py:804-807
+        out = {"one2many": one2many, "one2one": one2one, "o2m_embs": o2m_embs, "o2o_embs": o2o_embs, "depth_maps": depth_maps}
         if fused:
             out["_y3d_maps"] = self.__dict__.pop("_maps")  # private extra next to the reference's keys (head.py:833)
             slots = self.__dict__.pop("_slots")

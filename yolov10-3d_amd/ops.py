@@ -959,8 +959,10 @@ def _fp8_dgrad_plan(plan, need_dx, dx_range):
     return ent, lo, hi
 
 
-def _conv_backward(plan, saved, dy, dgb, dres, need_dx, dx_range, dx_out=None):
-    """data and weight gradients of the conv given dy (gradient wrt its pre-BatchNorm output)"""
+def _conv_backward(plan, saved, dy, dgb, dres, need_dx, dx_range, dx_out=None, registry=True):
+    """data and weight gradients of the conv given dy (gradient wrt its pre-BatchNorm output).  registry False: the data-gradient pack of
+    the weight is made on the spot (a weight that is no parameter: the pack registry re-reads its entries' memory once per weight epoch,
+    at the first lookup of ANY weight, which may come before the caller has refreshed such a buffer)"""
     L = lib()
     xin, w32 = saved[:2]
     B, Cin, Cin_k, H, W, Cout, Ho, Wo = plan.B, plan.Cin, plan.Cin_k, plan.H, plan.W, plan.Cout, plan.Ho, plan.Wo
@@ -1005,7 +1007,7 @@ def _conv_backward(plan, saved, dy, dgb, dres, need_dx, dx_range, dx_out=None):
             lo, hi = dx_range if dx_range is not None else (0, Cout)
             assert g == 1 or (lo, hi) == (0, Cout)
             co = hi - lo
-            wpd = _dgrad_packed(w32, w32.data_ptr() + lo * (Cin // g) * k * k * 4, co, Cin // g, g, k, dtype, plan.wver, registry=not plan.stem)
+            wpd = _dgrad_packed(w32, w32.data_ptr() + lo * (Cin // g) * k * k * 4, co, Cin // g, g, k, dtype, plan.wver, registry=registry and not plan.stem)
             dx = dx_out if dx_out is not None else nhwc_empty(B, Cin, H, W, dtype, dev)  # dx_out: a slice of a shared gradient buffer (grad_slot)
             dsb, dsh, dsw = s3(dy)
             _timed(("conv_dgrad", dt, B, H, W, Cin, co, k, s, g),
@@ -1705,3 +1707,238 @@ class AttentionFn(torch.autograd.Function):
         L.attn_bwd(dt, qkv.data_ptr(), qkv.stride(3), out.data_ptr(), C, dout.data_ptr(), dout.stride(3), dvp, dvs, lse.data_ptr(),
                    delta.data_ptr(), dqkv.data_ptr(), Ct, B, N, nh, kd, hd, scale, stream())
         return dqkv, None, None, None, None
+
+
+# ---- depth predictor of the 3D head (modules.DepthPredictor, reference head.py:978-1042) -----------------------------------------------
+# Conv2d (with bias) + GroupNorm(32, 128) pairs.  The conv writes its raw output without the bias (conv2d_fwd with bias None keeps the
+# fast 3x3 / streaming 1x1 routes); the GroupNorm kernels of csrc/group_norm.hip add it.  Conv data / weight gradients are _conv_backward's.
+GN_C, GN_G = 128, 32
+
+
+def _ptrs(ts):
+    return (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+
+
+def _gn_maps(who, ts):
+    """the (B, C, H, W) maps of one GroupNorm call: same shape and dtype, pixel-dense NHWC on a HIP device"""
+    t0 = ts[0]
+    for t in ts:
+        _require_gpu(t)
+        if t.shape != t0.shape or t.dtype != t0.dtype or t.dim() != 4:
+            raise Y3DError(f"{who}: the maps must share one (B, C, H, W) shape and dtype")
+        if not (is_nhwc(t) and px_dense(t)):
+            raise Y3DError(f"{who}: the maps must be pixel-dense NHWC tensors")
+    return t0.shape, t0.dtype, t0.device
+
+
+def _gn_vecs(who, vs, C):
+    out = []
+    for v in vs:
+        _require_gpu(v)
+        v = v.detach()
+        if v.dtype != torch.float32 or not v.is_contiguous():
+            v = v.float().contiguous()
+        if v.numel() != C:
+            raise Y3DError(f"{who}: per-channel vectors must hold {C} values (got {v.numel()})")
+        out.append(v)
+    return out
+
+
+def gn_forward(ys, bconvs, gammas, betas, eps=1e-5, scale=1.0, relu=False, groups=GN_G, out=None):
+    """out = act(scale * sum_i GroupNorm_i(ys[i] + bconvs[i])) over 1 or 3 raw conv outputs -> (out, stats); stats [nsrc][B][G][2] =
+    (mean, rstd) for gn_backward.  Two launches: chunk statistics, then the apply pass that folds them in its prologue."""
+    (B, C, H, W), dtype, dev = _gn_maps("gn_forward", ys)
+    n = len(ys)
+    bconvs, gammas, betas = _gn_vecs("gn_forward", bconvs, C), _gn_vecs("gn_forward", gammas, C), _gn_vecs("gn_forward", betas, C)
+    L, st, dt = lib(), stream(), code(dtype)
+    if out is None:
+        out = nhwc_empty(B, C, H, W, dtype, dev)
+    else:
+        _gn_maps("gn_forward", [out, ys[0]])
+    sw = (ctypes.c_int64 * n)(*[y.stride(3) for y in ys])
+    part = _f32(n * B * max(L.gn_chunks(H * W), 1) * groups * 2, dev)
+    stats = _f32(n * B * groups * 2, dev)
+    L.gn_stats(dt, n, _ptrs(ys), sw, _ptrs(bconvs), B, H * W, C, groups, part.data_ptr(), st)
+    L.gn_apply(dt, n, _ptrs(ys), sw, _ptrs(bconvs), _ptrs(gammas), _ptrs(betas), part.data_ptr(), float(eps), float(scale), int(relu),
+               out.data_ptr(), out.stride(3), stats.data_ptr(), B, H * W, C, groups, st)
+    return out, stats
+
+
+def gn_backward(ys, bconvs, gammas, betas, stats, dz, scale=1.0, relu=False, groups=GN_G, dys=None):
+    """-> (dys, dgamma, dbeta, dbconv): the gradient wrt every raw conv output (compute dtype, pixel-dense) and the (nsrc, C) fp32 parameter
+    gradients, given dz = gradient wrt gn_forward's out.  Two launches: reduce, apply."""
+    (B, C, H, W), dtype, dev = _gn_maps("gn_backward", list(ys) + [dz])
+    n = len(ys)
+    bconvs, gammas, betas = _gn_vecs("gn_backward", bconvs, C), _gn_vecs("gn_backward", gammas, C), _gn_vecs("gn_backward", betas, C)
+    L, st, dt = lib(), stream(), code(dtype)
+    if dys is None:
+        dys = [nhwc_empty(B, C, H, W, dtype, dev) for _ in range(n)]
+    else:
+        _gn_maps("gn_backward", list(dys) + [ys[0]])
+    sw = (ctypes.c_int64 * n)(*[y.stride(3) for y in ys])
+    dsw = (ctypes.c_int64 * n)(*[d.stride(3) for d in dys])
+    part = _f32(B * max(L.gn_chunks(H * W), 1) * (2 * n + 1) * C, dev)
+    dpar = _f32(3 * n * C, dev).view(3, n, C)
+    args = (dt, n, _ptrs(ys), sw, _ptrs(bconvs), _ptrs(gammas), _ptrs(betas), stats.data_ptr(), float(scale), int(relu), dz.data_ptr(), dz.stride(3),
+            part.data_ptr())
+    L.gn_bwd_reduce(*args, B, H * W, C, groups, st)
+    L.gn_bwd_apply(*args, _ptrs(dys), dsw, dpar[0].data_ptr(), dpar[1].data_ptr(), dpar[2].data_ptr(), B, H * W, C, groups, st)
+    return dys, dpar[0], dpar[1], dpar[2]
+
+
+def resize_bilinear(x, size):
+    """F.interpolate(x, size=size, mode="bilinear", align_corners=False) of an NHWC map (C % 8 == 0) on the HIP kernel of csrc/resize.hip"""
+    _require_gpu(x)
+    x = to_nhwc(x, x.dtype if x.dtype in (torch.float32, torch.bfloat16) else None)
+    B, C, H, W = x.shape
+    y = nhwc_empty(B, C, size[0], size[1], x.dtype, x.device)
+    lib().resize_bilinear_fwd(code(x.dtype), x.data_ptr(), *s3(x), y.data_ptr(), y.stride(3), B, H, W, size[0], size[1], C, stream())
+    return y
+
+
+def resize_bilinear_adjoint(dy, size):
+    """the adjoint of resize_bilinear from (H, W) = `size`: dx (B, C, H, W) given dy (B, C, Ho, Wo)"""
+    _require_gpu(dy)
+    dy = to_nhwc(dy, dy.dtype if dy.dtype in (torch.float32, torch.bfloat16) else None, dense=True)
+    B, C, Ho, Wo = dy.shape
+    dx = nhwc_empty(B, C, size[0], size[1], dy.dtype, dy.device)
+    lib().resize_bilinear_bwd(code(dy.dtype), dy.data_ptr(), dy.stride(3), dx.data_ptr(), dx.stride(3), B, size[0], size[1], Ho, Wo, C, stream())
+    return dx
+
+
+class ResizeBilinearFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, size):
+        ctx.size = tuple(x.shape[2:])
+        return resize_bilinear(x, size)
+
+    @staticmethod
+    def backward(ctx, dy):
+        return resize_bilinear_adjoint(dy, ctx.size), None
+
+
+def _raw_conv(x, w32, k, s, p):
+    """y = conv(x, w) without bias, dense, groups 1 -> (xin, y, plan): the operands _conv_backward takes"""
+    _require_gpu(x)
+    dtype = _COMPUTE_DTYPE
+    xin = to_nhwc(x.detach(), dtype)
+    B, Cin, H, W = xin.shape
+    Cout = w32.shape[0]
+    if Cin % ce(dtype) or w32.shape[1] != Cin:
+        raise Y3DError(f"conv over {Cin} input channels: a multiple of {ce(dtype)} that matches the weight's {w32.shape[1]} is needed")
+    Ho, Wo = (H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1
+    y = nhwc_empty(B, Cout, Ho, Wo, dtype, xin.device)
+    wp = _fwd_packed(w32, Cout, Cin, Cin, k, dtype, None, registry=True)
+    lib().conv2d_fwd(code(dtype), xin.data_ptr(), *s3(xin), B, H, W, Cin, wp.data_ptr(), None, y.data_ptr(), Cout, Ho, Wo, Cout, 1, k, k, s, p,
+                     None, stream())
+    return xin, y, ConvPlan(B, Cin, Cin, H, W, Cout, Ho, Wo, k, s, p, 1, False, 0, True, dtype, 0, None, None)
+
+
+class ConvGroupNormFn(torch.autograd.Function):
+    """out = act(scale * sum_i GroupNorm(conv_i(x_i) + b_i)) for 1 or 3 branches of Conv2d(c_i, 128, k_i, s_i, p_i) + GroupNorm(32, 128).
+    apply(spec, x_0, w_0, b_0, gamma_0, beta_0, x_1, ...); spec = (((k, s, p), ...), eps, scale, relu, (H, W)).  A branch whose conv output
+    is not (H, W) is resized to it bilinearly AFTER the conv: conv and resize are linear and the
+    bilinear weights sum to 1, so conv(resize(x)) + b = resize(conv(x)) + b, at a quarter of the conv's work for a 2x map."""
+
+    @staticmethod
+    def forward(ctx, spec, *args):
+        geo, eps, scale, relu, size = spec
+        srcs, saved, plans = [], [], []
+        for i, (k, s, p) in enumerate(geo):
+            x, w, b, gamma, beta = args[5 * i:5 * i + 5]
+            w32 = _w32(w)
+            xin, y, plan = _raw_conv(x, w32, k, s, p)
+            if w32.shape[0] != GN_C:
+                raise Y3DError(f"ConvGroupNormFn: the GroupNorm kernels are built for {GN_C} channels in {GN_G} groups (got {w32.shape[0]})")
+            if (plan.Ho, plan.Wo) != tuple(size):
+                y = resize_bilinear(y, size)
+            srcs.append(y)
+            plans.append(plan)
+            saved += [xin, w32, y, b.detach(), gamma.detach(), beta.detach()]
+        out, stats = gn_forward(srcs, saved[3::6], saved[4::6], saved[5::6], eps, scale, relu)
+        ctx.plans, ctx.spec = plans, spec
+        ctx.save_for_backward(stats, *saved)
+        return out
+
+    @staticmethod
+    def backward(ctx, dz):
+        geo, eps, scale, relu, size = ctx.spec
+        stats, *saved = ctx.saved_tensors
+        dtype = ctx.plans[0].dtype
+        dz = to_nhwc(dz, dtype, dense=True)
+        dys, dgamma, dbeta, dbconv = gn_backward(saved[2::6], saved[3::6], saved[4::6], saved[5::6], stats, dz, scale, relu)
+        grads = [None]
+        for i, plan in enumerate(ctx.plans):
+            xin, w32 = saved[6 * i], saved[6 * i + 1]
+            dy = dys[i]
+            if (plan.Ho, plan.Wo) != tuple(size):
+                dy = resize_bilinear_adjoint(dy, (plan.Ho, plan.Wo))
+            dx, dW = _conv_backward(plan, (xin, w32), dy, (None, None), None, ctx.needs_input_grad[1 + 5 * i], None)[:2]
+            grads += [dx, dW, dbconv[i], dgamma[i], dbeta[i]]
+        return tuple(grads)
+
+
+CLS_PAD = 8  # the depth classifier's 81 output channels run as 88: the data / weight gradient kernels take whole 16-byte chunks of Cout
+
+
+class DepthClassifierFn(torch.autograd.Function):
+    """logits = Conv2d(128, 81, 1)(x) (head.py:1014, 1034) on a weight zero-padded to 88 rows: the logits live in an 88-channel NHWC
+    buffer whose pad columns are 0 (zero weight rows, zero bias), the result is its [:, :81] view; the backward pads the logits'
+    gradient with +0 columns, runs _conv_backward at 88 channels and slices dW back.  apply(x, weight, bias, wpad, bpad): wpad / bpad are
+    the caller's persistent padded fp32 buffers, refreshed here."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, wpad, bpad):
+        co = weight.shape[0]
+        wpad[:co].copy_(weight.detach())
+        bpad[:co].copy_(bias.detach())
+        _require_gpu(x)
+        dtype = _COMPUTE_DTYPE
+        xin = to_nhwc(x.detach(), dtype)
+        B, Cin, H, W = xin.shape
+        cp = wpad.shape[0]
+        z = nhwc_empty(B, cp, H, W, dtype, xin.device)
+        # packed on the spot, here and in the backward: a registry entry of wpad would be repacked at the first lookup of any weight after
+        # an optimizer step - possibly before the refresh above - and then count as current: last step's classifier
+        wp = _fwd_packed(wpad, cp, Cin, Cin, 1, dtype, None, registry=False)
+        lib().conv2d_fwd(code(dtype), xin.data_ptr(), *s3(xin), B, H, W, Cin, wp.data_ptr(), bpad.data_ptr(), z.data_ptr(), cp, H, W, cp, 1, 1, 1, 1, 0,
+                         None, stream())
+        ctx.plan = ConvPlan(B, Cin, Cin, H, W, cp, H, W, 1, 1, 0, 1, False, 0, True, dtype, 0, None, None)
+        ctx.co = co
+        # (wpad rides outside save_for_backward: the next forward refreshes it in place - with the same values until an optimizer step)
+        ctx.wpad = wpad
+        ctx.save_for_backward(xin)
+        return z[:, :co]
+
+    @staticmethod
+    def backward(ctx, dz):
+        (xin,), wpad = ctx.saved_tensors, ctx.wpad
+        plan, co = ctx.plan, ctx.co
+        B, cp, H, W = plan.B, plan.Cout, plan.H, plan.W
+        dy = torch.zeros((B, H, W, cp), dtype=plan.dtype, device=dz.device).permute(0, 3, 1, 2)  # the pad columns: +0
+        dy[:, :co].copy_(dz)
+        L = lib()
+        M = B * H * W
+        part = _f32(L.colsum_blocks(M) * cp, dz.device)
+        db = _f32(cp, dz.device)
+        L.colsum(code(plan.dtype), dy.data_ptr(), cp, M, cp, part.data_ptr(), db.data_ptr(), stream())
+        dx, dW = _conv_backward(plan, (xin, wpad), dy, (None, None), None, ctx.needs_input_grad[0], None, registry=False)[:2]
+        return dx, dW[:co], db[:co], None, None
+
+
+def depth_expect(logits, bins):
+    """weighted_depth = sum_c softmax(logits)_c * bins[c] (head.py:1036-1037) -> (B, h, w) fp32, one launch.  No gradient: nothing in the
+    reference consumes it (the fgdm loss reads the logits); call it under no_grad."""
+    _require_gpu(logits)
+    z = logits.detach()
+    B, C, h, w = z.shape
+    c = ce(z.dtype)
+    if not (z.dtype in (torch.float32, torch.bfloat16) and is_nhwc(z) and px_dense(z) and z.stride(3) % c == 0 and z.stride(3) >= -(-C // c) * c
+            and z.data_ptr() % 16 == 0):
+        pad = nhwc_empty(B, -(-C // c) * c, h, w, z.dtype if z.dtype in (torch.float32, torch.bfloat16) else _COMPUTE_DTYPE, z.device)
+        pad[:, :C].copy_(z)
+        z = pad[:, :C]
+    out = torch.empty(B, h, w, dtype=torch.float32, device=z.device)
+    bins = bins.detach().float().contiguous()
+    lib().depth_expect(code(z.dtype), z.data_ptr(), z.stride(3), B * h * w, C, bins.data_ptr(), out.data_ptr(), stream())
+    return out

@@ -32,7 +32,7 @@ CFG_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "cfg", "model
 DEFAULT_HYP = dict(box=5.0, cls=1.0, dfl=1.5, loss2d=2.0, depth=1.0, offset3d=10.0, size3d=1.0, heading=1.0,
                    tal_topk=8, tal_alpha=0.5, tal_beta=1.0, tal_gamma=1.0, tal_3d=True, tal_2d=True, kps_dist_metric="l1",
                    constrain_anchors=True, distillation=False, distillation_temp=2, distillation_weight=0.75, distillation_loss="soft",
-                   distillation_no_mixup=True, fgdm_loss=False, fgdm_supervision=False, htl=False)
+                   distillation_no_mixup=True, fgdm_loss=False, fgdm_loss_weight=2, fgdm_supervision=False, htl=False)
 
 _REGISTRY = {"Conv": Conv, "DWConv": DWConv, "C2f": C2f, "C2fCIB": C2fCIB, "SCDown": SCDown, "SPPF": SPPF, "PSA": PSA,
              "Concat": Concat, "nn.Upsample": Upsample, "Detect": Detect, "v10Detect": v10Detect, "v10Detect3d": v10Detect3d}

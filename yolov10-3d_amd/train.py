@@ -202,6 +202,13 @@ class Trainer:
                  val_period=1, patience=150, save_dir=None, save_period=-1, seed=0, data_args=None, max_norm=10.0, resume=None, htl=None):
         if htl is None:
             htl = getattr(getattr(model, "args", None), "htl", False)
+        margs = getattr(model, "args", None)
+        if htl and getattr(margs, "fgdm_loss", False):
+            raise NotImplementedError("Trainer: htl with fgdm_loss: 12 weights for 13 items, as with distillation; set one of them off")
+        head = model.model[-1] if hasattr(model, "model") else None
+        if getattr(head, "fgdm_pred", False) and not getattr(margs, "fgdm_loss", False):
+            raise Y3DError("Trainer: the head was built with fgdm_predictor but fgdm_loss is off: the depth predictor's parameters would "
+                           "never get a gradient; set fgdm_loss: True (and load_depth_maps: True in the data args) or build the head without it")
         if htl:
             if next(model.parameters()).device.type != "cuda":
                 raise NotImplementedError("Trainer: htl (hierarchical task learning) keeps its weight table on the device and weights the "
