@@ -5,6 +5,7 @@
     python tools/train.py yolov10n.yaml --data /data/coco/images/train2017 --val /data/coco/images/val2017     # 2D: image directories / lists
     python tools/train.py yolov10s_3D.yaml --data /data/kitti --resume runs/s3d/weights/last.pt --save-dir runs/s3d
     python tools/train.py yolov10s_3D.yaml --data /data/kitti --htl --save-dir runs/s3d_htl                     # hierarchical task learning
+    python tools/train.py yolov10s_3D.yaml --data /data/kitti --pretrained-body v10s_2d.pt --freeze 11          # transfer: frozen backbone
 
 The training split is decoded once and held on the device (`kitti.DeviceSplit`, `json3d.DeviceSplit`, `yolo2d.DeviceSplit`); the
 validator (`val.Validator3d` / `val.Validator2d`, twice the training batch as in the reference) runs on the EMA model.  Without --val
@@ -19,6 +20,14 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import yolov10_3d_amd as y3d  # noqa: E402
 from yolov10_3d_amd import json3d, kitti, train, val, yolo2d  # noqa: E402
+
+
+def freeze_arg(text):
+    """"11" -> 11 (layers 0..10); "0,1,2" -> [0, 1, 2]"""
+    try:
+        return [int(t) for t in text.split(",")] if "," in text else int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"--freeze {text}: a layer count or a comma-separated list of layer indices") from None
 
 
 def parser():
@@ -55,6 +64,9 @@ def parser():
     ap.add_argument("--fgdm", action="store_true", help="3D KITTI models: train the head's depth predictor on the foreground depth maps "
                     "(sets fgdm_predictor, fgdm_loss and load_depth_maps; the split needs its segmentation masks)")
     ap.add_argument("--resume", help="a last.pt of this trainer: continue at its epoch + 1")
+    ap.add_argument("--freeze", type=freeze_arg, help="freeze layers: N (layers 0..N-1) or a comma-separated list of layer indices, e.g. 0,1,2")
+    ap.add_argument("--pretrained-body", help="fill every layer but the detection head from a trainer checkpoint or a state_dict file "
+                    "(BaseModel.load_pretrained_body), e.g. a 2D model of the same scale")
     return ap
 
 
@@ -75,6 +87,8 @@ def main(argv=None):
             ck = ck.get("ema") or ck.get("model") or ck
         got, own = model.load(ck)
         print(f"loaded {got} of {own} tensors from {a.weights}")
+    if a.pretrained_body:
+        print(f"loaded {model.load_pretrained_body(a.pretrained_body)} body tensors from {a.pretrained_body}")
     model = model.to("cuda").train()
     if a.fgdm:
         model.args.fgdm_loss = True
@@ -99,7 +113,7 @@ def main(argv=None):
                       momentum=a.momentum, weight_decay=a.weight_decay, warmup_epochs=a.warmup_epochs, warmup_momentum=a.warmup_momentum,
                       warmup_bias_lr=a.warmup_bias_lr, cos_lr=a.cos_lr, close_mixup=a.close_mixup, close_mosaic=a.close_mosaic,
                       val_period=a.val_period, patience=a.patience, save_dir=a.save_dir, save_period=a.save_period, seed=a.seed,
-                      data_args=data_args, max_norm=a.max_norm, resume=a.resume, htl=a.htl or None)
+                      data_args=data_args, max_norm=a.max_norm, resume=a.resume, htl=a.htl or None, freeze=a.freeze)
 
     def line(h):
         skip = ("epoch", "fitness")

@@ -99,6 +99,10 @@ class GraphedTrainStep:
         from . import loss as _loss
         from .ddp import PER_BOX_KEYS
         from .modules import Conv
+        if getattr(model, "freeze_layers", None):
+            # a frozen prefix or frozen layers change which backward nodes exist; the capture has not been run on such a step
+            raise Y3DError(f"GraphedTrainStep: the model has frozen layers {model.freeze_layers} (train.apply_freeze); the captured step "
+                           "is not supported with frozen layers - train them with train.Trainer or an eager step")
         self.model, self.opt, self.max_norm, self.reducer = model, opt, max_norm, reducer
         self.box_keys = tuple(k for k in (("batch_idx",) + PER_BOX_KEYS) if k in batch)
         B = batch["img"].shape[0]

@@ -907,16 +907,17 @@ def _bn_act_tail(xin, y, part, nblk, ss_eval, call, Cin, wver, fp8_entry):
     return z, plan, (xin, w32, y, stats, rr if res_mode == 2 else None)
 
 
-def _cba_backward(plan, saved, dz, need_dx, need_dres, dx_range=None, pre=None, dx_out=None):
+def _cba_backward(plan, saved, dz, need_dx, need_dres, dx_range=None, pre=None, dx_out=None, need_dw=True):
     """-> dx, dW (fp32 OIHW), dgamma, dbeta, dres.  dx_range=(lo, hi): only output channels lo..hi feed dx
-    (the one-to-one head sees a detached input, reference head.py:820)."""
+    (the one-to-one head sees a detached input, reference head.py:820).  need_dw False (a frozen weight): no weight-gradient launch, no
+    slab, no fold, no dW buffer - dW is None; the BatchNorm reduce / finalize still run (their sums feed the apply pass)."""
     L = lib()
     _, _, y, stats, rr = saved
     B, Cout, Ho, Wo, res_mode, dtype, act = plan.B, plan.Cout, plan.Ho, plan.Wo, plan.res_mode, plan.dtype, plan.act
     if not plan.training:
         raise Y3DError("backward through an eval-mode (running-statistics) Conv is not supported")
     if pre is not None:  # (dy, dgb): the BatchNorm part was done by the caller (FusedConvBNProjFn)
-        return _conv_backward(plan, saved, pre[0], pre[1], None, need_dx, dx_range, dx_out)
+        return _conv_backward(plan, saved, pre[0], pre[1], None, need_dx, dx_range, dx_out, need_dw=need_dw)
     dt, st, dev = code(dtype), stream(), dz.device
     M = B * Ho * Wo
     dz = to_nhwc(dz, dtype, dense=True)
@@ -937,7 +938,7 @@ def _cba_backward(plan, saved, dz, need_dx, need_dres, dx_range=None, pre=None, 
                        dy.data_ptr(), Cout, dres.data_ptr() if dres is not None else None, Cout, M, Cout, st)
     if res_mode == 1:
         dres = dz
-    return _conv_backward(plan, saved, dy, dgb, dres, need_dx, dx_range, dx_out)
+    return _conv_backward(plan, saved, dy, dgb, dres, need_dx, dx_range, dx_out, need_dw=need_dw)
 
 
 def _fp8_dgrad_plan(plan, need_dx, dx_range):
@@ -959,10 +960,11 @@ def _fp8_dgrad_plan(plan, need_dx, dx_range):
     return ent, lo, hi
 
 
-def _conv_backward(plan, saved, dy, dgb, dres, need_dx, dx_range, dx_out=None, registry=True):
+def _conv_backward(plan, saved, dy, dgb, dres, need_dx, dx_range, dx_out=None, registry=True, need_dw=True):
     """data and weight gradients of the conv given dy (gradient wrt its pre-BatchNorm output).  registry False: the data-gradient pack of
     the weight is made on the spot (a weight that is no parameter: the pack registry re-reads its entries' memory once per weight epoch,
-    at the first lookup of ANY weight, which may come before the caller has refreshed such a buffer)"""
+    at the first lookup of ANY weight, which may come before the caller has refreshed such a buffer).  need_dw False: the weight-gradient
+    half (launch, split-K slab, fold, dW buffer) is left out and dW is None; the data gradient - bf16 or fp8 - is the same call"""
     L = lib()
     xin, w32 = saved[:2]
     B, Cin, Cin_k, H, W, Cout, Ho, Wo = plan.B, plan.Cin, plan.Cin_k, plan.H, plan.W, plan.Cout, plan.Ho, plan.Wo
@@ -973,16 +975,17 @@ def _conv_backward(plan, saved, dy, dgb, dres, need_dx, dx_range, dx_out=None, r
     M = B * Ho * Wo
     sb, sh, sw = s3(xin)
     dx = None
-    dW = torch.empty_like(w32)
+    dW = torch.empty_like(w32) if need_dw else None
     if plan.dw:
         wp = _dw_packed(w32, Cout, k, dtype, plan.wver)  # (the buffer the forward of this step used)
         if need_dx:
             dx = nhwc_empty(B, Cin, H, W, dtype, dev)
             dsb, dsh, dsw = s3(dy)
             L.dwconv2d_bwd_data(dt, dy.data_ptr(), dsb, dsh, dsw, B, Ho, Wo, Cout, wp.data_ptr(), dx.data_ptr(), Cin, H, W, k, k, s, p, st)
-        slab = _f32(L.dw_wgrad_blocks(M) * k * k * Cout, dev)
-        L.dwconv2d_bwd_weight(dt, xin.data_ptr(), sb, sh, sw, B, H, W, Cin, dy.data_ptr(), Cout, Ho, Wo, k, k, s, p, slab.data_ptr(),
-                              dW.data_ptr(), 0, st)
+        if need_dw:
+            slab = _f32(L.dw_wgrad_blocks(M) * k * k * Cout, dev)
+            L.dwconv2d_bwd_weight(dt, xin.data_ptr(), sb, sh, sw, B, H, W, Cin, dy.data_ptr(), Cout, Ho, Wo, k, k, s, p, slab.data_ptr(),
+                                  dW.data_ptr(), 0, st)
     else:
         f8 = _fp8_dgrad_plan(plan, need_dx, dx_range)
         if f8 is not None and not (px_dense(dy) and dy.data_ptr() % 16 == 0 and dy.stride(3) % 8 == 0):
@@ -1013,13 +1016,15 @@ def _conv_backward(plan, saved, dy, dgb, dres, need_dx, dx_range, dx_out=None, r
             _timed(("conv_dgrad", dt, B, H, W, Cin, co, k, s, g),
                    lambda: L.conv2d_bwd_data(dt, dy.data_ptr() + lo * esz, dsb, dsh, dsw, B, Ho, Wo, co, wpd.data_ptr(), dx.data_ptr(), dx.stride(3), H, W,
                                              Cin, g, k, k, s, p, st))
-        ns = L.conv2d_wgrad_plan(dt, B, H, W, Cin_k, Cout, g, k, k, s, p)
-        slab = _f32(ns * Cout * k * k * (Cin_k // g), dev)
-        _timed(("conv_wgrad", dt, B, H, W, Cin_k, Cout, k, s, g),
-               lambda: L.conv2d_bwd_weight(dt, xin.data_ptr(), sb, sh, sw, B, H, W, Cin_k, Cin, dy.data_ptr(), Cout, Ho, Wo, Cout, g, k, k,
-                                           s, p, slab.data_ptr(), ns, dW.data_ptr(), 0, st))
+        if need_dw:
+            ns = L.conv2d_wgrad_plan(dt, B, H, W, Cin_k, Cout, g, k, k, s, p)
+            slab = _f32(ns * Cout * k * k * (Cin_k // g), dev)
+            _timed(("conv_wgrad", dt, B, H, W, Cin_k, Cout, k, s, g),
+                   lambda: L.conv2d_bwd_weight(dt, xin.data_ptr(), sb, sh, sw, B, H, W, Cin_k, Cin, dy.data_ptr(), Cout, Ho, Wo, Cout, g, k, k,
+                                               s, p, slab.data_ptr(), ns, dW.data_ptr(), 0, st))
     if plan.stem:  # [Cout][(r*3+q)*3+ci | 5 zeros] -> OIHW (Cout, 3, 3, 3); the image itself gets no gradient
-        dW = dW.reshape(Cout, 32)[:, :27].reshape(Cout, 3, 3, 3).permute(0, 3, 1, 2).contiguous()
+        if need_dw:
+            dW = dW.reshape(Cout, 32)[:, :27].reshape(Cout, 3, 3, 3).permute(0, 3, 1, 2).contiguous()
         dx = None
     return dx, dW, dgb[0], dgb[1], dres
 
@@ -1053,8 +1058,9 @@ class ConvBNActFn(torch.autograd.Function):
     def backward(ctx, dz):
         if ctx.cfg is None:
             raise Y3DError("backward through an eval-mode (running-statistics) Conv is not supported")
-        dx, dW, dg, db, dres = _cba_backward(ctx.cfg, ctx.saved_tensors, dz, ctx.needs_input_grad[0], ctx.needs_input_grad[4])
-        return dx, dW, dg, db, dres, None, None
+        need = ctx.needs_input_grad  # x, weight, gamma, beta, res: a frozen parameter gets None (and a frozen weight no launch)
+        dx, dW, dg, db, dres = _cba_backward(ctx.cfg, ctx.saved_tensors, dz, need[0], need[4], need_dw=need[1])
+        return dx, dW, dg if need[2] else None, db if need[3] else None, dres, None, None
 
 
 class StackedConvs:
@@ -1107,6 +1113,16 @@ class StackedConvs:
         return [c.conv.weight for c in self.convs] + [c.bn.weight for c in self.convs] + [c.bn.bias for c in self.convs]
 
 
+def _stack_grads(dW, dg, db, couts):
+    """the per-branch row slices of a stack's gradients in StackedConvs.params() order; dW None (frozen weights): None per branch"""
+    return [*(dW.split(couts) if dW is not None else [None] * len(couts)), *dg.split(couts), *db.split(couts)]
+
+
+def _masked(grads, need):
+    """`grads` with None wherever autograd asked for no gradient (a frozen parameter)"""
+    return [g if n else None for g, n in zip(grads, need)]
+
+
 class FusedConvBNActFn(torch.autograd.Function):
     """One conv+BN+SiLU over the stacked output channels of `stack.convs`.  args: x, stack, groups, dx_range, *params
     (params only tie the per-branch Parameters into the autograd graph; the math runs on the stacked storage)."""
@@ -1128,8 +1144,13 @@ class FusedConvBNActFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dz):
         dx_out = grad_slot_tensor(ctx.gslot) if (ctx.gslot is not None and ctx.needs_input_grad[0]) else None
-        dx, dW, dg, db, _ = _cba_backward(ctx.cfg, ctx.saved_tensors, dz, ctx.needs_input_grad[0], False, ctx.dx_range, dx_out=dx_out)
-        return (dx, None, None, None, *dW.split(ctx.couts), *dg.split(ctx.couts), *db.split(ctx.couts))  # per-branch row slices of the stack
+        need = ctx.needs_input_grad[4:]  # per branch: weights, gammas, betas
+        n = len(ctx.couts)
+        need_dw = any(need[:n])
+        dx, dW, dg, db, _ = _cba_backward(ctx.cfg, ctx.saved_tensors, dz, ctx.needs_input_grad[0], False, ctx.dx_range, dx_out=dx_out, need_dw=need_dw)
+        if all(need):
+            return (dx, None, None, None, *dW.split(ctx.couts), *dg.split(ctx.couts), *db.split(ctx.couts))  # per-branch row slices of the stack
+        return (dx, None, None, None, *_masked(_stack_grads(dW, dg, db, ctx.couts), need))
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -1319,9 +1340,11 @@ class HeadProjFn(torch.autograd.Function):
         dsw = dout.stride(3)
         nb = L.proj_blocks(P)
         dxs, dws, dbs, off = [], [], [], 0
+        need = ctx.needs_input_grad
         for j, (x, w, co) in enumerate(zip(xs, ws, couts)):
             Cin = x.shape[1]
-            dx = None
+            dx = dW = db = None
+            need_w, need_b = need[1 + n + j], need[1 + 2 * n + j]  # a frozen branch: neither the weight-gradient launch nor the bias sums
             if ctx.wide[j]:
                 dptr = dout.data_ptr() + off * esz
                 dsb, dsh, _ = s3(dout)
@@ -1329,17 +1352,19 @@ class HeadProjFn(torch.autograd.Function):
                     wpd = _dgrad_packed(w, w.data_ptr(), co, Cin, 1, 1, dtype)
                     dx = nhwc_empty(B, Cin, H, W, dtype, dev)
                     L.conv2d_bwd_data(dt, dptr, dsb, dsh, dsw, B, H, W, co, wpd.data_ptr(), dx.data_ptr(), Cin, H, W, Cin, 1, 1, 1, 1, 0, st)
-                sb, sh, sw = s3(x)
-                ns = L.conv2d_wgrad_plan(dt, B, H, W, Cin, co, 1, 1, 1, 1, 0)
-                slab = _f32(ns * co * Cin, dev)
-                dW = torch.empty_like(w)
-                L.conv2d_bwd_weight(dt, x.data_ptr(), sb, sh, sw, B, H, W, Cin, Cin, dptr, dsw, H, W, co, 1, 1, 1, 1, 0, slab.data_ptr(), ns,
-                                    dW.data_ptr(), 0, st)
-                nbb = L.bn_bwd_blocks(P, co)  # bias gradient: column sums of the dout slice
-                part = _f32(nbb * co * 2, dev)
-                L.colsum_partials(dt, dptr, dsw, part.data_ptr(), P, co, st)
-                db, scratch = _f32(co, dev), _f32(2 * co, dev)
-                L.bn_bwd_finalize(part.data_ptr(), nbb, co, P, None, db.data_ptr(), 0, scratch.data_ptr(), scratch.data_ptr() + 4 * co, st)
+                if need_w:
+                    sb, sh, sw = s3(x)
+                    ns = L.conv2d_wgrad_plan(dt, B, H, W, Cin, co, 1, 1, 1, 1, 0)
+                    slab = _f32(ns * co * Cin, dev)
+                    dW = torch.empty_like(w)
+                    L.conv2d_bwd_weight(dt, x.data_ptr(), sb, sh, sw, B, H, W, Cin, Cin, dptr, dsw, H, W, co, 1, 1, 1, 1, 0, slab.data_ptr(), ns,
+                                        dW.data_ptr(), 0, st)
+                if need_b:
+                    nbb = L.bn_bwd_blocks(P, co)  # bias gradient: column sums of the dout slice
+                    part = _f32(nbb * co * 2, dev)
+                    L.colsum_partials(dt, dptr, dsw, part.data_ptr(), P, co, st)
+                    db, scratch = _f32(co, dev), _f32(2 * co, dev)
+                    L.bn_bwd_finalize(part.data_ptr(), nbb, co, P, None, db.data_ptr(), 0, scratch.data_ptr(), scratch.data_ptr() + 4 * co, st)
             else:
                 if ctx.needs_input_grad[1 + j]:
                     dx = nhwc_empty(B, Cin, H, W, dtype, dev)
@@ -1349,10 +1374,12 @@ class HeadProjFn(torch.autograd.Function):
                                         min(24, co - o0), st)
                         if o0:
                             L.add2d(dt, dx.data_ptr(), Cin, tgt.data_ptr(), Cin, dx.data_ptr(), Cin, P, Cin, st)
-                dW, db = torch.empty_like(w), _f32(co, dev)
-                slab, bslab = _f32(nb * co * Cin, dev), _f32(nb * co, dev)
-                L.proj_bwd_weight(dt, x.data_ptr(), x.stride(3), dout.data_ptr() + off * esz, dsw, slab.data_ptr(), bslab.data_ptr(),
-                                  dW.data_ptr(), db.data_ptr(), 0, P, Cin, co, st)
+                if need_w or need_b:  # one launch makes both: with one of the two frozen the other half is computed and dropped
+                    dW, db = torch.empty_like(w), _f32(co, dev)
+                    slab, bslab = _f32(nb * co * Cin, dev), _f32(nb * co, dev)
+                    L.proj_bwd_weight(dt, x.data_ptr(), x.stride(3), dout.data_ptr() + off * esz, dsw, slab.data_ptr(), bslab.data_ptr(),
+                                      dW.data_ptr(), db.data_ptr(), 0, P, Cin, co, st)
+                    dW, db = (dW if need_w else None), (db if need_b else None)
             dxs.append(dx)
             dws.append(dW)
             dbs.append(db)
@@ -1450,10 +1477,15 @@ class HeadProjSlicesFn(torch.autograd.Function):
             if pg.n * cin != Ct:
                 dx.zero_()
             L.proj_group_bwd_data(dt, pg.n, cin, dout.data_ptr(), dout.stride(3), pg.c_off, pg.c_w, pg.c_co, dx.data_ptr(), Ct, P, st)
+        need = ctx.needs_input_grad[4:]  # the weights, then the biases
+        if not any(need):  # a frozen head: no weight-gradient launch, no slabs
+            return (dx, None, None, None, *([None] * len(need)))
         dws, dbs, slab, bslab, c_dw, c_db = _proj_wgrad_buffers(pg, L.proj_group_blocks(P), dev)
         L.proj_group_bwd_weight(dt, pg.n, cin, x.data_ptr(), x.stride(3), pg.c_off, dout.data_ptr(), dout.stride(3), pg.c_co, slab.data_ptr(),
                                 bslab.data_ptr(), c_dw, c_db, P, st)
-        return (dx, None, None, None, *dws, *dbs)
+        if all(need):
+            return (dx, None, None, None, *dws, *dbs)
+        return (dx, None, None, None, *_masked(dws + dbs, need))
 
 
 class FusedConvBNProjFn(torch.autograd.Function):
@@ -1512,14 +1544,20 @@ class FusedConvBNProjFn(torch.autograd.Function):
         n, c_w, c_off, c_co = pg.n, pg.c_w, pg.c_off, pg.c_co
         mfma = _proj_mfma(dtype, cin)
         dx_out = grad_slot_tensor(ctx.gslot) if (ctx.gslot is not None and ctx.needs_input_grad[0]) else None
-        nb = L.proj_group_bwd_weight_bn_mfma_blocks(P) if mfma else L.proj_group_blocks(P)
-        dws, dbs, slab, bslab, c_dw, c_db = _proj_wgrad_buffers(pg, nb, dev)
-        tail = (y.data_ptr(), y.stride(3), c_off, dout.data_ptr(), dout.stride(3), c_co, stats[2].data_ptr(), stats[3].data_ptr(), act, slab.data_ptr(),
-                bslab.data_ptr(), c_dw, c_db, P, st)
-        if mfma:
-            L.proj_group_bwd_weight_bn_mfma(n, cin, *tail)
-        else:
-            L.proj_group_bwd_weight_bn(dt, n, cin, *tail)
+        ns = len(ctx.couts_stack)
+        need_stack, need_proj = ctx.needs_input_grad[6:6 + 3 * ns], ctx.needs_input_grad[6 + 3 * ns:]
+        need_dw = any(need_stack[:ns])
+        if any(need_proj):
+            nb = L.proj_group_bwd_weight_bn_mfma_blocks(P) if mfma else L.proj_group_blocks(P)
+            dws, dbs, slab, bslab, c_dw, c_db = _proj_wgrad_buffers(pg, nb, dev)
+            tail = (y.data_ptr(), y.stride(3), c_off, dout.data_ptr(), dout.stride(3), c_co, stats[2].data_ptr(), stats[3].data_ptr(), act, slab.data_ptr(),
+                    bslab.data_ptr(), c_dw, c_db, P, st)
+            if mfma:
+                L.proj_group_bwd_weight_bn_mfma(n, cin, *tail)
+            else:
+                L.proj_group_bwd_weight_bn(dt, n, cin, *tail)
+        else:  # frozen projections: their weight-gradient launch, slabs and folds are left out
+            dws, dbs = [None] * n, [None] * n
         if mfma and ctx.cfg.training:
             # BatchNorm backward straight from `dout`: dz = dout . W is recomputed on the matrix cores by the reduce and the apply pass
             # (proj_bn_mfma.hip) instead of being written once and read twice (839 MB at the stride-8 level)
@@ -1532,13 +1570,15 @@ class FusedConvBNProjFn(torch.autograd.Function):
             L.bn_bwd_finalize(part.data_ptr(), nblk, Ct, P, dgb[0].data_ptr(), dgb[1].data_ptr(), 0, stats[4].data_ptr(), stats[5].data_ptr(), st)
             dy = nhwc_empty(B, Ct, H, W, dtype, dev)
             L.proj_group_bn_bwd(1, *args, stats[4].data_ptr(), stats[5].data_ptr(), act, None, 0, dy.data_ptr(), Ct, P, Ct, st)
-            dx, dW, dg, db, _ = _cba_backward(ctx.cfg, saved, None, ctx.needs_input_grad[0], False, None, pre=(dy, dgb), dx_out=dx_out)
+            dx, dW, dg, db, _ = _cba_backward(ctx.cfg, saved, None, ctx.needs_input_grad[0], False, None, pre=(dy, dgb), dx_out=dx_out, need_dw=need_dw)
         else:
             dz = nhwc_empty(B, Ct, H, W, dtype, dev)
             L.proj_group_bwd_data(dt, n, cin, dout.data_ptr(), dout.stride(3), c_off, c_w, c_co, dz.data_ptr(), Ct, P, st)
-            dx, dW, dg, db, _ = _cba_backward(ctx.cfg, saved, dz, ctx.needs_input_grad[0], False, None, dx_out=dx_out)
+            dx, dW, dg, db, _ = _cba_backward(ctx.cfg, saved, dz, ctx.needs_input_grad[0], False, None, dx_out=dx_out, need_dw=need_dw)
         cs = ctx.couts_stack
-        return (dx, None, None, None, None, None, *dW.split(cs), *dg.split(cs), *db.split(cs), *dws, *dbs)
+        if all(need_stack) and all(need_proj):
+            return (dx, None, None, None, None, None, *dW.split(cs), *dg.split(cs), *db.split(cs), *dws, *dbs)
+        return (dx, None, None, None, None, None, *_masked(_stack_grads(dW, dg, db, cs), need_stack), *_masked(dws + dbs, need_proj))
 
 
 def _dense_any(x, dtype):
@@ -1873,8 +1913,10 @@ class ConvGroupNormFn(torch.autograd.Function):
             dy = dys[i]
             if (plan.Ho, plan.Wo) != tuple(size):
                 dy = resize_bilinear_adjoint(dy, (plan.Ho, plan.Wo))
-            dx, dW = _conv_backward(plan, (xin, w32), dy, (None, None), None, ctx.needs_input_grad[1 + 5 * i], None)[:2]
-            grads += [dx, dW, dbconv[i], dgamma[i], dbeta[i]]
+            need = ctx.needs_input_grad[1 + 5 * i:6 + 5 * i]  # x, w, b, gamma, beta of branch i
+            dx, dW = _conv_backward(plan, (xin, w32), dy, (None, None), None, need[0], None, need_dw=need[1])[:2]
+            # (the GroupNorm apply pass folds dgamma / dbeta / db_conv beside dy: frozen ones are computed and dropped here)
+            grads += _masked([dx, dW, dbconv[i], dgamma[i], dbeta[i]], need)
         return tuple(grads)
 
 
@@ -1919,11 +1961,15 @@ class DepthClassifierFn(torch.autograd.Function):
         dy[:, :co].copy_(dz)
         L = lib()
         M = B * H * W
-        part = _f32(L.colsum_blocks(M) * cp, dz.device)
-        db = _f32(cp, dz.device)
-        L.colsum(code(plan.dtype), dy.data_ptr(), cp, M, cp, part.data_ptr(), db.data_ptr(), stream())
-        dx, dW = _conv_backward(plan, (xin, wpad), dy, (None, None), None, ctx.needs_input_grad[0], None, registry=False)[:2]
-        return dx, dW[:co], db[:co], None, None
+        need = ctx.needs_input_grad
+        db = None
+        if need[2]:
+            part = _f32(L.colsum_blocks(M) * cp, dz.device)
+            db = _f32(cp, dz.device)
+            L.colsum(code(plan.dtype), dy.data_ptr(), cp, M, cp, part.data_ptr(), db.data_ptr(), stream())
+            db = db[:co]
+        dx, dW = _conv_backward(plan, (xin, wpad), dy, (None, None), None, need[0], None, registry=False, need_dw=need[1])[:2]
+        return dx, dW[:co] if need[1] else None, db, None, None
 
 
 def depth_expect(logits, bins):

@@ -326,6 +326,60 @@ class BaseModel(nn.Module):
         self.load_state_dict(ok, strict=False)
         return len(ok), len(own)
 
+    def load_pretrained_body(self, source):
+        """What the reference's `get_model` does with a pretrained 2D YOLOv10 of the same scale (models/yolov10_3D/train.py:50-62), from
+        something local: every layer `model[i]` but the detection head receives the parameters and buffers of `source`'s layer i; the
+        head is untouched.  source: a model of this package (2D or 3D), a state_dict, or a path to a file - a checkpoint of
+        train.Trainer (its "ema", else its "model") or a plain state_dict, read with weights_only=True (a file of pickled model
+        objects, as the reference's .pt files are, is refused).  Strict per layer: a missing key, a shape mismatch or a layer of another
+        module type raises, naming the key, before anything is copied.  -> the number of tensors copied."""
+        src_types = None
+        if isinstance(source, nn.Module):
+            sd = source.state_dict()
+            if hasattr(source, "model"):
+                src_types = [type(m).__name__ for m in source.model]
+        elif isinstance(source, dict):
+            sd = source
+        else:
+            import pickle
+            import numpy as np
+            # a trainer checkpoint keeps numpy's random state beside its state_dicts: plain arrays, allowed by name; nothing else is
+            ma = getattr(np, "_core", None) or np.core
+            allow = [np.ndarray, np.dtype, ma.multiarray._reconstruct, type(np.dtype(np.uint32))]
+            try:
+                with torch.serialization.safe_globals(allow):
+                    sd = torch.load(source, map_location="cpu", weights_only=True)
+            except pickle.UnpicklingError as e:
+                raise Y3DError(f"load_pretrained_body: {source} holds pickled objects (a whole model, as the reference's .pt files do), "
+                               f"which are not loaded; export a state_dict from it (torch.save(model.state_dict(), path)) [{e}]") from None
+        if isinstance(sd, dict) and not all(torch.is_tensor(v) for v in sd.values()):
+            sd = sd.get("ema") or sd.get("model")
+        if not (isinstance(sd, dict) and sd and all(isinstance(k, str) and torch.is_tensor(v) for k, v in sd.items())):
+            raise Y3DError("load_pretrained_body: no state_dict found (a model, a state_dict, a trainer checkpoint or a state_dict file is expected)")
+        body = [i for i, m in enumerate(self.model) if not isinstance(m, (Detect, v10Detect3d))]
+        pairs = []
+        for i in body:
+            if src_types is not None and (i >= len(src_types) or src_types[i] != type(self.model[i]).__name__):
+                raise Y3DError(f"load_pretrained_body: model.{i} is a {type(self.model[i]).__name__}, the source's layer {i} is "
+                               f"{src_types[i] if i < len(src_types) else 'missing'} (another yaml?)")
+            own = self.model[i].state_dict(prefix=f"model.{i}.")
+            extra = [k for k in sd if k.startswith(f"model.{i}.") and k not in own]
+            if extra:
+                raise Y3DError(f"load_pretrained_body: the source's {extra[0]} has no counterpart: layer {i} is another module "
+                               f"(another scale or yaml?) than this model's {type(self.model[i]).__name__}")
+            for k, t in own.items():
+                if k not in sd:
+                    raise Y3DError(f"load_pretrained_body: the source has no {k}")
+                if sd[k].shape != t.shape:
+                    raise Y3DError(f"load_pretrained_body: {k} is {tuple(sd[k].shape)} in the source and {tuple(t.shape)} here "
+                                   "(another scale or yaml?)")
+                pairs.append((t, sd[k]))
+        with torch.no_grad():  # (state_dict tensors share the parameters' / buffers' storage)
+            for t, v in pairs:
+                t.copy_(v)
+        ops.bump_weight_epoch()
+        return len(pairs)
+
 
 class DetectionModel(BaseModel):
     """reference tasks.py:283-318"""

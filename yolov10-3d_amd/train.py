@@ -34,6 +34,9 @@ skipped on the device and the EMA update with it (optim.FusedSGD.step); there is
 `on_epoch_end` hook, no
 plots of training samples, no time limit, no AutoBatch, no multi-GPU.
 
+Frozen layers (`freeze`, engine/trainer.py:247-267): `freeze_layer_names` / `apply_freeze` restate the rule; the autograd functions of
+ops.py read `needs_input_grad` per parameter, so a frozen layer launches no weight gradient and a frozen prefix no backward at all.
+
 Hierarchical task learning (`htl`, engine/trainer.py:349-358, 398-400, 498-512 + utils/htl.py): `HtlWeights` keeps the reference's
 `Hierarchical_Task_Learning` state on the device and `y3d_htl_update` restates `compute_weight` there; the criterion reads the 12 weights
 from that table (loss.DetectLoss3d.set_item_weights -> y3d_loss3d_weighted), so nothing about the weights crosses to the host but the
@@ -137,6 +140,68 @@ def preprocess_batch(batch):
     return batch
 
 
+ALWAYS_FROZEN = (".dfl",)  # engine/trainer.py:255
+
+
+def _freeze_indices(freeze):
+    """the layer indices of a `freeze` setting: None -> none, an int n -> 0..n-1, a list / tuple / range of ints -> themselves"""
+    if freeze is None:
+        return []
+    if isinstance(freeze, bool):
+        raise Y3DError(f"freeze = {freeze}: a bool is not a layer count; pass None, an int n (layers 0..n-1) or a list of layer indices")
+    if isinstance(freeze, int):
+        if freeze < 0:
+            raise Y3DError(f"freeze = {freeze}: a layer count cannot be negative")
+        return list(range(freeze))
+    if isinstance(freeze, (list, tuple, range)):
+        idx = list(freeze)
+        bad = [i for i in idx if isinstance(i, bool) or not isinstance(i, int) or i < 0]
+        if bad:
+            raise Y3DError(f"freeze = {freeze!r}: layer indices are non-negative ints (got {bad})")
+        return idx
+    raise Y3DError(f"freeze = {freeze!r}: pass None, an int n (layers 0..n-1) or a list of layer indices")
+
+
+def freeze_layer_names(freeze):
+    """Host only.  engine/trainer.py:248-256: the substrings that freeze a parameter: "model.{i}." per layer index, then the always
+    frozen ".dfl".  A bool is refused (the reference reads True as range(1))."""
+    return [f"model.{i}." for i in _freeze_indices(freeze)] + list(ALWAYS_FROZEN)
+
+
+def normalize_freeze(freeze):
+    """the form a checkpoint keeps: None, an int, or a list of ints"""
+    _freeze_indices(freeze)
+    return freeze if freeze is None or isinstance(freeze, int) else [int(i) for i in freeze]
+
+
+def apply_freeze(model, freeze):
+    """engine/trainer.py:257-267 -> the names of the frozen parameters.  A parameter whose name holds one of `freeze_layer_names(freeze)`
+    gets requires_grad = False; a floating-point parameter that matches none and arrives frozen is set back to True.  Where this
+    differs, on purpose: a layer index past the model's last layer raises (the reference trains everything, silently); a bool raises; a
+    freeze that leaves nothing to train raises; `DepthPredictor.depth_bin_values` - a constant table created with requires_grad =
+    False that nothing differentiable reads - stays as it is.  Only the flags change: BatchNorm layers of frozen modules stay in
+    training mode, as in the reference.  The flags survive the head's restack (it re-points `.data`, the Parameter objects stay)."""
+    idx = _freeze_indices(freeze)
+    layers = getattr(model, "model", None)
+    nl = len(layers) if hasattr(layers, "__len__") else 0
+    bad = sorted({i for i in idx if i >= nl})
+    if bad:
+        raise Y3DError(f"freeze: layer {', '.join(map(str, bad))} does not exist (the model has layers 0..{nl - 1})")
+    names = freeze_layer_names(freeze)
+    named = list(model.named_parameters())
+    frozen = [k for k, _ in named if any(x in k for x in names)]
+    hit = set(frozen)
+    if not any(k not in hit and v.dtype.is_floating_point and not k.endswith("depth_bin_values") for k, v in named):
+        raise Y3DError(f"freeze = {freeze!r} leaves no trainable parameter")
+    for k, v in named:
+        if k in hit:
+            v.requires_grad = False
+        elif not v.requires_grad and v.dtype.is_floating_point and not k.endswith("depth_bin_values"):
+            v.requires_grad = True
+    model.freeze_layers = sorted(set(idx))  # graph.GraphedTrainStep reads it
+    return frozen
+
+
 HTL_STAT_EPOCHS, HTL_MAX_EPOCHS = 5, 200  # utils/htl.py:4, never overridden by engine/trainer.py:351
 
 
@@ -193,13 +258,16 @@ class Trainer:
     four resident splits).  validator: `model -> callable -> results dict with "fitness"`, called once with the EMA model.
     fit() seeds numpy, torch and random with `seed` (a resumed run restores their states instead); epoch e is drawn with seed + e.
     htl: hierarchical task learning (module docstring); None follows `model.args.htl`.  3D models only, not with distillation.
+    freeze: None, an int n (layers 0..n-1) or a list of layer indices (`apply_freeze`); kept in `train_args`, so a resumed run re-freezes
+    the same names.  Frozen layers keep BatchNorm in training mode (batch statistics; their running statistics and the EMA move on).
     After fit(): `history` (one dict per epoch: epoch, the loss items by name, htl/<name> weights when htl is on, lr/pg*, the validation
     results, fitness),
     `best_fitness`, `ema`, `opt`."""
 
     def __init__(self, model, train_split, validator=None, epochs=400, batch=32, nbs=64, optimizer="auto", lr0=0.001, lrf=0.01, momentum=0.937,
                  weight_decay=0.0005, warmup_epochs=3.0, warmup_momentum=0.8, warmup_bias_lr=0.1, cos_lr=False, close_mixup=0, close_mosaic=0,
-                 val_period=1, patience=150, save_dir=None, save_period=-1, seed=0, data_args=None, max_norm=10.0, resume=None, htl=None):
+                 val_period=1, patience=150, save_dir=None, save_period=-1, seed=0, data_args=None, max_norm=10.0, resume=None, htl=None,
+                 freeze=None):
         if htl is None:
             htl = getattr(getattr(model, "args", None), "htl", False)
         margs = getattr(model, "args", None)
@@ -232,6 +300,12 @@ class Trainer:
             if self.ckpt["epoch"] + 1 >= int(epochs) or self.ckpt["epoch"] < 0:
                 raise Y3DError(f"{resume} training to {int(epochs)} epochs is finished, nothing to resume.\n"
                                "Start a new training without resuming, i.e. Trainer(...) without resume")
+            # the freeze is the checkpoint's (checkpoints from before `freeze` froze nothing); an explicit one has to agree with it
+            kept = self.ckpt["train_args"].get("freeze")
+            if freeze is not None and normalize_freeze(freeze) != kept:
+                raise Y3DError(f"Trainer: freeze = {freeze!r} disagrees with the checkpoint's freeze = {kept!r}: a resumed run keeps the "
+                               "frozen set it was started with (its optimizer state is laid out over the trainable parameters)")
+            freeze = kept
         dev = next(model.parameters()).device
         if dev.type != "cuda":
             raise Y3DError(f"Trainer: the model must live on a HIP device, not {dev} (no host fallback)")
@@ -243,7 +317,8 @@ class Trainer:
         self.train_args = dict(epochs=self.epochs, batch=self.batch, nbs=self.nbs, optimizer=optimizer, lr0=lr0, lrf=lrf, momentum=momentum,
                                weight_decay=weight_decay, warmup_epochs=warmup_epochs, warmup_momentum=warmup_momentum,
                                warmup_bias_lr=warmup_bias_lr, cos_lr=bool(cos_lr), close_mixup=close_mixup, close_mosaic=close_mosaic,
-                               val_period=val_period, patience=patience, save_period=save_period, seed=seed, max_norm=max_norm)
+                               val_period=val_period, patience=patience, save_period=save_period, seed=seed, max_norm=max_norm,
+                               freeze=normalize_freeze(freeze))
         self.val_period, self.save_period, self.seed, self.max_norm = int(val_period), int(save_period), int(seed), max_norm
         self.close_mixup, self.close_mosaic = int(close_mixup), int(close_mosaic)
         self.save_dir = save_dir
@@ -253,6 +328,8 @@ class Trainer:
         self.data_args = data_args
         self.nb = math.ceil(n / self.batch)
         self.plan = plan(n, self.batch, self.epochs, self.nbs, warmup_epochs)
+        # engine/trainer.py:247-267, before the optimizer, the EMA and the accumulator size their tables from the flags
+        self.frozen = apply_freeze(model, freeze)
         # engine/trainer.py:307-317
         self.opt = build_optimizer(model, name=optimizer, lr=lr0, momentum=momentum, decay=scaled_weight_decay(weight_decay, self.batch, self.nbs),
                                    iterations=optimizer_iterations(n, self.batch, self.epochs, self.nbs), device_momentum=True)
@@ -308,7 +385,10 @@ class Trainer:
     def checkpoint(self, epoch):
         opt_sd = self.opt.state_dict(torch_format=True, native=True)
         cpu = lambda sd: {k: v.detach().cpu().clone() for k, v in sd.items()}
-        rng = {"numpy": np.random.get_state(), "torch": torch.get_rng_state(), "torch_cuda": torch.cuda.get_rng_state(self.device),
+        # numpy's state with its key array as a tensor: the file then holds tensors and plain Python values only, so that
+        # BaseModel.load_pretrained_body can read it with weights_only=True
+        kind, keys, *rest = np.random.get_state()
+        rng = {"numpy": (kind, torch.from_numpy(keys.astype(np.int64)), *rest), "torch": torch.get_rng_state(), "torch_cuda": torch.cuda.get_rng_state(self.device),
                "random": random.getstate()}
         ck = {"epoch": epoch, "best_fitness": self.best_fitness, "model": cpu(self.model.state_dict()),
               "ema": {k: (v.float() if v.is_floating_point() else v) for k, v in cpu(self.ema.ema.state_dict()).items()},
@@ -384,7 +464,8 @@ class Trainer:
         else:
             rng = self.ckpt["rng"]
             random.setstate(rng["random"])
-            np.random.set_state(rng["numpy"])
+            kind, keys, *rest = rng["numpy"]  # (older checkpoints keep the key array as numpy's)
+            np.random.set_state((kind, np.asarray(keys.numpy() if torch.is_tensor(keys) else keys, dtype=np.uint32), *rest))
             torch.set_rng_state(rng["torch"])
             torch.cuda.set_rng_state(rng["torch_cuda"], self.device)
             self.ckpt = None
