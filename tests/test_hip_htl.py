@@ -213,19 +213,19 @@ class Run:
         bufs = [TR.sentinel((B * h * w * no + 2 * GUARD,), self.dtype, DEV) for h, w in zip(Hs, Ws)]
         esz = bufs[0].element_size()
         cfg = self.crit.cfg(len(maps))
-        assert len(cfg) == 8
+        assert cfg.item_w is None and cfg.store_grads
         if table is not None:
-            cfg = cfg + (table, store)
+            cfg = cfg._replace(item_w=table, store_grads=store)
         r = PL._loss3d_set(cfg, self.gt.float().contiguous(), self.n_used, self.db["calib"].float().contiguous(), self.db["mean_sizes"].float().contiguous(),
-                           [m.data_ptr() for m in maps], [m.stride(3) for m in maps], [b.data_ptr() + GUARD * esz for b in bufs] if store else None,
-                           [no] * len(maps), Hs, Ws, B, self.dtype, DEV)
+                           PL.Levels([m.data_ptr() for m in maps], [m.stride(3) for m in maps], Hs, Ws, cfg.strides),
+                           [b.data_ptr() + GUARD * esz for b in bufs] if store else None, [no] * len(maps), B, self.dtype, DEV)
         torch.cuda.synchronize()
         for b in bufs:
             assert bool(TR.untouched(b[:GUARD]).all() and TR.untouched(b[-GUARD:]).all()), "a gradient row went outside its map"
         rows = [b[GUARD:-GUARD].view(B, h, w, no).cpu() for b, h, w in zip(bufs, Hs, Ws)]
         if store:
             assert not any(bool(TR.untouched(x).any()) for x in rows), "an anchor's row was not written"
-        return r[0].cpu(), rows, (r[4].cpu() if len(r) > 4 else None), r[1].cpu()
+        return r.items.cpu(), rows, (r.total.cpu() if r.total is not None else None), r.fg.cpu()
 
 
 def fold(items, w):
@@ -356,7 +356,7 @@ def test_criterion_takes_the_table_and_none_restores_the_calls():
     assert abs(float(l0) - B * float(i0.sum())) < 1e-5 * float(l0)
     t = table_of(GENERAL)
     crit.set_item_weights(t)
-    assert len(crit.cfg(3)) == 10
+    assert crit.cfg(3).item_w is t
     l1, i1, g1 = go()
     assert same_bits(i1, i0) and np.float32(l1) == fold(i0, GENERAL)
     w = torch.tensor(GENERAL)[item_of_channel(3)].view(1, -1, 1, 1)
@@ -368,7 +368,7 @@ def test_criterion_takes_the_table_and_none_restores_the_calls():
     l3, i3, g3 = go(no_grad=True)
     assert same_bits(i3, i0) and l3 == l2 and all(g is None for g in g3) and not l3.requires_grad
     crit.set_item_weights(None)
-    assert len(crit.cfg(3)) == 8
+    assert crit.cfg(3).item_w is None
     l4, i4, g4 = go()
     assert l4 == l0 and same_bits(i4, i0) and all(same_bits(a, b) for a, b in zip(g4, g0))
     with pytest.raises(Y3DError, match="set_item_weights"):

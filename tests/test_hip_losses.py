@@ -174,9 +174,9 @@ def test_row_bound_from_pad_targets_changes_nothing(fam, boxes):
         if fam == "3d":
             r = PL.Loss3dFn.apply(crit.cfg(len(dm)), g, nu, db["calib"], db["mean_sizes"], *dm)
         else:
-            cfg = (crit.stride[:len(dm)], crit.nc, crit.topk, 0.5, 6.0, (RS.HYP["box"], RS.HYP["cls"], RS.HYP["dfl"]))
+            cfg = PL.LossCfg2d(crit.stride[:len(dm)], crit.nc, crit.topk, 0.5, 6.0, (RS.HYP["box"], RS.HYP["cls"], RS.HYP["dfl"]))
             r = PL.Loss2dFn.apply(cfg, g, nu, *dm)
-        out.append([t.cpu() for t in r[1:]])
+        out.append([t.cpu() for t in r[1:5]])
     for x, y, nm in zip(out[0], out[1], ("items", "fg_mask", "target_gt_idx", "target_scores")):
         assert torch.equal(x, y), f"{nm} depends on the padded row bound"
     assert out[0][1].any()
@@ -289,8 +289,8 @@ def test_dual_path_upstream_gradient_scales_per_set(dname):
     db = {k: v.to(DEV) for k, v in batch.items()}
     g, n_used = crit.one2one.targets(db, B, bases[0].shape[2], bases[0].shape[3], DEV)
     nl = len(bases)
-    t1, i1, tm, im, fg1, gi1, ts1, fgm, gim, tsm = PL.DualLoss3dFn.apply(crit.one2one.cfg(nl), crit.one2many.cfg(nl), g, n_used, db["calib"],
-                                                                         db["mean_sizes"], *bases)
+    t1, i1, fg1, gi1, ts1, _, tm, im, fgm, gim, tsm, _ = PL.DualLoss3dFn.apply(crit.one2one.cfg(nl), crit.one2many.cfg(nl), g, n_used, db["calib"],
+                                                                               db["mean_sizes"], *bases)
     (2.5 * tm + 0.25 * t1).backward()
     for case, maps, a, dev, it, half, wgt in ((cm, mm, am, (fgm, gim, tsm), im, slice(no, 2 * no), 2.5), (c1, m1, a1, (fg1, gi1, ts1), i1, slice(0, no), 0.25)):
         dev = (dev[0].bool().cpu(), dev[1].long().cpu(), dev[2].cpu())

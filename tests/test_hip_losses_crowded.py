@@ -93,8 +93,8 @@ def test_row_bound_changes_nothing_on_the_crowded_route():
     out = []
     for nu in (n_used, None):
         dm = [m.detach() for m in THL.device_maps(maps, torch.float32)]
-        cfg = (crit.stride[:len(dm)], crit.nc, crit.topk, 0.5, 6.0, (1.0, 1.0, 1.0))
-        out.append([t.cpu() for t in PL.Loss2dFn.apply(cfg, g, nu, *dm)[1:]])
+        cfg = PL.LossCfg2d(crit.stride[:len(dm)], crit.nc, crit.topk, 0.5, 6.0, (1.0, 1.0, 1.0))
+        out.append([t.cpu() for t in PL.Loss2dFn.apply(cfg, g, nu, *dm)[1:5]])
     for x, y, nm in zip(out[0], out[1], ("items", "fg_mask", "target_gt_idx", "target_scores")):
         assert torch.equal(x, y), f"{nm} depends on the padded row bound"
     assert out[0][1].any()

@@ -23,6 +23,9 @@ each arm makes are in the trace):
   head glue       HeadProjFn narrow and wide arm, forward and backward (2D head); HeadProjSlicesFn / FusedConvBNProjFn on the VALU forms
                   (16-wide tiny head, PROJ_BN_MFMA off) and on the matrix-core forms (128-wide head); proj_slices_eval on both;
                   conv_bias_act_eval (the model folded the reference's way)
+  loss glue       (`loss/...` cases, through the criterion classes of loss.py) Loss3dFn; DualLoss3dFn at an odd element offset; the
+                  weighted entry with and without a gradient-pointer array; DistillFn forward, its dense backward (two calls) and the
+                  compact rows through the head's slots; Loss2dFn on the dense and on the crowded assigner; FgdmLossFn forward + backward
 Not reached: the eval arm of `_bn_act_tail` without `bn_apply` (statistics rows built from the cached scale / shift pair).  Its only
 caller, FusedConvBNProjFn, runs in the training forward alone, and the arm makes no launch.
 """

@@ -50,7 +50,7 @@ def main():
     g = torch.Generator().manual_seed(0)
     maps = [y3d.ops._dense_any(torch.randn(B, 64 + nc, int(S // s), int(S // s), generator=g).to(dev), torch.bfloat16) for s in strides]
     A = sum(m.shape[2] * m.shape[3] for m in maps)
-    cfg = (strides, nc, 10, 0.5, 6.0, (7.5, 0.5, 1.5))
+    cfg = PL.LossCfg2d(strides, nc, 10, 0.5, 6.0, (7.5, 0.5, 1.5))
 
     def call(gt, n_used):
         return PL.Loss2dFn.apply(cfg, gt, n_used, *maps)

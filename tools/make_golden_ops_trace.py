@@ -18,7 +18,10 @@ reference's way; the stem on uint8 images; the 128-wide head of tests/test_hip_f
 PROJ_BN_MFMA off; the 2D `v10Detect` head with a wide and a narrow projection; eval Bottlenecks with a shortcut on both residual arms;
 the stacking layouts of `modules.v10Detect3d` that the models above do not have (`head3d_layout`: cls wider than the regression
 branches with every / some / no part on the fused BatchNorm projections, the uniform layout unfused at 64 channels, no second-layer
-stack, the distillation node), each in training and in eval.
+stack, the distillation node), each in training and in eval; the loss glue (`loss/...`) through the public criterion classes on the
+smallest cases of the loss tests: DDDetectionLoss on separate maps, DetectLoss3d on shared maps (nc = 2: an odd element offset), the
+same with an item-weight table (with grad, under no_grad, the table taken away again), with distillation through both ways back into
+the head, v10DetectLoss on the dense and on the crowded assigner, ForegroundDepthMapLoss.
 """
 from __future__ import annotations
 
@@ -326,6 +329,129 @@ def bottleneck_eval():
     torch.cuda.synchronize()
 
 
+# ---- the loss glue: the public criterion classes of loss.py on the smallest cases of the loss tests ------------------------------------
+def _on_device(maps, dtype, grad=True):
+    from yolov10_3d_amd import ops
+    return [ops._dense_any(m.to(DEV), dtype).requires_grad_(grad) for m in maps]
+
+
+def loss3d_single():
+    """DDDetectionLoss on separate maps (the Loss3dFn route): tests/test_hip_htl.py's B = 4, nc = 3 case, 64 + 16 + 4 anchors per image"""
+    import torch
+    import loss_ref as LR
+    from test_hip_htl import CASES as HTL_CASES
+    from yolov10_3d_amd import loss as PL
+    case = HTL_CASES["b4_nc3_nl3"]
+    with compute_dtype(torch.float32):
+        batch, B = LR.make_batch(case)
+        crit = PL.DDDetectionLoss(LR.model_of(case), tal_topk=case["topk"])
+        loss, _ = crit(_on_device(LR.make_maps(case), torch.float32), {k: v.to(DEV) for k, v in batch.items()})
+        loss.backward()
+    torch.cuda.synchronize()
+
+
+def _dual_odd(dtype):
+    """DetectLoss3d + the head's own (B, 2 * no, H, W) maps of loss_ref's l3_dual_o2o / l3_dual_o2m pair (nc = 2, no = 37) + the batch"""
+    import torch
+    import loss_ref as LR
+    from yolov10_3d_amd import loss as PL
+    c1, cm = LR.BY_NAME["l3_dual_o2o"], LR.BY_NAME["l3_dual_o2m"]
+    batch, B = LR.make_batch(c1)
+    no = c1["nc"] + 35
+    crit = PL.DetectLoss3d(LR.model_of(cm))
+
+    def preds():
+        bases = _on_device([torch.cat((x, y), 1) for x, y in zip(LR.make_maps(c1, dtype), LR.make_maps(cm, dtype))], dtype)
+        return {"one2one": [b[:, :no] for b in bases], "one2many": [b[:, no:] for b in bases], "_y3d_maps": bases}
+
+    return crit, preds, {k: v.to(DEV) for k, v in batch.items()}
+
+
+def loss3d_dual_odd():
+    """DetectLoss3d on shared maps, bf16: the DualLoss3dFn route with the one-to-many half at an odd element offset"""
+    import torch
+    with compute_dtype(torch.bfloat16):
+        crit, preds, batch = _dual_odd(torch.bfloat16)
+        loss, _ = crit(preds(), batch)
+        loss.backward()
+    torch.cuda.synchronize()
+
+
+def loss3d_weighted():
+    """the same criterion with an item-weight table: with grad, under no_grad (a null gradient-pointer array), and after
+    set_item_weights(None)"""
+    import torch
+    with compute_dtype(torch.float32):
+        crit, preds, batch = _dual_odd(torch.float32)
+        crit.set_item_weights(torch.linspace(0.5, 1.6, 12, device=DEV))
+        loss, _ = crit(preds(), batch)
+        loss.backward()
+        with torch.no_grad():
+            crit(preds(), batch)
+        crit.set_item_weights(None)
+        loss, _ = crit(preds(), batch)
+        loss.backward()
+    torch.cuda.synchronize()
+
+
+def loss3d_distill(fused):
+    """DetectLoss3d with `distillation: True` behind the two-level 12x12 + 8x8 head of tests/test_hip_distill.py, the teacher map in the
+    batch.  fused: the head's shared maps and z1 slots (compact rows, ops.InjectRowsFn); else the per-branch head: two calls and dense
+    embedding gradients (DistillFn.backward)."""
+    import torch
+    from types import SimpleNamespace
+    import yolov10_3d_amd as y3d
+    from bench import synth_batch
+    from test_hip_distill import _head
+    from yolov10_3d_amd import loss as PL
+    with compute_dtype(torch.float32):
+        hd = _head((64, 64), DEV)
+        hd.fused = fused
+        hyp = dict(y3d.tasks.DEFAULT_HYP, distillation=True, distillation_temp=2.0, distillation_weight=1.0, distillation_loss="soft",
+                   distillation_no_mixup=True)
+        crit = PL.DetectLoss3d(SimpleNamespace(model=[hd], args=SimpleNamespace(**hyp)))
+        g = torch.Generator().manual_seed(8)
+        xs = [torch.randn(2, 32, 12, 12, generator=g).to(DEV).requires_grad_(True), torch.randn(2, 64, 8, 8, generator=g).to(DEV).requires_grad_(True)]
+        batch = synth_batch(2, 96, 96, 5, DEV)
+        batch["mixed"] = torch.tensor([0, 0], dtype=torch.uint8, device=DEV)
+        batch["teacher_emb"] = torch.randn(2, 64, 5, 7, generator=g).to(DEV)
+        out = hd(xs)
+        assert ("_y3d_distill" in out) == fused
+        loss, items = crit(out, batch)
+        assert items.numel() == 14
+        loss.backward()
+    torch.cuda.synchronize()
+
+
+def loss2d(max_boxes):
+    """v10DetectLoss: max_boxes=None on loss_ref's one-level 2D case (the dense assigner), max_boxes=128 on the 65-box crowd"""
+    import torch
+    import crowded_cases as CC
+    import loss_ref as LR
+    from yolov10_3d_amd import loss as PL
+    case = LR.BY_NAME["l2_nl1"] if max_boxes is None else CC.BY_NAME["c65_nc1_k10"]
+    with compute_dtype(torch.float32), CC.registered():
+        batch, B = LR.make_batch(case)
+        maps = LR.make_maps(case, seed=case["seeds"]["fp32"] if max_boxes else None)
+        crit = PL.v10DetectLoss(LR.model_of(case), max_boxes=max_boxes)
+        loss, _ = crit({"one2many": _on_device(maps, torch.float32), "one2one": _on_device(maps, torch.float32)}, {k: v.to(DEV) for k, v in batch.items()})
+        loss.backward()
+        PL.check_target_overflow(wait=True)
+    torch.cuda.synchronize()
+
+
+def loss_fgdm():
+    """ForegroundDepthMapLoss on logits (2, 81, 2, 3) and float32 depth maps (2, 32, 48), forward + backward"""
+    import torch
+    from types import SimpleNamespace
+    from yolov10_3d_amd import loss as PL
+    g = torch.Generator().manual_seed(4)
+    z = torch.randn(2, 81, 2, 3, generator=g).to(DEV).requires_grad_(True)
+    dm = (torch.rand(2, 32, 48, generator=g) * 60.0 * (torch.rand(2, 32, 48, generator=g) > 0.5)).to(DEV)
+    PL.ForegroundDepthMapLoss(SimpleNamespace(min_depth_threshold=1, max_depth_threshold=120))(z, dm).backward()
+    torch.cuda.synchronize()
+
+
 CASES = {
     "tiny/bf16": lambda: tiny("bf16"),
     "tiny/f32": lambda: tiny("f32"),
@@ -350,6 +476,14 @@ CASES = {
     "head3d/uniform/unfused": head3d_uniform_unfused,
     "head3d/no_stack": head3d_no_stack,
     "head3d/distill": head3d_distill,
+    "loss/3d/single": loss3d_single,
+    "loss/3d/dual_odd": loss3d_dual_odd,
+    "loss/3d/weighted": loss3d_weighted,
+    "loss/3d/distill/two_call": lambda: loss3d_distill(False),
+    "loss/3d/distill/slots": lambda: loss3d_distill(True),
+    "loss/2d/dense": lambda: loss2d(None),
+    "loss/2d/crowded": lambda: loss2d(128),
+    "loss/fgdm": loss_fgdm,
 }
 
 # the head layout cases: (launches a case must hold, launches it must not), looked at when the fixture is minted
@@ -389,7 +523,7 @@ def run_case(name):
     return json.loads(json.dumps(calls))
 
 
-# ---- which arms of the conv + BatchNorm + activation glue a trace reaches --------------------------------------------------------
+# ---- which arms of the conv + BatchNorm + activation glue and of the loss glue a trace reaches -------------------------------------
 def _has(name, cond=lambda a: True):
     return lambda calls: any(c[0] == name and cond(c[1]) for c in calls)
 
@@ -430,6 +564,15 @@ ARMS = {
     "FusedConvBNProjFn: matrix-core forms": _has("proj_group_bn_bwd"),
     "proj_slices_eval: matrix-core form": _has("proj_group_fwd_bn_mfma", lambda a: a[10] == 0),
     "conv_bias_act_eval (folded model)": _has("bn_eval_scale", lambda a: a[5] == 0.0),
+    "Loss2dFn: dense assigner": _has("tal2d_assign"),
+    "Loss2dFn: crowded assigner": _has("tal2d_assign_crowded"),
+    "Loss2dFn: loss + gradient rows": _has("loss2d"),
+    "_loss3d_set: weighted entry with a gradient-pointer array": _has("loss3d_weighted", lambda a: a[4] != 0),
+    "_loss3d_set: weighted entry under no_grad (null gradient-pointer array)": _has("loss3d_weighted", lambda a: a[4] == 0),
+    "DistillFn: forward": _has("distill_loss"),
+    "DistillFn: backward, dense embedding gradient (pixel stride = width)": _has("distill_scatter", lambda a: a[10] == a[6]),
+    "FgdmLossFn: forward": _has("fgdm_loss"),
+    "FgdmLossFn: backward": _has("fgdm_scale"),
 }
 
 

@@ -7,8 +7,12 @@ under autocast's fp32 policy), on the tensors' own device.
 
 Both training losses (3D: DetectLoss3d / DDDetectionLoss, 2D: v10DetectLoss / v8DetectionLoss — target padding, assignment, the loss
 terms and the gradient wrt the head maps) run on the fused HIP kernels of csrc/tal_loss3d.hip / tal_loss2d.hip (`Loss3dFn`,
-`Loss2dFn`).  Tie rule of the top-k is pinned to lowest-index-first.  Torch formulations of the assigners used
-as test comparators live in tests/torch_assigners.py, not here.
+`DualLoss3dFn`, `Loss2dFn`).  Tie rule of the top-k is pinned to lowest-index-first.  Torch formulations of the
+assigners used as test comparators live in tests/torch_assigners.py, not here.
+
+The glue between the criteria and the kernels passes named records: `LossCfg3d` / `LossCfg2d` (what a head set's
+kernels are told), `Levels` (the per-level ctypes arrays of a launch) and `SetResult` (a head set's outputs, the assignment's `scal`
+words among them: the distillation item is handed its own set's).
 
 Feature distillation (`distillation: True`; SupervisionLoss.forward_head :1156-1188): the seventh item of each 3D head set runs on
 csrc/distill.hip (`DistillFn`) over a teacher feature map the caller supplies (batch["teacher_emb"] or `set_teacher`); the DINOv2
@@ -22,8 +26,8 @@ from __future__ import annotations
 import torch
 import torch.nn.functional as F
 
-import contextlib
 import ctypes
+from typing import NamedTuple, Optional
 
 from . import ops
 from ._lib import Y3DError, lib
@@ -111,21 +115,123 @@ def _flatten_maps(feats):
     return torch.cat([f.permute(0, 2, 3, 1).reshape(B, -1, no) for f in feats], 1).float()
 
 
-_SCAL_TAP = None  # a list while a distillation step runs: _loss3d_set appends each set's device words [max(sum(target_scores), 1), n_fg]
+class LossCfg3d(NamedTuple):
+    """what one 3D head set's kernels are told (`DDDetectionLoss.cfg`)"""
+    strides: list
+    nc: int
+    topk: int
+    alpha: float
+    beta: float
+    gamma: float
+    weights: tuple  # the six gains (loss2d, cls, depth, offset3d, size3d, heading)
+    mode: int = 11  # assigner mode bits (include/y3d.h: y3d_tal3d_assign); default tal_2d | tal_3d | constrain_anchors, l1
+    item_w: Optional[torch.Tensor] = None  # 6 device floats (`set_item_weights`): the y3d_loss3d_weighted entry
+    store_grads: bool = True  # False (a weighted call under no_grad): no gradient rows are stored
 
 
-class _tap_scal:
-    """with _tap_scal() as tap: the `scal` words of the head sets assigned inside, in call order (the distillation item divides by
-    the first word, loss.py:898; the word never visits the host)"""
+class LossCfg2d(NamedTuple):
+    """what one 2D head set's kernels are told (`v8DetectionLoss.cfg`)"""
+    strides: list
+    nc: int
+    topk: int
+    alpha: float
+    beta: float
+    weights: tuple  # the three gains (box, cls, dfl)
 
-    def __enter__(self):
-        global _SCAL_TAP
-        self.prev, _SCAL_TAP = _SCAL_TAP, []
-        return _SCAL_TAP
 
-    def __exit__(self, *exc):
-        global _SCAL_TAP
-        _SCAL_TAP = self.prev
+class SetResult(NamedTuple):
+    """one head set's outputs.  scal: the assignment's two device words [max(sum(target_scores), 1), n_fg] (the distillation item
+    divides by the first, loss.py:898; they never visit the host).  total: 1 float = sum(item_w * items) of the weighted entry, else None"""
+    items: torch.Tensor
+    fg: torch.Tensor  # (B, A) uint8
+    gt_idx: torch.Tensor  # (B, A) int32
+    target_scores: torch.Tensor  # (B, A, nc)
+    scal: torch.Tensor
+    total: Optional[torch.Tensor] = None
+
+    def outputs(self):
+        """the six outputs of Loss3dFn / Loss2dFn (and each half of DualLoss3dFn's twelve): the differentiable total first"""
+        total = self.total.reshape(()) if self.total is not None else self.items.sum()
+        return (total, *self[:5])
+
+    @classmethod
+    def of(cls, six):
+        return cls(*six[1:], six[0])
+
+
+class Levels:
+    """the per-level arguments of a launch, built once per call from raw pointers (DualLoss3dFn offsets them by a channel count):
+    nl, A = sum(H * W), and the ctypes arrays maps, psw (pixel strides), H, W, st (strides; None where the kernel takes none)"""
+    __slots__ = ("nl", "A", "maps", "psw", "H", "W", "st")
+
+    def __init__(self, ptrs, psw, Hs, Ws, strides=None):
+        nl = self.nl = len(ptrs)
+        self.A = sum(h * w for h, w in zip(Hs, Ws))
+        self.maps, self.psw = (ctypes.c_void_p * nl)(*ptrs), (ctypes.c_int64 * nl)(*psw)
+        self.H, self.W = (ctypes.c_int * nl)(*Hs), (ctypes.c_int * nl)(*Ws)
+        self.st = (ctypes.c_float * nl)(*strides) if strides is not None else None
+
+    @classmethod
+    def of(cls, maps, strides=None, offset=0):
+        """of (B, C, H, W) NHWC maps, read `offset` bytes behind their first element"""
+        return cls([m.data_ptr() + offset for m in maps], [m.stride(3) for m in maps], [m.shape[2] for m in maps], [m.shape[3] for m in maps], strides)
+
+    def rows(self, ptrs, psw):
+        """the gradient-row arguments: (pointer array or None: nothing is stored, pixel strides)"""
+        return (ctypes.c_void_p * self.nl)(*ptrs) if ptrs is not None else None, (ctypes.c_int64 * self.nl)(*psw)
+
+
+def _check_maps(maps, who, what="head maps"):
+    """every map of a call lives on a HIP device with its channels dense per pixel"""
+    if not all(m.is_cuda and ops.px_dense(m) for m in maps):
+        raise Y3DError(f"{who}: {what} must be pixel-dense NHWC tensors on a HIP device")
+
+
+def _assignment_buffers(nfloats, who, B, A, nc, dev):
+    """what an assigner writes: (scratch of `nfloats`, fg (B, A) uint8, gt_idx (B, A) int32, target_scores (B, A, nc), scal (2,))"""
+    if nfloats < 0:
+        raise Y3DError(f"{who}: assignment scratch exceeds 2^31 floats")
+    return (torch.empty(nfloats, dtype=torch.float32, device=dev), torch.empty(B, A, dtype=torch.uint8, device=dev),
+            torch.empty(B, A, dtype=torch.int32, device=dev), torch.empty(B, A, nc, dtype=torch.float32, device=dev),
+            torch.empty(2, dtype=torch.float32, device=dev))
+
+
+def _item_buffers(B, A, k, dev):
+    """(per-block partial sums, the k loss items) of a loss launch: one block per 256 anchors"""
+    return torch.empty((B * A + 255) // 256 * k, dtype=torch.float32, device=dev), torch.empty(k, dtype=torch.float32, device=dev)
+
+
+def _head_inputs(crit, dim, preds, batch, targets):
+    """the opening of both criteria: preds -> (feats, device, B, image (w, h), targets or None: the batch has no box, maps in the compute dtype)"""
+    feats = preds[1] if isinstance(preds, tuple) else preds
+    dev = feats[0].device
+    if not feats[0].is_cuda:
+        raise Y3DError(f"the {dim} loss runs on the HIP kernels of tal_loss{dim.lower()}.hip: head maps must live on a HIP device (no CPU fallback)")
+    B, (H, W) = feats[0].shape[0], feats[0].shape[2:]
+    if targets is None:
+        targets = crit.targets(batch, B, H, W, dev)
+    dt = ops.compute_dtype()
+    maps = None if targets is None else [f if f.dtype == dt else f.to(dt) for f in feats]
+    return feats, dev, B, (W * crit.stride[0], H * crit.stride[0]), targets, maps
+
+
+def _close_forward(ctx, grads, nmaps, *sets):
+    """the close of the three forwards: the gradient rows kept for the backward -> the six outputs of every set, all but the totals
+    non-differentiable"""
+    ctx.save_for_backward(*grads)
+    ctx.nmaps = nmaps
+    ctx.set_materialize_grads(False)  # no zero-filled gradients for the assignment outputs
+    out = tuple(t for r in sets for t in r.outputs())
+    ctx.mark_non_differentiable(*[t for i, t in enumerate(out) if i % 6])
+    return out
+
+
+def _scaled_rows(ctx, d_total, lead):
+    """the backward of Loss3dFn / Loss2dFn: the rows the forward stored times the incoming scalar, one multiply per level"""
+    grads = ctx.saved_tensors
+    if d_total is None or not grads:
+        return (None,) * (lead + ctx.nmaps)
+    return (None,) * lead + tuple(g * d_total.to(g.dtype) for g in grads)
 
 
 _TEACHER = None
@@ -198,12 +304,12 @@ class DistillFn(torch.autograd.Function):
         L = lib()
         embs, teacher, gt, fg = spec["embs"], spec["teacher"], spec["gt"], spec["fg"]
         dtype, dev = embs[0].dtype, embs[0].device
-        if dtype != ops.compute_dtype() or not all(e.is_cuda and ops.is_nhwc(e) and ops.px_dense(e) for e in embs):
-            raise Y3DError("DistillFn: embeddings must be pixel-dense NHWC tensors of the compute dtype on a HIP device")
-        nl = len(embs)
+        _check_maps(embs, "DistillFn", "embeddings")
+        if dtype != ops.compute_dtype() or not all(ops.is_nhwc(e) for e in embs):
+            raise Y3DError("DistillFn: embeddings must be NHWC tensors of the compute dtype")
         B, C = embs[0].shape[:2]
-        Hs, Ws = [e.shape[2] for e in embs], [e.shape[3] for e in embs]
-        A, n, cap = sum(h * w for h, w in zip(Hs, Ws)), gt.shape[1], int(spec["cap"])
+        lv = Levels.of(embs)
+        A, n, cap = lv.A, gt.shape[1], int(spec["cap"])
         if fg.shape != (B, A):
             raise ValueError(f"DistillFn: fg_mask {tuple(fg.shape)} does not match the {B} x {A} anchors of the embeddings")
         check_teacher(teacher, embs[0])
@@ -217,16 +323,15 @@ class DistillFn(torch.autograd.Function):
         part = torch.empty((cap + 3) // 4, dtype=torch.float32, device=dev)
         item = torch.empty(1, dtype=torch.float32, device=dev)
         mixed = spec["mixed"]
-        L.distill_loss(ops.code(dtype), nl, (ctypes.c_void_p * nl)(*[e.data_ptr() for e in embs]), (ctypes.c_int64 * nl)(*[e.stride(3) for e in embs]),
-                       (ctypes.c_int * nl)(*Hs), (ctypes.c_int * nl)(*Ws), B, C, teacher.data_ptr(), ops.code(teacher.dtype), teacher.shape[2],
+        L.distill_loss(ops.code(dtype), lv.nl, lv.maps, lv.psw, lv.H, lv.W, B, C, teacher.data_ptr(), ops.code(teacher.dtype), teacher.shape[2],
                        teacher.shape[3], *teacher.stride(), gt.data_ptr(), n, fg.data_ptr(), spec["gi"].data_ptr(), spec["scal"].data_ptr(),
                        mixed.data_ptr() if mixed is not None else None, int(spec["img_wh"][0]), int(spec["img_wh"][1]), float(spec["T"]),
                        float(spec["weight"]), int(spec["crit"]), int(bool(spec["no_mixup"])), cap, counts.data_ptr(), idx.data_ptr(), rows.data_ptr(),
                        part.data_ptr(), item.data_ptr(), ops.stream())
         ctx.entries, a0 = [], 0
-        for l in range(nl):
-            ctx.entries.append({"rows": rows, "idx": idx, "nrows": counts[B:], "cap": cap, "C": C, "a0": a0, "scale": None, "shape": (B, C, Hs[l], Ws[l])})
-            a0 += Hs[l] * Ws[l]
+        for h, w in zip(lv.H, lv.W):
+            ctx.entries.append({"rows": rows, "idx": idx, "nrows": counts[B:], "cap": cap, "C": C, "a0": a0, "scale": None, "shape": (B, C, h, w)})
+            a0 += h * w
         ctx.sparse = spec["slots"] is not None
         if ctx.sparse:
             for e, slot in zip(ctx.entries, spec["slots"]):
@@ -362,83 +467,51 @@ def loss_names(args):
     return names
 
 
-def _loss3d_set(cfg, gt, n_used, calib, mean_sizes, map_ptrs, psw, grad_ptrs, gsw, Hs, Ws, B, dtype, dev):
-    """one head set on the HIP kernels: assignment + six loss items + gradient rows written at grad_ptrs (pixel stride gsw).
-    -> (items[6], fg (B, A) uint8, gt_idx (B, A) int32, target_scores (B, A, nc))
-    A cfg with an item-weight table (cfg[8]: 6 device floats, `set_item_weights`) takes y3d_loss3d_weighted instead: the rows come out
-    times the weight of their item, the items as ever, and a fifth result `total` (1 float) = sum(item_w * items); grad_ptrs None (a
-    pass under no_grad): no rows are stored."""
+def _loss3d_set(cfg, gt, n_used, calib, mean_sizes, lv, grad_ptrs, gsw, B, dtype, dev):
+    """one head set (cfg: LossCfg3d) on the HIP kernels over the levels `lv`: assignment + six loss items + gradient rows written at
+    grad_ptrs (pixel strides gsw) -> SetResult.  With cfg.item_w the launch is y3d_loss3d_weighted: the rows come out times the weight
+    of their item, the items as ever, and `total` = sum(item_w * items); grad_ptrs None (a pass under no_grad): no rows are stored."""
     L = lib()
-    strides, nc, topk, alpha, beta, gamma, w = cfg[:7]
-    mode = cfg[7] if len(cfg) > 7 else 11  # assigner mode bits (include/y3d.h: y3d_tal3d_assign); default tal_2d | tal_3d | constrain_anchors, l1
-    item_w = cfg[8] if len(cfg) > 8 else None
-    dt, st, nl = ops.code(dtype), ops.stream(), len(map_ptrs)
-    A = sum(h * w_ for h, w_ in zip(Hs, Ws))
+    nc, w = cfg.nc, cfg.weights
+    dt, st = ops.code(dtype), ops.stream()
     n = gt.shape[1]
-    PV = ctypes.c_void_p * nl
-    c_maps, c_grads = PV(*map_ptrs), (PV(*grad_ptrs) if grad_ptrs is not None else None)
-    c_psw, c_gsw = (ctypes.c_int64 * nl)(*psw), (ctypes.c_int64 * nl)(*gsw)
-    c_H, c_W = (ctypes.c_int * nl)(*Hs), (ctypes.c_int * nl)(*Ws)
-    c_st = (ctypes.c_float * nl)(*strides)
-    nsc = L.tal3d_scratch_floats(B, n, A, topk)
-    if nsc < 0:
-        raise Y3DError("Loss3dFn: assignment scratch exceeds 2^31 floats")
-    scratch = torch.empty(nsc, dtype=torch.float32, device=dev)
-    fg = torch.empty(B, A, dtype=torch.uint8, device=dev)
-    gi = torch.empty(B, A, dtype=torch.int32, device=dev)
-    ts = torch.empty(B, A, nc, dtype=torch.float32, device=dev)
-    scal = torch.empty(2, dtype=torch.float32, device=dev)
-    if _SCAL_TAP is not None:
-        _SCAL_TAP.append(scal)
-    L.tal3d_assign(dt, nl, c_maps, c_psw, c_H, c_W, c_st, B, nc, gt.data_ptr(), n, calib.data_ptr(), mean_sizes.data_ptr(), topk,
-                   alpha, beta, gamma, int(mode), scratch.data_ptr(), fg.data_ptr(), gi.data_ptr(), ts.data_ptr(), scal.data_ptr(),
+    c_grads, c_gsw = lv.rows(grad_ptrs, gsw)
+    scratch, fg, gi, ts, scal = _assignment_buffers(L.tal3d_scratch_floats(B, n, lv.A, cfg.topk), "Loss3dFn", B, lv.A, nc, dev)
+    L.tal3d_assign(dt, lv.nl, lv.maps, lv.psw, lv.H, lv.W, lv.st, B, nc, gt.data_ptr(), n, calib.data_ptr(), mean_sizes.data_ptr(), cfg.topk,
+                   cfg.alpha, cfg.beta, cfg.gamma, int(cfg.mode), scratch.data_ptr(), fg.data_ptr(), gi.data_ptr(), ts.data_ptr(), scal.data_ptr(),
                    n_used.data_ptr() if n_used is not None else None, st)
-    nblk = (B * A + 255) // 256
-    part = torch.empty(nblk * 6, dtype=torch.float32, device=dev)
-    items = torch.empty(6, dtype=torch.float32, device=dev)
-    if item_w is not None:
-        total = torch.empty(1, dtype=torch.float32, device=dev)
-        L.loss3d_weighted(dt, nl, c_maps, c_psw, c_grads, c_gsw, c_H, c_W, c_st, B, nc, gt.data_ptr(), n, fg.data_ptr(), gi.data_ptr(),
-                          ts.data_ptr(), scal.data_ptr(), w[0], w[1], w[2], w[3], w[4], w[5], 1.0, part.data_ptr(), items.data_ptr(),
-                          item_w.data_ptr(), total.data_ptr(), st)
-        return items, fg, gi, ts, total
-    L.loss3d(dt, nl, c_maps, c_psw, c_grads, c_gsw, c_H, c_W, c_st, B, nc, gt.data_ptr(), n, fg.data_ptr(), gi.data_ptr(), ts.data_ptr(),
-             scal.data_ptr(), w[0], w[1], w[2], w[3], w[4], w[5], 1.0, part.data_ptr(), items.data_ptr(), st)
-    return items, fg, gi, ts
+    part, items = _item_buffers(B, lv.A, 6, dev)
+    if cfg.item_w is None:
+        L.loss3d(dt, lv.nl, lv.maps, lv.psw, c_grads, c_gsw, lv.H, lv.W, lv.st, B, nc, gt.data_ptr(), n, fg.data_ptr(), gi.data_ptr(), ts.data_ptr(),
+                 scal.data_ptr(), w[0], w[1], w[2], w[3], w[4], w[5], 1.0, part.data_ptr(), items.data_ptr(), st)
+        return SetResult(items, fg, gi, ts, scal)
+    total = torch.empty(1, dtype=torch.float32, device=dev)
+    L.loss3d_weighted(dt, lv.nl, lv.maps, lv.psw, c_grads, c_gsw, lv.H, lv.W, lv.st, B, nc, gt.data_ptr(), n, fg.data_ptr(), gi.data_ptr(),
+                      ts.data_ptr(), scal.data_ptr(), w[0], w[1], w[2], w[3], w[4], w[5], 1.0, part.data_ptr(), items.data_ptr(),
+                      cfg.item_w.data_ptr(), total.data_ptr(), st)
+    return SetResult(items, fg, gi, ts, scal, total)
 
 
 class Loss3dFn(torch.autograd.Function):
     """One head set: task-aligned assignment (no grad) + the six 3D loss terms + d(sum of terms)/d(head maps), on the fused HIP
-    kernels.  apply(cfg, gt(B,n,17), n_used, calib, mean_sizes, *maps) -> (sum_of_items, items[6], fg_mask, target_gt_idx, target_scores);
-    n_used: device int32 from pad_targets (or None: walk all n rows).  A cfg of `DDDetectionLoss.cfg` with an item-weight table
-    (`set_item_weights`): the weighted entry, sum_of_items = sum(table * items), and no gradient rows when the cfg was made under no_grad."""
+    kernels.  apply(cfg, gt(B,n,17), n_used, calib, mean_sizes, *maps) -> (sum_of_items, items[6], fg_mask, target_gt_idx, target_scores,
+    scal), `SetResult.outputs`; cfg: LossCfg3d; n_used: device int32 from pad_targets (or None: walk all n rows).  With cfg.item_w
+    (`set_item_weights`): the weighted entry, sum_of_items = sum(table * items), and no gradient rows when cfg.store_grads is off."""
 
     @staticmethod
     def forward(ctx, cfg, gt, n_used, calib, mean_sizes, *maps):
         dtype, dev = maps[0].dtype, maps[0].device
-        for m in maps:
-            if not (m.is_cuda and ops.px_dense(m)):
-                raise Y3DError("Loss3dFn: head maps must be pixel-dense NHWC tensors on a HIP device")
+        _check_maps(maps, "Loss3dFn")
         B, no = maps[0].shape[:2]
-        Hs, Ws = [m.shape[2] for m in maps], [m.shape[3] for m in maps]
-        weighted, store = len(cfg) > 8, not (len(cfg) > 9 and not cfg[9])
-        grads = [ops.nhwc_empty(B, no, h, w_, dtype, dev) for h, w_ in zip(Hs, Ws)] if store else []
-        items, fg, gi, ts, *tot = _loss3d_set(cfg, gt.float().contiguous(), n_used, calib.float().contiguous(), mean_sizes.float().contiguous(),
-                                              [m.data_ptr() for m in maps], [m.stride(3) for m in maps],
-                                              [g.data_ptr() for g in grads] if store else None, [no] * len(maps), Hs, Ws, B, dtype, dev)
-        ctx.save_for_backward(*grads)
-        ctx.nmaps = len(maps)
-        ctx.set_materialize_grads(False)  # no zero-filled gradients for the assignment outputs
-        total = tot[0].reshape(()) if weighted else items.sum()
-        ctx.mark_non_differentiable(items, fg, gi, ts)
-        return total, items, fg, gi, ts
+        lv = Levels.of(maps, cfg.strides)
+        grads = [ops.nhwc_empty(B, no, h, w, dtype, dev) for h, w in zip(lv.H, lv.W)] if cfg.store_grads else []
+        r = _loss3d_set(cfg, gt.float().contiguous(), n_used, calib.float().contiguous(), mean_sizes.float().contiguous(), lv,
+                        [g.data_ptr() for g in grads] if cfg.store_grads else None, [no] * lv.nl, B, dtype, dev)
+        return _close_forward(ctx, grads, len(maps), r)
 
     @staticmethod
     def backward(ctx, d_total, *unused):
-        grads = ctx.saved_tensors
-        if d_total is None or not grads:
-            return (None,) * (5 + ctx.nmaps)
-        return (None, None, None, None, None, *[g * d_total.to(g.dtype) for g in grads])
+        return _scaled_rows(ctx, d_total, 5)
 
 
 class DualLoss3dFn(torch.autograd.Function):
@@ -446,35 +519,25 @@ class DualLoss3dFn(torch.autograd.Function):
     v10Detect3d.forward_train_fused writes them): the gradient rows of both sets go into ONE NHWC tensor per level and the backward
     is one broadcast multiply per level.  With the two sets as separate autograd inputs (channel slices of that map) autograd
     zero-fills a full map per slice, copies, adds and re-lays the sum out: 7 elementwise launches per level instead of 1.
-    apply(cfg_o2o, cfg_o2m, gt, n_used, calib, mean_sizes, *maps) -> (total_o2o, items_o2o, total_o2m, items_o2m, fg1, gi1, ts1, fgm, gim, tsm)"""
+    apply(cfg_o2o, cfg_o2m, gt, n_used, calib, mean_sizes, *maps) -> the six outputs of Loss3dFn for the one-to-one set, then the six
+    for the one-to-many set.  Each set takes its own cfg's item weights (`set_item_weights` gives both a table or neither); whether
+    gradient rows are stored is cfg_o2o.store_grads for both"""
 
     @staticmethod
     def forward(ctx, cfg1, cfgm, gt, n_used, calib, mean_sizes, *maps):
         dtype, dev = maps[0].dtype, maps[0].device
-        for m in maps:
-            if not (m.is_cuda and ops.px_dense(m)):
-                raise Y3DError("DualLoss3dFn: head maps must be pixel-dense NHWC tensors on a HIP device")
+        _check_maps(maps, "DualLoss3dFn")
         B, no2 = maps[0].shape[:2]
-        no, esz = no2 // 2, maps[0].element_size()
-        Hs, Ws = [m.shape[2] for m in maps], [m.shape[3] for m in maps]
-        weighted, store = len(cfg1) > 8, not (len(cfg1) > 9 and not cfg1[9])
-        grads = [ops.nhwc_empty(B, no2, h, w_, dtype, dev) for h, w_ in zip(Hs, Ws)] if store else []
+        no, esz, store = no2 // 2, maps[0].element_size(), cfg1.store_grads
+        grads = [ops.nhwc_empty(B, no2, m.shape[2], m.shape[3], dtype, dev) for m in maps] if store else []
         gt, calib, mean_sizes = gt.float().contiguous(), calib.float().contiguous(), mean_sizes.float().contiguous()
-        outs = []
-        for cfg, off in ((cfg1, 0), (cfgm, no)):
-            outs.append(_loss3d_set(cfg, gt, n_used, calib, mean_sizes, [m.data_ptr() + off * esz for m in maps], [m.stride(3) for m in maps],
-                                    [g.data_ptr() + off * esz for g in grads] if store else None, [no2] * len(maps), Hs, Ws, B, dtype, dev))
-        ctx.save_for_backward(*grads)
-        ctx.no, ctx.nmaps = no, len(maps)
-        ctx.set_materialize_grads(False)
-        (i1, fg1, gi1, ts1, *tot1), (im, fgm, gim, tsm, *totm) = outs
-        ctx.mark_non_differentiable(i1, im, fg1, gi1, ts1, fgm, gim, tsm)
-        if weighted:  # the item-weight table is set: the two `total`s of y3d_loss3d_weighted
-            return tot1[0].reshape(()), i1, totm[0].reshape(()), im, fg1, gi1, ts1, fgm, gim, tsm
-        return i1.sum(), i1, im.sum(), im, fg1, gi1, ts1, fgm, gim, tsm
+        r1, rm = [_loss3d_set(cfg, gt, n_used, calib, mean_sizes, Levels.of(maps, cfg.strides, off), [g.data_ptr() + off for g in grads] if store else None,
+                              [no2] * len(maps), B, dtype, dev) for cfg, off in ((cfg1, 0), (cfgm, no * esz))]
+        ctx.no = no
+        return _close_forward(ctx, grads, len(maps), r1, rm)
 
     @staticmethod
-    def backward(ctx, d1, _i1, dm, *unused):
+    def backward(ctx, d1, _i1, _fg1, _gi1, _ts1, _scal1, dm, *unused):
         grads = ctx.saved_tensors
         if (d1 is None and dm is None) or not grads:
             return (None,) * (6 + ctx.nmaps)
@@ -531,30 +594,21 @@ class DDDetectionLoss:
 
     def __call__(self, preds, batch, embeddings=None, targets=None, teacher=None):
         """`targets`: the result of `self.targets(...)` when the caller shares it between the two head sets of a step"""
-        feats = preds[1] if isinstance(preds, tuple) else preds
-        dev = feats[0].device
-        if not feats[0].is_cuda:
-            raise Y3DError("the 3D loss runs on the HIP kernels of tal_loss3d.hip: head maps must live on a HIP device (no CPU fallback)")
-        B = feats[0].shape[0]
-        H, W = feats[0].shape[2:]
-        if targets is None:
-            targets = self.targets(batch, B, H, W, dev)
+        feats, dev, B, img_wh, targets, maps = _head_inputs(self, "3D", preds, batch, targets)
         if targets is None:
             loss = torch.zeros(7 if self.distillation else 6, device=dev)
             return loss.sum() * B, loss  # reference: graph-less zeros (loss.py:873-877); callers skip the step
         g, n_used = targets
-        maps = [f if f.dtype == ops.compute_dtype() else f.to(ops.compute_dtype()) for f in feats]
-        with (_tap_scal() if self.distillation else contextlib.nullcontext()) as tap:
-            total, items, fg, gt_idx, t_sc = Loss3dFn.apply(self.cfg(len(feats)), g, n_used, batch["calib"].to(dev), batch["mean_sizes"].to(dev), *maps)
-        self._assignment = (fg, gt_idx, t_sc)
+        r = SetResult.of(Loss3dFn.apply(self.cfg(len(feats)), g, n_used, batch["calib"].to(dev), batch["mean_sizes"].to(dev), *maps))
+        self._assignment = r[1:4]
         if self.item_w is not None:
-            return total, items
+            return r.total, r.items
         if not self.distillation:
-            return total * B, items
+            return r.total * B, r.items
         if embeddings is None:
             raise Y3DError("distillation: the head's embeddings (preds['o2o_embs'] / preds['o2m_embs']) must be passed as `embeddings`")
-        dis = self.distill(batch, g, embeddings, fg, gt_idx, tap[0], (W * self.stride[0], H * self.stride[0]), teacher=teacher)
-        return (total + dis) * B, torch.cat((items, dis.detach().reshape(1)))
+        dis = self.distill(batch, g, embeddings, r.fg, r.gt_idx, r.scal, img_wh, teacher=teacher)
+        return (r.total + dis) * B, torch.cat((r.items, dis.detach().reshape(1)))
 
     def distill(self, batch, gt, embeddings, fg, gt_idx, scal, img_wh, teacher=None, slots=None, which=0, ties=()):
         """the distillation item of this head set (loss.py:893-898) -> 0-dim tensor tied into the autograd graph (DistillFn)"""
@@ -586,12 +640,10 @@ class DDDetectionLoss:
 
     def cfg(self, nl):
         h = self.hyp
-        cfg = (self.stride[:nl], self.nc, self.topk, float(h.tal_alpha), float(h.tal_beta), float(h.tal_gamma),
-               (float(h.loss2d), float(h.cls), float(h.depth), float(h.offset3d), float(h.size3d), float(h.heading)), self.mode)
-        if self.item_w is None:
-            return cfg
-        # ... the table, and whether gradient rows are wanted (read HERE: inside an autograd Function's forward grad mode is always off)
-        return cfg + (self.item_w, torch.is_grad_enabled())
+        # with a table, whether gradient rows are wanted is read HERE: inside an autograd Function's forward grad mode is always off
+        return LossCfg3d(self.stride[:nl], self.nc, self.topk, float(h.tal_alpha), float(h.tal_beta), float(h.tal_gamma),
+                         (float(h.loss2d), float(h.cls), float(h.depth), float(h.offset3d), float(h.size3d), float(h.heading)), self.mode,
+                         self.item_w, self.item_w is None or torch.is_grad_enabled())
 
     @property
     def last_assignment(self):
@@ -684,94 +736,81 @@ class DetectLoss3d:
         tg = self.one2one.targets(batch, B, H, W, dev) if o2o[0].is_cuda else None  # padded once per step
         kw = {"targets": tg} if tg is not None else {}
         o2m = preds.get("one2many", None)
-        dist = self.one2one.distillation and tg is not None
-        if dist:  # one teacher map per step, shared by both head sets (the reference runs its teacher once per set, loss.py:1159-1160)
+        if self.one2one.distillation and tg is not None:  # one teacher map per step, shared by both head sets (the reference runs its teacher once per set, loss.py:1159-1160)
             kw["teacher"] = teacher_map(batch, like=preds["o2o_embs"][0])
-        if o2m and tg is not None:
-            o2m = o2m[1] if isinstance(o2m, tuple) else o2m
-            bases = self._shared_maps(preds.get("_y3d_maps"), o2o, o2m, self.one2one.no)
-            if bases is not None:
-                g, n_used = tg
-                nl = len(bases)
-                with (_tap_scal() if dist else contextlib.nullcontext()) as tap:
-                    t1, i1, tm, im, fg1, gi1, ts1, fgm, gim, tsm = DualLoss3dFn.apply(self.one2one.cfg(nl), self.one2many.cfg(nl), g, n_used, batch["calib"].to(dev),
-                                                                                      batch["mean_sizes"].to(dev), *bases)
-                self.one2one._assignment, self.one2many._assignment = (fg1, gi1, ts1), (fgm, gim, tsm)
-                if self.one2one.item_w is not None:
-                    return tm + t1, torch.cat((im, i1))
-                if not dist:
-                    return tm * B + t1 * B, torch.cat((im, i1))
-                e1, em = preds["o2o_embs"], preds["o2m_embs"]
-                slots = self._z1_slots(preds.get("_y3d_distill"), e1, em)
-                ties = tuple(bases) if slots is not None else ()
-                wh = (W * self.one2one.stride[0], H * self.one2one.stride[0])
-                d1 = self.one2one.distill(batch, g, e1, fg1, gi1, tap[0], wh, teacher=kw["teacher"], slots=slots, which=0, ties=ties)
-                dm = self.one2many.distill(batch, g, em, fgm, gim, tap[1], wh, teacher=kw["teacher"], slots=slots, which=1, ties=ties)
-                return (tm + dm) * B + (t1 + d1) * B, torch.cat((im, dm.detach().reshape(1), i1, d1.detach().reshape(1)))
+        out = self._dual(preds, batch, o2o, o2m[1] if isinstance(o2m, tuple) else o2m, tg, kw.get("teacher")) if o2m and tg is not None else None
+        return out if out is not None else self._two_calls(preds, batch, kw)
+
+    def _dual(self, preds, batch, o2o, o2m, tg, teacher):
+        """both head sets in one DualLoss3dFn call on the head's own (B, 2*no, H, W) maps (teacher: the step's teacher map under
+        distillation, else None) -> (loss, items), or None when `_shared_maps` refuses"""
+        c1, cm = self.one2one, self.one2many
+        bases = self._shared_maps(preds.get("_y3d_maps"), o2o, o2m, c1.no)
+        if bases is None:
+            return None
+        dev, B, (H, W) = o2o[0].device, o2o[0].shape[0], o2o[0].shape[2:]
+        g, n_used = tg
+        nl = len(bases)
+        out = DualLoss3dFn.apply(c1.cfg(nl), cm.cfg(nl), g, n_used, batch["calib"].to(dev), batch["mean_sizes"].to(dev), *bases)
+        r1, rm = SetResult.of(out[:6]), SetResult.of(out[6:])
+        c1._assignment, cm._assignment = r1[1:4], rm[1:4]
+        items = (rm.items, r1.items)
+        if c1.item_w is not None:
+            loss = rm.total + r1.total
+        elif teacher is None:
+            loss = rm.total * B + r1.total * B
+        else:
+            e1, em = preds["o2o_embs"], preds["o2m_embs"]
+            slots = self._z1_slots(preds.get("_y3d_distill"), e1, em)
+            ties = tuple(bases) if slots is not None else ()
+            wh = (W * c1.stride[0], H * c1.stride[0])
+            d1 = c1.distill(batch, g, e1, r1.fg, r1.gt_idx, r1.scal, wh, teacher=teacher, slots=slots, which=0, ties=ties)
+            dm = cm.distill(batch, g, em, rm.fg, rm.gt_idx, rm.scal, wh, teacher=teacher, slots=slots, which=1, ties=ties)
+            loss = (rm.total + dm) * B + (r1.total + d1) * B
+            items = (rm.items, dm.detach().reshape(1), r1.items, d1.detach().reshape(1))
+        return loss, torch.cat(items)
+
+    def _two_calls(self, preds, batch, kw):
+        """the head sets through their own criteria, one Loss3dFn call each (separate maps, or a batch without boxes)"""
         l1, i1 = self.one2one(preds["one2one"], batch, embeddings=preds.get("o2o_embs"), **kw)
-        if o2m:
-            lm, im = self.one2many(preds["one2many"], batch, embeddings=preds.get("o2m_embs"), **kw)
-            return lm + l1, torch.cat((im, i1))
-        return torch.zeros(1), i1
+        if not preds.get("one2many", None):
+            return torch.zeros(1), i1
+        lm, im = self.one2many(preds["one2many"], batch, embeddings=preds.get("o2m_embs"), **kw)
+        return lm + l1, torch.cat((im, i1))
 
 
 class Loss2dFn(torch.autograd.Function):
     """2D head set: assignment + (box, cls, dfl) + gradient wrt the head maps on the fused HIP kernels of tal_loss2d.hip.
-    apply(cfg, gt(B,n,5), n_used, *maps) -> (sum_of_items, items[3], fg_mask, target_gt_idx, target_scores)"""
+    apply(cfg, gt(B,n,5), n_used, *maps) -> (sum_of_items, items[3], fg_mask, target_gt_idx, target_scores, scal), `SetResult.outputs`;
+    cfg: LossCfg2d"""
 
     @staticmethod
     def forward(ctx, cfg, gt, n_used, *maps):
         L = lib()
-        strides, nc, topk, alpha, beta, w = cfg
-        dtype = maps[0].dtype
-        dt = ops.code(dtype)
-        st = ops.stream()
-        dev = maps[0].device
-        nl = len(maps)
-        for m in maps:
-            if not (m.is_cuda and ops.px_dense(m)):
-                raise Y3DError("Loss2dFn: head maps must be pixel-dense NHWC tensors on a HIP device")
+        nc, topk, w = cfg.nc, cfg.topk, cfg.weights
+        dtype, dev = maps[0].dtype, maps[0].device
+        dt, st = ops.code(dtype), ops.stream()
+        _check_maps(maps, "Loss2dFn")
         B, no = maps[0].shape[:2]
-        Hs = [m.shape[2] for m in maps]
-        Ws = [m.shape[3] for m in maps]
-        A = sum(h * w_ for h, w_ in zip(Hs, Ws))
+        lv = Levels.of(maps, cfg.strides)
         n = gt.shape[1]
         gt = gt.float().contiguous()
-        grads = [ops.nhwc_empty(B, no, h, w_, dtype, dev) for h, w_ in zip(Hs, Ws)]
-        PV = ctypes.c_void_p * nl
-        c_maps, c_grads = PV(*[m.data_ptr() for m in maps]), PV(*[g.data_ptr() for g in grads])
-        c_psw = (ctypes.c_int64 * nl)(*[m.stride(3) for m in maps])
-        c_gsw = (ctypes.c_int64 * nl)(*[no] * nl)
-        c_H, c_W = (ctypes.c_int * nl)(*Hs), (ctypes.c_int * nl)(*Ws)
-        c_st = (ctypes.c_float * nl)(*strides)
+        grads = [ops.nhwc_empty(B, no, h, w_, dtype, dev) for h, w_ in zip(lv.H, lv.W)]
+        c_grads, c_gsw = lv.rows([g.data_ptr() for g in grads], [no] * lv.nl)
         crowded = n > TARGET_CAP  # more rows than the dense assigner takes (`max_boxes`): the route without (B, n, A) planes
-        nsc = L.tal2d_scratch_floats(B, n, A, topk) if crowded else L.tal3d_scratch_floats(B, n, A, topk)
-        if nsc < 0:
-            raise Y3DError("Loss2dFn: assignment scratch exceeds 2^31 floats")
-        scratch = torch.empty(nsc, dtype=torch.float32, device=dev)
-        fg = torch.empty(B, A, dtype=torch.uint8, device=dev)
-        gi = torch.empty(B, A, dtype=torch.int32, device=dev)
-        ts = torch.empty(B, A, nc, dtype=torch.float32, device=dev)
-        scal = torch.empty(2, dtype=torch.float32, device=dev)
+        nsc = L.tal2d_scratch_floats(B, n, lv.A, topk) if crowded else L.tal3d_scratch_floats(B, n, lv.A, topk)
+        scratch, fg, gi, ts, scal = _assignment_buffers(nsc, "Loss2dFn", B, lv.A, nc, dev)
         assign = L.tal2d_assign_crowded if crowded else L.tal2d_assign
-        assign(dt, nl, c_maps, c_psw, c_H, c_W, c_st, B, nc, gt.data_ptr(), n, topk, alpha, beta, scratch.data_ptr(), fg.data_ptr(),
+        assign(dt, lv.nl, lv.maps, lv.psw, lv.H, lv.W, lv.st, B, nc, gt.data_ptr(), n, topk, cfg.alpha, cfg.beta, scratch.data_ptr(), fg.data_ptr(),
                gi.data_ptr(), ts.data_ptr(), scal.data_ptr(), n_used.data_ptr() if n_used is not None else None, st)
-        nblk = (B * A + 255) // 256
-        part = torch.empty(nblk * 3, dtype=torch.float32, device=dev)
-        items = torch.empty(3, dtype=torch.float32, device=dev)
-        L.loss2d(dt, nl, c_maps, c_psw, c_grads, c_gsw, c_H, c_W, c_st, B, nc, gt.data_ptr(), n, fg.data_ptr(), gi.data_ptr(), ts.data_ptr(),
+        part, items = _item_buffers(B, lv.A, 3, dev)
+        L.loss2d(dt, lv.nl, lv.maps, lv.psw, c_grads, c_gsw, lv.H, lv.W, lv.st, B, nc, gt.data_ptr(), n, fg.data_ptr(), gi.data_ptr(), ts.data_ptr(),
                  scal.data_ptr(), w[0], w[1], w[2], 1.0, part.data_ptr(), items.data_ptr(), st)
-        ctx.save_for_backward(*grads)
-        ctx.set_materialize_grads(False)  # no zero-filled gradients for the assignment outputs
-        total = items.sum()
-        ctx.mark_non_differentiable(items, fg, gi, ts)
-        return total, items, fg, gi, ts
+        return _close_forward(ctx, grads, len(maps), SetResult(items, fg, gi, ts, scal))
 
     @staticmethod
     def backward(ctx, d_total, *unused):
-        if d_total is None:
-            return (None,) * (3 + len(ctx.saved_tensors))
-        return (None, None, None, *[g * d_total.to(g.dtype) for g in ctx.saved_tensors])
+        return _scaled_rows(ctx, d_total, 3)
 
 
 class v8DetectionLoss:
@@ -797,14 +836,7 @@ class v8DetectionLoss:
         return pad_targets(rows, B, 5, (W * self.stride[0], H * self.stride[0]), cap=self.max_boxes or TARGET_CAP)
 
     def __call__(self, preds, batch, targets=None):
-        feats = preds[1] if isinstance(preds, tuple) else preds
-        dev = feats[0].device
-        if not feats[0].is_cuda:
-            raise Y3DError("the 2D loss runs on the HIP kernels of tal_loss2d.hip: head maps must live on a HIP device (no CPU fallback)")
-        B = feats[0].shape[0]
-        H, W = feats[0].shape[2:]
-        if targets is None:
-            targets = self.targets(batch, B, H, W, dev)
+        feats, dev, B, _, targets, maps = _head_inputs(self, "2D", preds, batch, targets)
         if targets is None:
             # no boxes at all: background-only classification loss (loss.py:244), dense BCE against zero targets
             sc = _flatten_maps(feats)[..., self.reg_max * 4:]
@@ -812,12 +844,13 @@ class v8DetectionLoss:
             loss = torch.stack((torch.zeros((), device=dev), l_cls, torch.zeros((), device=dev)))
             return loss.sum() * B, loss.detach()
         g, n_used = targets
+        r = SetResult.of(Loss2dFn.apply(self.cfg(len(feats)), g, n_used, *maps))
+        self.last_assignment = (r.fg.bool(), r.gt_idx.long(), r.target_scores)
+        return r.total * B, r.items
+
+    def cfg(self, nl):
         h = self.hyp
-        cfg = (self.stride[: len(feats)], self.nc, self.topk, 0.5, 6.0, (float(h.box), float(h.cls), float(h.dfl)))
-        maps = [f if f.dtype == ops.compute_dtype() else f.to(ops.compute_dtype()) for f in feats]
-        total, items, fg, gt_idx, t_sc = Loss2dFn.apply(cfg, g, n_used, *maps)
-        self.last_assignment = (fg.bool(), gt_idx.long(), t_sc)
-        return total * B, items
+        return LossCfg2d(self.stride[:nl], self.nc, self.topk, 0.5, 6.0, (float(h.box), float(h.cls), float(h.dfl)))
 
 
 class v10DetectLoss:
